@@ -20,6 +20,15 @@ Multi-GPU (torch.distributed.run, one process per GPU): independent frames are s
 over ranks with no data-path collective (weak scaling); the detections of the completed
 frames are gathered to rank 0 with one all_gather over RCCL inside the timed region.
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline figure
+needs: it makes the resident grids, fills the pipeline, times the K steps, writes the last
+step's detections with --dump-outputs DIR, and prints the result line (the roofline block
+comes from the HIP events of the timed ticks themselves, not from a run of its own).
+--full adds every pass that takes a run of its own: the voxeliser's timed calls, the
+per-stage breakdown on the lanes path (and its check against the pipeline), the points-in
+passes (configs[3], the real Kinect views), the per-callback latency pass and the CPU
+baselines with the first timed frame's check against the oracle.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -55,6 +64,13 @@ def parse():
     ap.add_argument("--batch", type=int, default=BATCH)
     ap.add_argument("--frames", type=int, default=0,
                     help="resident grids (0: batch + 8; every frame of a tick reads its own grid)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the passes beside the headline figure: voxeliser timing, per-stage breakdown "
+                         "on the lanes path, points-in passes, per-callback latency, CPU baselines and their "
+                         "checks against the oracle (the options below apply to these passes only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the detections of the last timed step's batch to DIR/scores.npy and "
+                         "DIR/positions.npy (float64)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--point-frames", type=int, default=512,
@@ -147,21 +163,30 @@ def scene_points(synth, rank, s):
     return synth.kinect_scene(N_RAYS, grid=GRID, leaf=LEAF, seed=synth.BASE_SEED + 1000 * rank + s)
 
 
-def make_grids(ctx, dev, nf, rank, synth, c3hlac, torch):
-    """nf resident 256^3 grids: scenes voxelised on the GPU, plus x-shifted copies."""
+def make_grids(ctx, dev, nf, rank, synth, c3hlac, torch, time_voxelize=False):
+    """nf resident 256^3 grids: scenes voxelised on the GPU, plus x-shifted copies.  The
+    scenes are ray-cast on host threads (numpy releases the GIL) while the GPU voxelises the
+    ones before them.  time_voxelize: a second, timed c3h_voxelize call per scene."""
+    from concurrent.futures import ThreadPoolExecutor
     grids, t_vox_ms, n_points = [], [], 0
     per_scene = 4  # the scene and three x-shifts of it (distinct buffers)
-    for s in range(-(-nf // per_scene)):
-        pts = scene_points(synth, rank, s)
+    n_scenes = -(-nf // per_scene)
+    pool = ThreadPoolExecutor(max(1, min(16, host_cpu()[2], n_scenes)))
+    scenes = [pool.submit(scene_points, synth, rank, s) for s in range(n_scenes)]
+    pool.shutdown(wait=False)
+    for s in range(n_scenes):
+        pts = scenes[s].result()
+        scenes[s] = None
         d_pts = torch.from_numpy(pts).to(dev)
         torch.cuda.current_stream(dev).synchronize()
-        # untimed first call per scene: a scene with more points than any before it grows the
-        # voxeliser's buffers (hipMalloc); the timed call is the steady-state per-frame cost
-        ctx.voxelize(d_pts, LEAF)
-        ctx.timing(True)
+        # a scene with more points than any before it grows the voxeliser's buffers
+        # (hipMalloc), so the timed call is a second one: the steady-state per-frame cost
         gi = ctx.voxelize(d_pts, LEAF)
-        t_vox_ms.append(ctx.kernel_times(reset=True)["voxelize"][0])
-        ctx.timing(False)
+        if time_voxelize:
+            ctx.timing(True)
+            gi = ctx.voxelize(d_pts, LEAF)
+            t_vox_ms.append(ctx.kernel_times(reset=True)["voxelize"][0])
+            ctx.timing(False)
         n_points += pts.shape[0]
         assert list(gi.div_b) == [GRID] * 3, list(gi.div_b)
         words = torch.empty(GRID ** 3, dtype=torch.int32, device=dev)
@@ -209,6 +234,19 @@ def torch_mod():
     return torch
 
 
+def write_outputs(out_dir, records):
+    """--dump-outputs: the detection records a caller of c3h_stream_frames receives for one
+    batch, (frames, models x rank, 3) int64 words of DET_DTYPE, as float64 arrays:
+    scores.npy (frames, models x rank) and positions.npy (frames, models x rank, 4) = x, y, z
+    of the box in subdivisions and the rotation mode."""
+    records = np.ascontiguousarray(records, dtype=np.int64)
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "scores.npy", records[:, :, 0].copy().view(np.float64))
+    np.save(out_dir / "positions.npy",
+            records[:, :, 1:3].copy().view(np.int32).reshape(records.shape[:2] + (4,)).astype(np.float64))
+
+
 def main():
     args = parse()
     n_dev = _visible_devices() if args.gpus > 1 and "WORLD_SIZE" not in os.environ else 0
@@ -252,7 +290,7 @@ def main():
     ctx.set_pipeline(True)
 
     nf = args.frames if args.frames > 0 else B + 8
-    grids, t_vox_ms, n_points = make_grids(ctx, dev, nf, rank, synth, c3hlac, torch)
+    grids, t_vox_ms, n_points = make_grids(ctx, dev, nf, rank, synth, c3hlac, torch, time_voxelize=args.full)
 
     axis_t, var, axis_q = synth.random_bases(VARIANT, D, M, R, seed=synth.BASE_SEED)
     ctx.search_setup(axis_t, var, axis_q)
@@ -307,35 +345,38 @@ def main():
     ctx.timing(False)
     ctx.stream_flush()  # drain (untimed): the last batches' detections
     torch.cuda.synchronize(dev)
-    # per-stage breakdown: a separate, untimed pass on the lanes path (separate launches
-    # per stage, events around each)
-    n_sep = min(args.steps * B, 48)
-    ctx.set_pipeline(False)
-    ctx.timing(True)
-    sep_out = torch.zeros((n_sep, M * RANK * 3), dtype=torch.int64, device=dev)
-    ctx.run_frames(gptr[:n_sep], (GRID,) * 3, (0, 0, 0), LEAF, VARIANT, THR, SUBDIV, BOX, EXIST_THR, True,
-                   sep_out.data_ptr())
-    kt_all = ctx.kernel_times(reset=True)
-    ctx.timing(False)
-    ctx.set_pipeline(True)
-    torch.cuda.synchronize(dev)
+    if args.full:
+        # per-stage breakdown: a separate, untimed pass on the lanes path (separate launches
+        # per stage, events around each)
+        n_sep = min(args.steps * B, 48)
+        ctx.set_pipeline(False)
+        ctx.timing(True)
+        sep_out = torch.zeros((n_sep, M * RANK * 3), dtype=torch.int64, device=dev)
+        ctx.run_frames(gptr[:n_sep], (GRID,) * 3, (0, 0, 0), LEAF, VARIANT, THR, SUBDIV, BOX, EXIST_THR, True,
+                       sep_out.data_ptr())
+        kt_all = ctx.kernel_times(reset=True)
+        ctx.timing(False)
+        ctx.set_pipeline(True)
+        torch.cuda.synchronize(dev)
     if dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # every frame (warmup, timed and drained) produced a detection for every model, and the
-    # lanes path agrees with the pipeline on the frames both ran
+    # every frame (warmup, timed and drained) produced a detection for every model, and
+    # (--full) the lanes path agrees with the pipeline on the frames both ran
     d = dets.view(n_total, M * RANK, 3).cpu().numpy()
     scores = d[:, :, 0].view(np.float64)
     # (diagnostics builds can run a subset of the tick's roles: C3H_TICK_ROLES, no checks)
     roles_subset = os.environ.get("C3H_TICK_ROLES") not in (None, "", "15")
     assert roles_subset or np.all(scores > 0), "no detection"
-    assert roles_subset or np.array_equal(sep_out.cpu().numpy(), dets[:n_sep].cpu().numpy()), "pipeline != lanes"
+    if args.full:
+        assert roles_subset or np.array_equal(sep_out.cpu().numpy(), dets[:n_sep].cpu().numpy()), "pipeline != lanes"
+    if args.dump_outputs and rank == 0:  # the batch pushed in the last timed step (completed by the drain)
+        write_outputs(args.dump_outputs, d[n_total - B:])
 
     frames_done = n_done * B
     voxels = GRID ** 3 * frames_done * world
-    search_ms = kt_all["compress"][0] + kt_all["score"][0] + kt_all["replay"][0]
     # the dominant kernel is the tick: in steady state every launch streams one batch's
     # grids and carries the other stages of the three batches before it
     tick_ms, tick_frames = kt["pipeline"]
@@ -343,17 +384,6 @@ def main():
     tick_avg_s = tick_ms / n_ticks / 1e3
     alg_bytes = algorithmic_bytes_c3(GRID, H, VARIANT) * B
     achieved = alg_bytes / tick_avg_s / 1e9
-    # the bytes the tick must move: the grid stream plus the rows of the non-empty
-    # subdivisions only (an empty subdivision keeps exist 0 and every reader gates on it)
-    # and exist, from the frames of the timed region (the context holds the last one)
-    nonempty = int((ctx.exist() > 0).sum())
-    # positions of the last frame that passed the exist gate (scored; the rest are -1)
-    try:
-        scored = int((ctx.scores().reshape(M, -1)[0] >= 0).sum())
-    except (c3hlac.C3HError, ValueError):
-        scored = 0
-    min_bytes = (GRID ** 3 * 4 + nonempty * VARIANT * 4 + H * 4) * B
-    achieved_min = min_bytes / tick_avg_s / 1e9
     result = {
         "metric": "Mvoxels/s C3-HLAC + detections/s sliding-box, 256^3 grid",
         "value": voxels / elapsed / 1e6,
@@ -391,19 +421,8 @@ def main():
         },
         "detections_per_s": P * M * frames_done * world / elapsed,
         "detections_note": "detections_per_s counts every box position x model (SURVEY 8(d)); only the positions "
-                           "passing the exist gate are scored: scored_detections_per_s (gate-passing positions of "
-                           "the last frame, %d of %d, x models x frames/s)" % (scored, P),
-        "scored_detections_per_s": (scored * M * frames_done * world / elapsed) if scored else None,
-        "detections_per_s_search_kernels": (P * M * max(kt_all["score"][1], 1) / (search_ms / 1e3)) if search_ms else None,
+                           "passing the exist gate are scored (--full: scored_detections_per_s)",
         "frames_per_s": frames_done * world / elapsed,
-        "kernel_ms_avg": {k: (v[0] / v[1] if v[1] else None) for k, v in kt_all.items()},
-        "kernel_ms_avg_note": "separate pass of %d frames on the lanes path (stand-alone launches per stage, "
-                              "events around every stage; %d lanes x %d frames per launch, so stages overlap; times "
-                              "are per frame); c3hlac = occupancy pass + tile kernel; score = compress(non-empty "
-                              "rows)+gate launch + score launch with the fused rank-1 replay" % (n_sep, LANES, B),
-        "voxelize_mpoints_per_s": n_points / (sum(t_vox_ms) / 1e3) / 1e6 if sum(t_vox_ms) else None,
-        "voxelize_note": "c3h_voxelize of each 1M-ray scene, HIP events around all of its kernels (an untimed "
-                         "call on the scene first sizes the context's buffers for its point count)",
         "roofline": {
             "kernel": "c3h_tick_kernel (pipeline tick: occupancy stream of one batch + C3 tile pass, compress+gate "
                       "and scoring of the three previous batches)",
@@ -418,6 +437,21 @@ def main():
             "frames_per_launch": B,
             "launches": n_ticks,
             "avg_launch_ms": tick_avg_s * 1e3,
+        },
+    }
+    if args.full:
+        # the bytes the tick must move: the grid stream plus the rows of the non-empty
+        # subdivisions only (an empty subdivision keeps exist 0 and every reader gates on it)
+        # and exist (the context holds the last frame of the lanes pass)
+        nonempty = int((ctx.exist() > 0).sum())
+        # positions of that frame that passed the exist gate (scored; the rest are -1)
+        try:
+            scored = int((ctx.scores().reshape(M, -1)[0] >= 0).sum())
+        except (c3hlac.C3HError, ValueError):
+            scored = 0
+        min_bytes = (GRID ** 3 * 4 + nonempty * VARIANT * 4 + H * 4) * B
+        achieved_min = min_bytes / tick_avg_s / 1e9
+        result["roofline"].update({
             "achieved_min_bytes": achieved_min,
             "frac_min_bytes": achieved_min / HBM_PEAK_GBS,
             "min_bytes_per_frame": min_bytes // B,
@@ -425,16 +459,32 @@ def main():
                               "feature rows of the %d non-empty subdivisions only (of %d) and exist; 'achieved' / "
                               "'frac' use SURVEY 8(d)'s algorithmic bytes, which charge a row to every "
                               "subdivision" % (nonempty, H),
-        },
-    }
-    if args.point_frames > 0:
+        })
+        search_ms = kt_all["compress"][0] + kt_all["score"][0] + kt_all["replay"][0]
+        result.update({
+            "scored_detections_note": "gate-passing positions of the last frame of the lanes pass, %d of %d, x models "
+                                      "x frames/s" % (scored, P),
+            "scored_detections_per_s": (scored * M * frames_done * world / elapsed) if scored else None,
+            "detections_per_s_search_kernels": (P * M * max(kt_all["score"][1], 1) / (search_ms / 1e3))
+            if search_ms else None,
+            "kernel_ms_avg": {k: (v[0] / v[1] if v[1] else None) for k, v in kt_all.items()},
+            "kernel_ms_avg_note": "separate pass of %d frames on the lanes path (stand-alone launches per stage, "
+                                  "events around every stage; %d lanes x %d frames per launch, so stages overlap; "
+                                  "times are per frame); c3hlac = occupancy pass + tile kernel; score = "
+                                  "compress(non-empty rows)+gate launch + score launch with the fused rank-1 replay"
+                                  % (n_sep, LANES, B),
+            "voxelize_mpoints_per_s": n_points / (sum(t_vox_ms) / 1e3) / 1e6 if sum(t_vox_ms) else None,
+            "voxelize_note": "c3h_voxelize of each 1M-ray scene, HIP events around all of its kernels (an untimed "
+                             "call on the scene first sizes the context's buffers for its point count)",
+        })
+    if args.full and args.point_frames > 0:
         result["points_in"] = points_pass(ctx, dev, rank, world, dist, torch, synth, c3hlac, args.point_frames,
                                           args.host_point_frames)
         if world == 1:
             result["points_in_real_views"] = real_views_pass(ctx, dev, torch, synth, c3hlac)
-    if world == 1 and args.single_frames > 0:
+    if args.full and world == 1 and args.single_frames > 0:
         result["single_frame"] = single_frame_pass(local, torch, synth, c3hlac, rank, args.single_frames)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         f0 = args.warmup * B  # the first timed frame: the oracle re-computes it as it is timed
         rec0 = d[f0]
         result["cpu_baseline"] = cpu_baseline(grids[f0 % nf].cpu().numpy().view(np.uint32), rec0, args.cpu_seconds,

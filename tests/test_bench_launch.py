@@ -65,8 +65,10 @@ def test_relay_keeps_only_the_result_line_on_stdout():
 
 
 def test_bench_exits_nonzero_without_devices():
-    """This container has no HIP device: --gpus 2 must fail loudly, not run one rank."""
+    """With no HIP device visible (the child sees none, whatever the box has): --gpus 2 must
+    fail loudly, not run one rank."""
     env = {k: v for k, v in __import__("os").environ.items() if k not in ("WORLD_SIZE", "C3H_BENCH_REHEARSAL")}
+    env["HIP_VISIBLE_DEVICES"] = env["CUDA_VISIBLE_DEVICES"] = "-1"
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2"], capture_output=True, text=True,
                        env=env, timeout=300)
     assert r.returncode == 2, r.stderr[-2000:]

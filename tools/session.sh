@@ -52,12 +52,12 @@ for step in "$@"; do
     test=*) t=${step#test=}; n=$(basename ${t%%::*} .py)
       timeout -k 10 600 $PYT "$t" > $O/test_$n.txt 2>&1 || exit 11 ;;
     smoke) timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || exit 12 ;;
-    bench) timeout -k 10 600 python -u bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || exit 13 ;;
+    bench) timeout -k 10 600 python -u bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || exit 13 ;;
     prof) prof 600 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- \
-            python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --single-frames 0 > $O/prof_bench.json 2> $O/prof_bench.err || exit 14
+            python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --single-frames 0 > $O/prof_bench.json 2> $O/prof_bench.err || exit 14
           python3 tools/tick_trace.py $O/prof/run_kernel_trace.csv 5 20 $O/prof_bench.json > $O/tick_trace.json || exit 14 ;;
     rehearse=*) n=${step#rehearse=}
-      C3H_BENCH_REHEARSAL=1 timeout -k 10 600 python -u bench.py --gpus $n --steps 5 --warmup 2 --no-cpu-baseline \
+      C3H_BENCH_REHEARSAL=1 timeout -k 10 600 python -u bench.py --full --gpus $n --steps 5 --warmup 2 --no-cpu-baseline \
         > $O/rehearse_$n.json 2> $O/rehearse_$n.err || exit 25 ;;
     pmc) bash tools/pmc.sh $TAG > $O/pmc.log 2>&1 || exit 15 ;;
     shard) timeout -k 10 500 python -u tools/points_shard.py ${SHARD_B:-64,32,16} 3 > $O/shard.jsonl 2> $O/shard.err || exit 16 ;;
