@@ -740,7 +740,8 @@ C3Args build_c3_args(const C3Launch& l) {
   c.bits = vec && l.ntiles <= kOccBitsMax;
   c.ax = l.gx + l.gy + l.gz <= kAxLds;
   c.vec = vec;
-  const int unroll = c.bits ? kOccBitsUnroll : kOccUnroll;
+  // the bitmap body's chunk is the depth of the path this grid takes (occ_sched.h)
+  const int unroll = c.bits ? occ_depth(occ_rowwave(l.gx, c.ax)) : kOccUnroll;
   c.g1 = (int)std::max<int64_t>(1, std::min<int64_t>((items + kBlock * unroll - 1) / (kBlock * unroll), occ_cap));
   c.occ_lds = c.bits ? occ_bits_lds_bytes(l.ntiles) : 0;
   OccArgs& oa = c.oa;

@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "c3h_internal.h"
+#include "occ_sched.h"
 
 namespace c3h {
 
@@ -147,10 +148,9 @@ struct OccArgs {
 // into an LDS list and stamps kBlock tiles at a time, every exchange in flight together.
 constexpr int kOccBitsMax = 1 << 18;  // 32 KB of LDS bits (512^3 at S >= 8)
 // 16 loads per lane issued together, not software-pipelined: the same 64 VGPRs of data in
-// flight as 2 x 8 pipelined, 4 % shorter tick (profiles/r1/v2_occ_variants.log, v3)
-#ifndef C3H_OCC_UNROLL
-#define C3H_OCC_UNROLL 16
-#endif
+// flight as 2 x 8 pipelined, 4 % shorter tick (profiles/r1/v2_occ_variants.log, v3).  The
+// depths (C3H_OCC_UNROLL: general path, C3H_OCC_ROW_UNROLL: row-wave path) and the chunk
+// schedule are in occ_sched.h, shared with the host.
 #ifndef C3H_OCC_PIPE
 #define C3H_OCC_PIPE 0
 #endif
@@ -170,7 +170,7 @@ constexpr bool kOccArith = C3H_OCC_ARITH;
 #ifndef C3H_OCC_RING
 #define C3H_OCC_RING 0
 #endif
-constexpr int kOccBitsUnroll = C3H_OCC_UNROLL;  // 16-B non-temporal loads per lane per chunk
+static_assert(kOccSchedBlock == kBlock, "occ_sched.h: threads per streaming workgroup");
 constexpr bool kOccPipe = C3H_OCC_PIPE;         // next chunk's loads issued before this one is used
 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 constexpr int kAxLds = 3072;  // axis-map entries kept in LDS (gx + gy + gz <= 3072)
@@ -281,9 +281,10 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
   // 6.9-7.0 TB/s vs 6.0-6.3 for default-policy loads.  Past the grid end the address is
   // clamped and the value zeroed (no per-element branch around the load).
   const int64_t cstride = (int64_t)gdx * kChunk4;
-  auto load_chunk = [&](uint4 (&dst)[kOccBitsUnroll], int64_t c) {
+  auto load_chunk = [&](auto& dst, int64_t c) {
+    constexpr int kN = (int)std::extent_v<std::remove_reference_t<decltype(dst)>>;
 #pragma unroll
-    for (int j = 0; j < kOccBitsUnroll; ++j) {
+    for (int j = 0; j < kN; ++j) {
       const int64_t i = c + j * kBlock + tid;
       const v4u t = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(g4) + (i < n4 ? i : n4 - 1));
       dst[j] = i < n4 ? make_uint4(t.x, t.y, t.z, t.w) : make_uint4(0, 0, 0, 0);
@@ -323,27 +324,67 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
       }
     }
     const bool pair_ok = C3H_OCC_PAIR && __ballot(cplx) == 0ull;  // uniform
-    // Chunk i of this workgroup is chunk i * gdx + (bx + i) % gdx of the frame: rotated, so
-    // every workgroup visits every y band of the grid (a fixed stride would give workgroup
-    // bx the same rows of every plane, and frames' occupancy varies with y: the workgroups of
-    // one frame ended up to 70 us apart, profiles/r1/tq3_occ_spread.txt).
+    // The chunk schedule (occ_sched.h): a workgroup's own chunks are rotated over the frame,
+    // or, for large stand-alone grids, one contiguous range (a tile's 10 planes meet few
+    // workgroups, so the flush stamps each tile ~2.5x fewer times on a dense 512^3 frame);
+    // with the tick's tail stealing this frame's own chunks end at nstat.
+    constexpr int kRow = kOccRowUnroll;       // this path's depth
+    constexpr int kChunkR = kBlock * kRow;    // 16-B words per chunk
     const int lg = gx == 256 ? 8 : gx == 512 ? 9 : 10;
-    const int64_t nch = (n4 + kChunk4 - 1) / kChunk4;
-    uint4 w[kOccBitsUnroll];
-    // large stand-alone grids: contiguous ranges (a tile's 10 planes meet few workgroups,
-    // so the flush stamps each tile ~2.5x fewer times on a dense 512^3 frame)
-    const int64_t per = (nch + gdx - 1) / gdx;
-    auto chunk_of = [&](int64_t i) {
-      return oa.contiguous ? (i < per ? bx * per + i : nch) : i * gdx + (bx + i) % gdx;
+    const OccSched sc =
+        occ_sched(n4, kRow, gdx, oa.contiguous, oa.steal_from, oa.steal_unit, oa.steal_units, oa.nframes);
+    const int64_t nch = sc.nch, nstat = sc.nstat;
+    uint4 w[kRow];
+    auto chunk_of = [&](int64_t i) { return occ_chunk_of(sc, bx, i); };
+    // Whole chunks (all but a frame's last, if that is partial) take unclamped, unpredicated
+    // loads: the chunk's base and the step per load are wave-uniform (scalar registers), the
+    // lane adds tid * 16 -- one address VGPR for all kRow loads, where load_chunk's clamp
+    // and zero-select cost an address pair and a predicate per load in flight.
+    // The empty asm statements pin that split: left visible, the compiler hoists the kRow
+    // frame-relative bases out of the chunk loop (SGPR spills), or folds the lane offset
+    // into the base first and keeps 64-bit address VGPR pairs again.  Per load the ISA is
+    // s_add_u32, s_addc_u32, global_load_dwordx4 v, v_off, s[base] nt; all kRow are issued
+    // before the first s_waitcnt vmcnt.  This, not more loads in flight, is the gain: the tick
+    // is 3-4 % shorter at the same depth of 16 and longer at 20 and 24 (occ_sched.h).
+    auto load_row = [&](uint64_t base, uint32_t voff, int j) {  // load j: the lane's word of a wave's grid row
+      uint64_t bj = base + (uint64_t)j * (kBlock * 16);
+      asm volatile("" : "+s"(bj));
+      typedef const __attribute__((address_space(1))) char* gptr;  // global (from an integer it would be flat)
+      const v4u t = __builtin_nontemporal_load(
+          reinterpret_cast<const __attribute__((address_space(1))) v4u*>(reinterpret_cast<gptr>(bj) + voff));
+      return make_uint4(t.x, t.y, t.z, t.w);
     };
-    // the tick's tail stealing (row-wave path): this frame's own chunks end at nstat
-    const int64_t nstat = oa.steal_unit > 0 ? oa.steal_from : nch;
+    // a chunk's base (uniform) and the lane offset, both made opaque once per chunk
+    auto chunk_base = [&](int64_t c, uint32_t& voff) {
+      uint64_t base = reinterpret_cast<uint64_t>(g4) + (uint64_t)c * (kChunkR * 16);
+      voff = (uint32_t)tid * 16u;
+      asm volatile("" : "+s"(base), "+v"(voff));
+      return base;
+    };
+    // A frame's partial last chunk: n4 is a multiple of 64 on this path (gx of 256), so the 64
+    // words of a wave's load lie all inside the frame or all past its end.  One uniform test
+    // per load instead of load_chunk's per-lane clamp, whose address pair per load is
+    // hoisted out of the chunk loop and spills at depths above 16 (50 VGPRs at 24) although
+    // the chunk is met once per frame.
+    auto load_any = [&](int64_t c) {
+      uint32_t voff;
+      if (occ_chunk_whole(sc, c)) {  // uniform
+        const uint64_t base = chunk_base(c, voff);
+#pragma unroll
+        for (int j = 0; j < kRow; ++j) w[j] = load_row(base, voff, j);
+      } else {
+        const uint64_t base = chunk_base(c, voff);
+#pragma unroll
+        for (int j = 0; j < kRow; ++j)
+          w[j] = occ_wave_load_inside(sc, c, j, wv) ? load_row(base, voff, j) : make_uint4(0, 0, 0, 0);
+      }
+    };
     // rows are mostly empty: skip a row unless some lane of the wave holds a voxel of it
     // (one ballot), look its (y, z) segment up only then
     auto proc = [&](uint32_t row0) {
       int y = (int)(row0 % (uint32_t)gy), z = (int)(row0 / (uint32_t)gy);
 #pragma unroll
-      for (int j = 0; j < kOccBitsUnroll; ++j) {
+      for (int j = 0; j < kRow; ++j) {
         const int yj = y, zjj = z;
         y += rpj;
         while (y >= gy) {
@@ -381,25 +422,24 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
     };
 #if C3H_OCC_RING
     // Rolling ring over whole chunks: slot j of the next chunk is loaded the moment slot j
-    // of this chunk has been read, so each lane keeps kOccBitsUnroll loads in flight all
+    // of this chunk has been read, so each lane keeps kRow loads in flight all
     // the time (the oldest is always the one waited for: vmcnt(unroll - 1)) instead of
     // draining to zero at every chunk end.  The loads carry no predicate (whole chunks
     // only), so none is sunk into a branch (a predicated load forces vmcnt(0) before the
     // first use).  A partial last chunk, if any, takes the loop below.
-    const int64_t nfull = min(n4 / kChunk4, nstat);  // whole chunks of this frame's own share
+    const int64_t nfull = min(n4 / kChunkR, nstat);  // whole chunks of this frame's own share
     int64_t ri = 0;
     if (chunk_of(0) < nfull) {
       // buffer loads off a per-chunk descriptor: one address VGPR (tid * 16) for all
       // slots, the slot offset j * 4 KB in an SGPR, non-temporal (aux 2)
-      const uint32_t voff = (uint32_t)tid * 16u;
 #if C3H_OCC_RING == 2  // diagnostics: global loads off a per-chunk base
-      auto chunk_rsrc = [&](int64_t c) { return reinterpret_cast<const char*>(g4 + c * kChunk4); };
+      auto chunk_rsrc = [&](int64_t c) { return reinterpret_cast<const char*>(g4 + c * kChunkR); };
       auto ring_load = [&](const char* r, int j) {
         return __builtin_nontemporal_load(reinterpret_cast<const v4u*>(r + voff + j * kBlock * 16));
       };
 #else
       auto chunk_rsrc = [&](int64_t c) {
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(g4 + c * kChunk4), (short)0, kChunk4 * 16, 0x00020000);
+        return __builtin_amdgcn_make_buffer_rsrc((void*)(g4 + c * kChunkR), (short)0, kChunkR * 16, 0x00020000);
       };
       auto ring_load = [&](__amdgpu_buffer_rsrc_t r, int j) {
         return __builtin_amdgcn_raw_buffer_load_b128(r, voff, j * kBlock * 16, 2);
@@ -409,14 +449,14 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
       {
         const auto r = chunk_rsrc(cur);
 #pragma unroll
-        for (int j = 0; j < kOccBitsUnroll; ++j) {
+        for (int j = 0; j < kRow; ++j) {
           const v4u t = ring_load(r, j);
           w[j] = make_uint4(t.x, t.y, t.z, t.w);
         }
       }
       // one chunk; kIssue: slot j of chunk nxt is loaded right after slot j is read
       auto run_chunk = [&](auto issue, int64_t c, int64_t nxt) {
-        const uint32_t row0 = (uint32_t)(((uint64_t)c * kChunk4 * 4 + (uint64_t)wv * 256) >> lg);
+        const uint32_t row0 = (uint32_t)(((uint64_t)c * kChunkR * 4 + (uint64_t)wv * 256) >> lg);
         int y = (int)(row0 % (uint32_t)gy), z = (int)(row0 / (uint32_t)gy);
         const auto rn = chunk_rsrc(decltype(issue)::value ? nxt : c);
         auto refill = [&](int j) {  // slot j of the next chunk, once slot j is consumed
@@ -426,7 +466,7 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
           }
         };
 #pragma unroll
-        for (int j = 0; j < kOccBitsUnroll; ++j) {
+        for (int j = 0; j < kRow; ++j) {
           if (j > 0) refill(j - 1);  // the previous slot is dead: its registers are reused
           const uint32_t ws[4] = {w[j].x, w[j].y, w[j].z, w[j].w};
           const int yj = y, zjj = z;
@@ -448,7 +488,7 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
             }
           }
         }
-        refill(kOccBitsUnroll - 1);
+        refill(kRow - 1);
       };
       for (;;) {  // chunk_of is increasing: the ring covers exactly the chunks below nfull
         const int64_t nxt = chunk_of(ri + 1);
@@ -462,21 +502,21 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
         }
       }
     }
-    for (int64_t i = ri; i * gdx < nch; ++i) {
+    for (int64_t i = ri; i < sc.per; ++i) {
       if (chunk_of(i) < nfull) continue;  // streamed by the ring (uniform)
 #else
-    if (kOccPipe && chunk_of(0) < nch) load_chunk(w, chunk_of(0) * kChunk4);
-    for (int64_t i = 0; i * gdx < nch; ++i) {
+    if (kOccPipe && chunk_of(0) < nch) load_chunk(w, chunk_of(0) * kChunkR);
+    for (int64_t i = 0; i < sc.per; ++i) {
 #endif
       const int64_t cidx = chunk_of(i);
       if (cidx >= nstat) continue;  // uniform: the last, partial round / the pooled tail
-      const int64_t c0 = cidx * kChunk4;
-      uint4 nx[kOccBitsUnroll];
+      const int64_t c0 = cidx * kChunkR;
+      uint4 nx[kRow];
       if constexpr (kOccPipe) {  // the next chunk's loads in flight while this one is processed
         const int64_t cn = chunk_of(i + 1);
-        if (cn < nch) load_chunk(nx, cn * kChunk4);
+        if (cn < nch) load_chunk(nx, cn * kChunkR);
       } else {
-        load_chunk(w, c0);
+        load_any(cidx);
       }
       // uniform 32-bit row arithmetic (rows < 2^24: nvox < 2^32 is host-checked): the
       // chunk's first row, then (y, z) stepped by whole rows per j
@@ -485,7 +525,7 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
       {
         uint32_t o = 0;
 #pragma unroll
-        for (int j = 0; j < kOccBitsUnroll; ++j) o |= w[j].x | w[j].y | w[j].z | w[j].w;
+        for (int j = 0; j < kRow; ++j) o |= w[j].x | w[j].y | w[j].z | w[j].w;
         if (o == 0x12345678u) atomicOr(&s_bits[0], 1u);
         continue;
       }
@@ -493,7 +533,7 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
       proc(row0);
       if constexpr (kOccPipe) {
 #pragma unroll
-        for (int j = 0; j < kOccBitsUnroll; ++j) w[j] = nx[j];
+        for (int j = 0; j < kRow; ++j) w[j] = nx[j];
       }
     }
     __syncthreads();
@@ -506,23 +546,23 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
         __syncthreads();  // the flush is done with the bitmap, list and scan scratch
         if (tid == 0) s_wsum[15] = (int)atomicAdd(pool, 1u);
         __syncthreads();
-        const int u = s_wsum[15];
-        if (u >= oa.steal_units) {  // uniform
+        const int u = __builtin_amdgcn_readfirstlane(s_wsum[15]);  // uniform: scalar chunk bases below
+        if (u >= oa.steal_units) {
           if (tid == 0 && atomicAdd(oa.tf + 1, 1u) == (uint32_t)oa.steal_wgs - 1) {
             atomicExch(pool, 0u);
             atomicExch(oa.tf + 1, 0u);
           }
           break;
         }
-        const int fu = u % oa.nframes, ju = u / oa.nframes;
+        const OccUnit un = occ_unit(sc, u);
+        const int fu = un.frame;
         for (int i = tid; i < nwords; i += kBlock) s_bits[i] = 0u;
         last = -1;  // another frame's bitmap
         g4 = reinterpret_cast<const uint4*>(oa.grid[fu]);
         __syncthreads();
-        const int64_t cb = nstat + (int64_t)ju * oa.steal_unit, ce = min(nch, cb + oa.steal_unit);
-        for (int64_t c = cb; c < ce; ++c) {
-          load_chunk(w, c * kChunk4);
-          proc((uint32_t)(((uint64_t)c * kChunk4 * 4 + (uint64_t)wv * 256) >> lg));
+        for (int64_t c = un.cb; c < un.ce; ++c) {
+          load_any(c);
+          proc((uint32_t)(((uint64_t)c * kChunkR * 4 + (uint64_t)wv * 256) >> lg));
         }
         __syncthreads();
         occ_flush_bits(s_bits, nwords, s_list, s_wsum, epoch, oa.tf + fu * oa.s_tf + 4,

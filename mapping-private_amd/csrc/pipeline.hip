@@ -297,15 +297,16 @@ hipError_t launch_tick(const TickParts& p, hipStream_t s) {
 #define C3H_TICK_STEAL_UNIT 8
 #endif
     const int64_t n4 = (int64_t)c.oa.gx * c.oa.gy * c.oa.gz / 4;
-    const int64_t nch = (n4 + (int64_t)kBlock * kOccBitsUnroll - 1) / ((int64_t)kBlock * kOccBitsUnroll);
-    const bool rowwave = c.ax && (c.oa.gx & 255) == 0 && 1024 % c.oa.gx == 0;
+    // chunks of the depth the launch takes (occ_sched.h: the row-wave path has its own)
+    const bool rowwave = occ_rowwave(c.oa.gx, c.ax);
+    const int64_t nch = occ_nchunks(n4, occ_depth(rowwave));
     const int div = env_int("C3H_TICK_STEAL_DIV", C3H_TICK_STEAL_DIV);
     const int unit = env_int("C3H_TICK_STEAL_UNIT", C3H_TICK_STEAL_UNIT);
-    if (rowwave && div > 0 && unit > 0 && nch >= 2 * div) {
-      const int64_t tail = nch / div;
-      t.oa.steal_from = (int)(nch - tail);
-      t.oa.steal_unit = unit;
-      t.oa.steal_units = (int)(c.nframes * ((tail + unit - 1) / unit));
+    const OccSteal st = rowwave ? occ_steal_plan(nch, c.nframes, div, unit) : OccSteal{0, 0, 0};
+    if (st.unit > 0) {
+      t.oa.steal_from = st.from;
+      t.oa.steal_unit = st.unit;
+      t.oa.steal_units = st.units;
       t.oa.nframes = c.nframes;
       t.oa.steal_wgs = t.n_occ;
     }
