@@ -260,13 +260,17 @@ int c3h_search_setup(c3h_ctx* ctx, const float* axis_p, const float* var, int32_
  * searches those rounded rows (widened to f32) until the next extract, so the 1e-5 bound of
  * fp32 precision holds only for features extracted at fp16 = 0: re-extract after switching. */
 int c3h_set_search_precision(c3h_ctx* ctx, int32_t fp16);
-/* Engine of the single-frame search's projection step (SearchObjMulti::searchPart's
- * M x r x D products, search.cpp:915-968): 0 = automatic (default: the matrix cores for
+/* Engine of the search's projection step (SearchObjMulti::searchPart's M x r x D products,
+ * search.cpp:915-968).  Single-frame searches: 0 = automatic (default: the matrix cores for
  * grids of >= 65,536 subdivisions and for models with r > 64, the VALU list kernel
  * otherwise), 1 = VALU (score_list_kernel for r <= 64; the generic kernel beyond),
  * 2 = matrix cores (score_mfma_kernel, v_mfma_f32_32x32x2_f32; D <= 160).
+ * Pipelined searches (c3h_run_frames / c3h_stream_frames with c3h_set_pipeline): 0 = the
+ * matrix cores when the models span more than one 64-column group (M * r > 64), the VALU
+ * score role otherwise; 1 = VALU; 2 = matrix cores whatever the group count.  Batches on
+ * the lanes path always use the VALU kernel.
  * Both engines form every product as the same k-ordered fp32 fma chain, so the scores are
- * bit-identical.  Batched / pipelined searches (c3h_run_frames) always use the VALU kernel. */
+ * bit-identical. */
 int c3h_set_score_engine(c3h_ctx* ctx, int32_t engine);
 /* SearchObj::setRank / SearchObjMulti::setRank (search.cpp:130-143, 778-815):
  * (re)allocates the per-model lists; modes start at S_MODE_1. */

@@ -224,7 +224,8 @@ class Context:
         return self.subdiv, self.hist_num
 
     def set_score_engine(self, engine):
-        """c3h_set_score_engine: 0 automatic, 1 VALU, 2 matrix cores (single-frame search)."""
+        """c3h_set_score_engine: 0 automatic, 1 VALU, 2 matrix cores (single-frame searches and
+        the pipelined tick's score role; the scores are bit-identical)."""
         self._chk(self.lib.c3h_set_score_engine(self.h, int(engine)), "set_score_engine")
 
     def set_search_precision(self, fp16):

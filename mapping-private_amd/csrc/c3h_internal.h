@@ -448,6 +448,9 @@ struct SparseSearch {
   // model-0 score is already -1 has -1 for every model (writers always fill all models of
   // a position), so the gate rewrites only positions that passed last time
   int sparse_scores = 0;
+  // c3h_set_score_engine of the context that runs the tick (read by launch_tick): 1 keeps the
+  // tick's score role on the VALU, 0 / 2 see launch_tick
+  int score_engine = 0;
 };
 bool score_mfma_ok(int D);  // D fits score_mfma_kernel
 // sparse compress fused into the gate launch (nullable in launch_sparse_search)

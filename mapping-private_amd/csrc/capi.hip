@@ -2327,6 +2327,7 @@ int pipe_prepare(c3h_ctx* ctx, const uint32_t* const* grids, c3h_det* const* out
   if (rc == C3H_OK) rc = search_frames(c, nb, k.range, k.thr, k.rotate, outs, 2);
   c->capture = false;
   c->cap_q.lim = lim;  // canvas frames: each frame's own subdivisions bound its positions
+  c->cap_q.score_engine = ctx->score_engine;  // the tick's score role (launch_tick)
   if (rc < 0) {
     if (c != ctx) ctx->err = c->err;
     return rc;

@@ -33,6 +33,7 @@ struct TickArgs {
   int n_score, n_cg, n_tile, n_occ;  // workgroups per role (all frames of its batch)
   SparseSearch sq;                   // score role
   int s_gx, s_groups;
+  int s_mpp;                         // > 0: the score role on the matrix cores, models per pass
   SparseSearch gq;                   // compress + gate role
   CompressRows cr;
   int g_ngate, g_ncomp;
@@ -127,7 +128,8 @@ __device__ __forceinline__ void tick_roles(const TickArgs& t, uint32_t* tick_sme
   b -= t.n_cg;
   C3H_SETPRIO(C3H_TICK_PRIO_SCORE);
   role_frame(b, t.s_gx * t.s_groups, t.xcd & 8, f, r);
-  score_list_body(t.sq, r % t.s_gx, r / t.s_gx, f, t.s_gx, t.s_groups, reinterpret_cast<float*>(tick_smem));
+  if (t.s_mpp > 0) score_tick_mfma_body(t.sq, r, f, t.s_gx, t.s_mpp, reinterpret_cast<float*>(tick_smem));
+  else score_list_body(t.sq, r % t.s_gx, r / t.s_gx, f, t.s_gx, t.s_groups, reinterpret_cast<float*>(tick_smem));
 }
 
 // waves per SIMD the register allocation must allow (4: the 128-VGPR cap); diagnostics builds
@@ -240,7 +242,18 @@ hipError_t launch_tick(const TickParts& p, hipStream_t s) {
 #ifndef C3H_TICK_GROUP_LOOP
 #define C3H_TICK_GROUP_LOOP 1
 #endif
-    if (C3H_TICK_GROUP_LOOP && t.s_groups > 1 && a.D * kOC >= kFP * (kOC + 1)) {
+    // the projection on the matrix cores (round 8, score_tick_mfma_body): one workgroup per
+    // list chunk covers every model, no basis window and no group loop.  Taken when there is
+    // more than one model group (a single group has no window to re-stage); c3h_set_score_engine
+    // 1 keeps the VALU body, 2 takes the matrix cores for a single group too
+#ifndef C3H_TICK_SCORE_MFMA
+#define C3H_TICK_SCORE_MFMA 1
+#endif
+    if (env_int("C3H_TICK_SCORE_MFMA", C3H_TICK_SCORE_MFMA) && a.score_engine != 1 &&
+        (t.s_groups > 1 || a.score_engine == 2)) {
+      t.s_mpp = score_tick_mpp(a.D, a.M, a.r, a.mpg);
+      t.s_groups = 1;
+    } else if (C3H_TICK_GROUP_LOOP && t.s_groups > 1 && a.D * kOC >= kFP * (kOC + 1)) {
       t.sq.group_loop = 1;
       t.s_groups = 1;
     }

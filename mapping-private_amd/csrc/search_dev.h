@@ -647,6 +647,69 @@ __device__ void argmax_finalize(const SparseSearch& a, const ScorePartial* parti
   }
 }
 
+// Box sums of a list chunk's kFP positions into fT (D x kFP, k-major), in the fixed (dz, dy, dx)
+// order over non-empty rows; lane = position.  Cells go in batches of kCB x (this thread's d4
+// slots): every load of a batch is in flight together.  Rows of empty subdivisions read as 0
+// (their G rows may be stale; +0 added to a sum that starts at +0 changes nothing) -- for C3
+// extracts, where exist 0 means empty (skip_empty); other features add every row.
+// gate / hrow / rng: the chunk's per-position flags, first rows and packed box ranges (LDS).
+__device__ __forceinline__ void score_gather_rows(const SparseSearch& a, const float* __restrict__ fG,
+                                                  const int32_t* __restrict__ fexist, const int* gate,
+                                                  const int* hrow, const int* rng, float* fT) {
+  const int tid = threadIdx.x, D4 = a.D >> 2, xyn = a.xn * a.yn;
+  const int pp = tid & (kFP - 1), dg = tid / kFP;
+  constexpr int kDG = kBlock / kFP;  // d4 stride
+  const bool ok = gate[pp];
+  const int h = hrow[pp], rr = rng[pp];
+  const int xr = rr & 1023, yr = (rr >> 10) & 1023, zr = rr >> 20;
+  const int ncell = ok ? xr * yr * zr : 0;
+  const float4* G4 = reinterpret_cast<const float4*>(fG);
+  constexpr int kSlots = 4;  // d4 values per thread handled together (D4 <= 64)
+  constexpr int kCB = C3H_SCORE_CB;  // box cells whose loads are in flight together
+  float4 s[kSlots];
+#pragma unroll
+  for (int q = 0; q < kSlots; ++q) s[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int d4b = 0; d4b < D4; d4b += kSlots * kDG) {
+    for (int c0 = 0; c0 < ncell; c0 += kCB) {
+      float4 g[kCB][kSlots];
+      bool lv[kCB];
+#pragma unroll
+      for (int k = 0; k < kCB; ++k) {
+        const int c = c0 + k;
+        const int dx = c % xr, dy = (c / xr) % yr, dz = c / (xr * yr);
+        const int hh = h + dz * xyn + dy * a.xn + dx;
+        lv[k] = c < ncell && (!a.skip_empty || fexist[c < ncell ? hh : h] != 0);
+#pragma unroll
+        for (int q = 0; q < kSlots; ++q) {
+          const int d4 = d4b + dg + q * kDG;
+          g[k][q] = (c < ncell && d4 < D4) ? G4[(int64_t)hh * D4 + d4] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < kCB; ++k)
+#pragma unroll
+        for (int q = 0; q < kSlots; ++q)
+          if (lv[k]) {
+            s[q].x += g[k][q].x;
+            s[q].y += g[k][q].y;
+            s[q].z += g[k][q].z;
+            s[q].w += g[k][q].w;
+          }
+    }
+#pragma unroll
+    for (int q = 0; q < kSlots; ++q) {
+      const int d4 = d4b + dg + q * kDG;
+      if (d4 < D4) {
+        fT[(4 * d4 + 0) * kFP + pp] = s[q].x;
+        fT[(4 * d4 + 1) * kFP + pp] = s[q].y;
+        fT[(4 * d4 + 2) * kFP + pp] = s[q].z;
+        fT[(4 * d4 + 3) * kFP + pp] = s[q].w;
+      }
+      s[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+}
+
 // Fast-path projection over the gate list:
 // kFP entries per workgroup; box rows of empty subdivisions are skipped (their G rows
 // may be stale: the sparse compress only writes non-empty rows; an all-zero row adds
@@ -766,62 +829,8 @@ __device__ __forceinline__ void score_list_body(const SparseSearch& b, int bx, i
         fT[(4 * d4 + 2) * kFP + pp] = v.z;
         fT[(4 * d4 + 3) * kFP + pp] = v.w;
       }
-    } else {  // box sums in the fixed (dz, dy, dx) order over non-empty rows; lane = position.
-       // Cells go in batches of 4 x (this thread's d4 slots): every load of a batch is in
-       // flight together.  Rows of empty subdivisions read as 0 (their G rows may be stale;
-       // +0 added to a sum that starts at +0 changes nothing) -- for C3 extracts, where
-       // exist 0 means empty (skip_empty); other features add every row.
-      const int pp = tid & (kFP - 1), dg = tid / kFP;
-      constexpr int kDG = kBlock / kFP;  // d4 stride
-      const bool ok = gate[pp];
-      const int h = hrow[pp], rr = rng[pp];
-      const int xr = rr & 1023, yr = (rr >> 10) & 1023, zr = rr >> 20;
-      const int ncell = ok ? xr * yr * zr : 0;
-      const float4* G4 = reinterpret_cast<const float4*>(fG);
-      constexpr int kSlots = 4;  // d4 values per thread handled together (D4 <= 64)
-      constexpr int kCB = C3H_SCORE_CB;  // box cells whose loads are in flight together
-      float4 s[kSlots];
-#pragma unroll
-      for (int q = 0; q < kSlots; ++q) s[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-      for (int d4b = 0; d4b < D4; d4b += kSlots * kDG) {
-        for (int c0 = 0; c0 < ncell; c0 += kCB) {
-          float4 g[kCB][kSlots];
-          bool lv[kCB];
-#pragma unroll
-          for (int k = 0; k < kCB; ++k) {
-            const int c = c0 + k;
-            const int dx = c % xr, dy = (c / xr) % yr, dz = c / (xr * yr);
-            const int hh = h + dz * xyn + dy * a.xn + dx;
-            lv[k] = c < ncell && (!a.skip_empty || fexist[c < ncell ? hh : h] != 0);
-#pragma unroll
-            for (int q = 0; q < kSlots; ++q) {
-              const int d4 = d4b + dg + q * kDG;
-              g[k][q] = (c < ncell && d4 < D4) ? G4[(int64_t)hh * D4 + d4] : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-          }
-#pragma unroll
-          for (int k = 0; k < kCB; ++k)
-#pragma unroll
-            for (int q = 0; q < kSlots; ++q)
-              if (lv[k]) {
-                s[q].x += g[k][q].x;
-                s[q].y += g[k][q].y;
-                s[q].z += g[k][q].z;
-                s[q].w += g[k][q].w;
-              }
-        }
-#pragma unroll
-        for (int q = 0; q < kSlots; ++q) {
-          const int d4 = d4b + dg + q * kDG;
-          if (d4 < D4) {
-            fT[(4 * d4 + 0) * kFP + pp] = s[q].x;
-            fT[(4 * d4 + 1) * kFP + pp] = s[q].y;
-            fT[(4 * d4 + 2) * kFP + pp] = s[q].z;
-            fT[(4 * d4 + 3) * kFP + pp] = s[q].w;
-          }
-          s[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-      }
+    } else {
+      score_gather_rows(a, fG, fexist, gate, hrow, rng, fT);
     }
     __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the basis window's LDS-DMA (first chunk)
     lds_barrier();
@@ -927,6 +936,233 @@ __device__ __forceinline__ void score_list_body(const SparseSearch& b, int bx, i
     lds_barrier();
     if (tid == 0) {
       const uint32_t total = (uint32_t)min(nch, gdx) * gdy;
+      s_last = atomicAdd(&fdone[a.epoch & 1], 1u) == total - 1;
+    }
+    lds_barrier();
+    if (s_last) argmax_finalize(a, fpart, flists, fout, nch);
+  }
+  C3H_SPROF(7);
+}
+
+// The tick's score role on the matrix cores (round 8).  score_list_body runs the projection
+// once per model group: every group pass stages a D x 64 basis window in LDS (an exposed
+// vmcnt(0) and two barriers), runs an LDS-read-bound VALU GEMM and repeats the epilogue.
+// Here the kFP x (M r) x D projection of a list chunk runs on v_mfma_f32_32x32x2_f32 in
+// passes of whole models (one pass at the bench's 10 x 20 columns): wave w takes the 32-column
+// tiles w and w + 4 of the pass; per k-pair the A operand is one conflict-free LDS read of
+// fT shared by the wave's tiles, the B operand comes straight from qt in global memory (83 KB,
+// L2-resident), kTickPF k-pairs ahead in registers -- no window, no group loop.  k-pairs
+// ascend from a zero accumulator: the MFMA is bit-for-bit the k-ordered fmaf chain
+// (compress_f32c_body), so every projection, score and detection is score_list_body's.
+// Everything around the projection is score_list_body's code: the speculative first chunk,
+// the chunk -> workgroup map, the box-sum gather, ffv, the per-(position, model) fold, the
+// partials and the hand-off to argmax_finalize.
+//
+// LDS: fT (D x kFP), the projections qv (32 T columns x kTickQS: column-major with an odd
+// stride, so the accumulator stores and the fold's reads are conflict-free and every offset
+// is an immediate; a runtime row stride cost 21 spilled VGPRs) and the per-chunk scratch,
+// inside score_list_lds_bytes(D, mpg): the role does not grow the tick's allocation.  With
+// every model in one pass qv lies over fT (free once the GEMM is done); otherwise beside it.
+// score_tick_mpp picks the models per pass.
+constexpr int kTickQS = kFP + 1;  // qv column stride
+constexpr int kTickPF = 8;  // k-pairs whose B fragments are in flight ahead of the MFMAs
+__host__ __device__ inline int score_tick_tiles(int models, int r) { return (models * r + 31) / 32; }
+__host__ __device__ inline size_t score_tick_lds_bytes(int D, int M, int r, int mpp) {
+  const size_t ft = (size_t)D * kFP, qv = (size_t)kTickQS * 32 * score_tick_tiles(mpp, r);
+  const size_t region = mpp >= M ? (ft > qv ? ft : qv) : ft + qv;
+  return sizeof(float) * (region + kFP) + sizeof(int) * 4 * kFP + sizeof(long long) * kFP +
+         sizeof(double) * kFP * mpp + 16 + 16;
+}
+// models per pass: the most whose pass is at most 8 tiles (two per wave) and fits the VALU
+// body's LDS (one model, r <= 64, always does)
+__host__ __device__ inline int score_tick_mpp(int D, int M, int r, int mpg) {
+  const size_t budget = score_list_lds_bytes(D, mpg);
+  int mpp = M;
+  while (mpp > 1 && (score_tick_tiles(mpp, r) > 8 || score_tick_lds_bytes(D, M, r, mpp) > budget)) --mpp;
+  return mpp;
+}
+
+// block bx of gdx workgroups of frame fz_; mpp: score_tick_mpp; smem: score_list_lds_bytes(D, mpg)
+__device__ __forceinline__ void score_tick_mfma_body(const SparseSearch& b, int bx, int fz_, int gdx, int mpp,
+                                                     float* ssm) {
+  const SparseSearch& a = b;
+  const int64_t fz = fz_;
+  const float* __restrict__ fG = b.G + fz * b.s_G;
+  const int32_t* __restrict__ fexist = b.exist + fz * b.s_exist;
+  double* __restrict__ fscores = b.scores + fz * b.s_scores;
+  const long long* __restrict__ flist = b.list + fz * b.s_list;
+  const uint32_t* fcnt = b.cnt + fz * b.s_cnt;
+  uint32_t* fdone = b.done + fz * b.s_cnt;
+  ScorePartial* fpart = b.partials ? b.partials + fz * b.s_partials : nullptr;
+  c3h_det* flists = b.lists ? b.lists + fz * b.s_lists : nullptr;
+  c3h_det* fout = b.outs[fz];
+  long long* fprof = fz ? nullptr : b.prof;
+  constexpr int by = 0;  // (C3H_SPROF)
+  const int D = a.D, Qs = a.Opad;  // qt row stride
+  C3H_SPROF(0);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hk = lane >> 5, l32 = lane & 31;
+  // issued together: the list count and this workgroup's first list chunk (speculative: the
+  // list buffer holds P_total entries, entries past the count are ignored)
+  const int64_t ptot = a.pstart[a.nmodes];
+  long long en_first = -1;
+  if (tid < kFP) en_first = flist[min((int64_t)bx * kFP + tid, ptot - 1)];
+  const int n = (int)fcnt[a.epoch & 1];
+  const int nch = (n + kFP - 1) / kFP;  // list chunks; chunk c -> workgroups c mod gdx
+  if (bx >= nch) {
+    if (n == 0 && flists && bx == 0) argmax_finalize(a, fpart, flists, fout, 0);  // clean / copy out
+    return;
+  }
+  const int nqv = kTickQS * 32 * score_tick_tiles(mpp, a.r);  // floats of qv
+  const bool one_pass = mpp >= a.M;
+  float* fT = ssm;                                  // D x kFP (k-major box features)
+  float* qv = one_pass ? ssm : ssm + D * kFP;       // a pass's projections, [column][position]
+  float* ffv = ssm + (one_pass ? max(D * kFP, nqv) : D * kFP + nqv);
+  int* gate = reinterpret_cast<int*>(ffv + kFP);
+  int* hrow = gate + kFP;
+  int* rng = hrow + kFP;                       // packed xr | yr << 10 | zr << 20
+  long long* ent = reinterpret_cast<long long*>(rng + kFP + (kFP & 1));
+  double* bsc = reinterpret_cast<double*>(ent + kFP);  // kFP * mpp
+  const int xyn = a.xn * a.yn;
+  const int KP = D >> 1;  // k-pairs (D % 4 == 0)
+  for (int ch = bx; ch < nch; ch += gdx) {
+    const int64_t e0 = (int64_t)ch * kFP;
+    if (tid < kFP) {
+      const int64_t e = e0 + tid;
+      int ok = 0, h = 0, rr = 0;
+      long long en = -1;
+      if (e < n) {
+        en = ch == bx ? en_first : flist[e];
+        const int mi = (int)(en >> 40);
+        const int64_t p = en & ((1ll << 40) - 1);
+        const ModeGeom& md = a.md[mi];
+        const int64_t xye = (int64_t)md.xe * md.ye;
+        const int x = (int)(p % md.xe), y = (int)((p / md.xe) % md.ye), z = (int)(p / xye);
+        h = z * xyn + y * a.xn + x;
+        rr = md.xr | (md.yr << 10) | (md.zr << 20);
+        ok = 1;
+      }
+      gate[tid] = ok;
+      hrow[tid] = h;
+      rng[tid] = rr;
+      ent[tid] = en;
+    }
+    lds_barrier();
+    C3H_SPROF(1);
+    score_gather_rows(a, fG, fexist, gate, hrow, rng, fT);
+    lds_barrier();
+    C3H_SPROF(2);
+    // f.f in ascending d, by the last wave (it has the fewest tiles when they do not divide)
+    if (tid >= kBlock - 64 && lane < kFP) {
+      float s = 0.0f;
+      for (int d = 0; d < D; ++d) s = __builtin_fmaf(fT[d * kFP + lane], fT[d * kFP + lane], s);
+      ffv[lane] = s;
+    }
+    for (int m0 = 0; m0 < a.M; m0 += mpp) {
+      const int m1 = min(a.M, m0 + mpp), nm = m1 - m0;
+      const int c0 = m0 * a.r, ncol = nm * a.r, ntile = (ncol + 31) >> 5;
+      // wave w: tiles w and w + 4 of the pass (at most 8), sharing every A fragment
+      const int t = wave;
+      const bool one = t < ntile, two = t + 4 < ntile;  // wave-uniform
+      mf_f32x16 acc0, acc1;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) acc0[q] = acc1[q] = 0.0f;
+      if (one) {
+        // columns past Opad - 1 are clamped, not masked: they are never folded (qt is finite).
+        // A load's address is a uniform row pair (scalar) plus the lane's offset in it: one
+        // address VGPR per tile for all the loads in flight
+        const uint32_t v0 = (uint32_t)(hk * Qs + min(c0 + 32 * t + l32, Qs - 1));
+        const uint32_t v1 = two ? (uint32_t)(hk * Qs + min(c0 + 32 * (t + 4) + l32, Qs - 1)) : v0;
+        float bc[2][kTickPF], bn[2][kTickPF];
+        auto load_b = [&](float (&v)[2][kTickPF], int j0) {
+#pragma unroll
+          for (int jj = 0; jj < kTickPF; ++jj) {
+            // pairs past D re-read the last pair and are never used
+            const float* __restrict__ rowp = a.qt + (int64_t)min(2 * (j0 + jj), D - 2) * Qs;
+            v[0][jj] = rowp[v0];
+            v[1][jj] = rowp[v1];  // (a wave with one tile reads it twice: no branch per load)
+          }
+        };
+        load_b(bc, 0);
+        for (int j0 = 0; j0 < KP; j0 += kTickPF) {
+          if (j0 + kTickPF < KP) load_b(bn, j0 + kTickPF);
+#pragma unroll
+          for (int jj = 0; jj < kTickPF; ++jj) {
+            if (j0 + jj < KP) {  // uniform
+              const float av = fT[(2 * (j0 + jj) + hk) * kFP + l32];
+              acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bc[0][jj], acc0, 0, 0, 0);
+              if (two) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bc[1][jj], acc1, 0, 0, 0);
+            }
+          }
+#pragma unroll
+          for (int jj = 0; jj < kTickPF; ++jj) {
+            bc[0][jj] = bn[0][jj];
+            bc[1][jj] = bn[1][jj];
+          }
+        }
+      }
+      lds_barrier();  // every wave is done with fT (qv lies over it in a one-pass role); ffv is written
+      C3H_SPROF(3);
+      // C/D map: column l32, row (q & 3) + 8 (q >> 2) + 4 hk
+      if (one) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) qv[(32 * t + l32) * kTickQS + 4 * hk + (q & 3) + 8 * (q >> 2)] = acc0[q];
+      }
+      if (two) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+          qv[(32 * (t + 4) + l32) * kTickQS + 4 * hk + (q & 3) + 8 * (q >> 2)] = acc1[q];
+      }
+      lds_barrier();
+      for (int e = tid; e < kFP * nm; e += kBlock) {
+        const int mm = e / kFP, pp = e - mm * kFP;
+        double sc = -2.0;
+        if (gate[pp]) {
+          float q2 = 0.0f;
+          const float* q = qv + mm * a.r * kTickQS + pp;
+#pragma unroll 4  // reads issued four at a time (a dependent LDS round trip per element otherwise)
+          for (int i = 0; i < a.r; ++i) q2 = __builtin_fmaf(q[i * kTickQS], q[i * kTickQS], q2);
+          sc = sqrt((double)q2) / sqrt((double)ffv[pp]);
+          const long long en = ent[pp];
+          const ModeGeom& md = a.md[(int)(en >> 40)];
+          fscores[md.offset + (int64_t)(m0 + mm) * md.P + (en & ((1ll << 40) - 1))] = sc;
+        }
+        bsc[e] = sc;
+      }
+      C3H_SPROF(4);
+      if (fpart) {
+        lds_barrier();
+        for (int mm = tid; mm < nm; mm += kBlock) {  // (score desc, scan order asc)
+          double best = -2.0;
+          long long bo = -1;
+          for (int pp = 0; pp < kFP; ++pp) {
+            if (!gate[pp]) continue;
+            const double sc = bsc[mm * kFP + pp];
+            const long long en = ent[pp];
+            const long long o = a.order_base[(int)(en >> 40)] + (en & ((1ll << 40) - 1));
+            if (sc > best || (sc == best && o < bo)) {
+              best = sc;
+              bo = o;
+            }
+          }
+          ScorePartial* q = fpart + (int64_t)ch * a.M + m0 + mm;
+          if (flists) {  // handed to another workgroup inside this launch: sc1 stores
+            __hip_atomic_store(&q->score, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&q->order, bo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          } else {
+            *q = ScorePartial{best, bo};
+          }
+        }
+      }
+    }
+    lds_barrier();  // LDS is reused by the next chunk
+  }
+  if (fpart && flists) {
+    // rank 1, fused replay: the last workgroup to finish reduces (score_list_body's hand-off)
+    int& s_last = *reinterpret_cast<int*>(reinterpret_cast<char*>(ssm) + score_list_lds_bytes(D, a.mpg) - 16);
+    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    lds_barrier();
+    if (tid == 0) {
+      const uint32_t total = (uint32_t)min(nch, gdx);
       s_last = atomicAdd(&fdone[a.epoch & 1], 1u) == total - 1;
     }
     lds_barrier();
