@@ -294,7 +294,10 @@ int c3h_search_async(c3h_ctx* ctx, const int32_t range[3], int32_t exist_thresho
  * d_out + i * M * rank, each frame starting from fresh lists (setRank state: scores 0,
  * S_MODE_1).  Frames go c3h_set_batch at a time through one set of launches and are
  * spread over c3h_set_lanes lanes; afterwards the context holds the last frame's state.
- * One host call, no host synchronisation. */
+ * Ranks 1 .. 64 (c3h_set_rank) run through the software pipeline (c3h_set_pipeline); above
+ * rank 1 one replay launch per batch follows the batch's scoring and updates every frame's
+ * lists (searchPart's order-dependent update with checkOverlap, exact).  Ranks above 64
+ * take the lanes with one replay launch per frame.  One host call, no host synchronisation. */
 int c3h_run_frames(c3h_ctx* ctx, const uint32_t* const* d_grids, int32_t nframes,
                    const int32_t div_b[3], const int32_t min_b[3], float leaf,
                    const c3h_extract_params* p, const int32_t range[3], int32_t exist_threshold,
@@ -311,8 +314,10 @@ int c3h_set_lanes(c3h_ctx* ctx, int32_t lanes);
  * once three more batches have been pushed, or after c3h_stream_flush.  The grids and
  * d_out must stay valid until then.  A call with a different geometry / parameter set,
  * and every other entry point that touches this context's buffers, drains the open
- * stream first.  Configurations the pipeline does not cover (rank > 1, ...) complete
- * synchronously as in c3h_run_frames.  Returns the number of searched modes. */
+ * stream first.  Ranks 1 .. 64 stream (above rank 1 a batch's lists are written by the
+ * replay launch behind its scoring tick: the same completion rule).  Configurations the
+ * pipeline does not cover (rank > 64, a search off the fast path, split subdivisions)
+ * complete synchronously as in c3h_run_frames.  Returns the number of searched modes. */
 int c3h_stream_frames(c3h_ctx* ctx, const uint32_t* const* d_grids, int32_t nframes,
                       const int32_t div_b[3], const int32_t min_b[3], float leaf,
                       const c3h_extract_params* p, const int32_t range[3], int32_t exist_threshold,
@@ -342,7 +347,7 @@ int c3h_stream_flush(c3h_ctx* ctx);
  * NULL): the frame's VoxelGrid geometry, getSubdivNum, point and voxel counts and status
  * (0 batched, 1 single-frame path, < 0 the C3H_ERR_* that frame failed with; its lists are
  * the fresh setRank state).  One host synchronisation per call (the frames' records).
- * Rank 1 on the fast search path (else every frame takes the single-frame path).
+ * Ranks 1 .. 64 on the fast search path (else every frame takes the single-frame path).
  * Returns the number of searched modes or an error. */
 typedef struct {
   int32_t div_b[3], min_b[3], subdiv_b[3];
@@ -360,7 +365,8 @@ int c3h_run_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n
 int c3h_set_batch(c3h_ctx* ctx, int32_t frames);
 /* c3h_run_frames scheduling (default 1): 1 = software pipeline on the context stream, one
  * fused launch per tick running occupancy (batch t) | tile (t-1) | compress+gate (t-2) |
- * score + rank-1 argmax (t-3); applies to rank 1 on the fast search path without split
+ * score + rank-1 argmax (t-3), at ranks 2 .. 64 followed by one replay launch for the batch
+ * scored in that tick; applies to ranks 1 .. 64 on the fast search path without split
  * subdivisions, other configurations use the lanes.  0 = lanes only. */
 int c3h_set_pipeline(c3h_ctx* ctx, int32_t enable);
 /* compressed features (setData before the summed-volume table): hist_num x D floats */

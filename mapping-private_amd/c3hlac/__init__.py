@@ -301,7 +301,8 @@ class Context:
                    rotate=True, d_out=None, offset=(0, 0, 0), color_mode=COLOR_C3_DOUBLE, stream=False):
         """c3h_run_frames (stream=True: c3h_stream_frames, the pipeline stays filled;
         call stream_flush() before reading the last batches): grid_ptrs = uint64 numpy
-        array of device pointers."""
+        array of device pointers.  Ranks 1..64 (set_rank) go through the pipelined tick,
+        above rank 1 with one rank-replay launch per batch; ranks above 64 take the lanes."""
         gp = np.ascontiguousarray(grid_ptrs, dtype=np.uint64)
         fn = self.lib.c3h_stream_frames if stream else self.lib.c3h_run_frames
         p = _capi.ExtractParams()
@@ -354,7 +355,8 @@ class Context:
         arrays (pinned or not) or all torch device tensors, or a PointFrames from
         prepare_point_frames; d_out = device pointer (int) or tensor of len(frames) * M * rank
         records.  Returns (modes, info) with info a numpy structured array (div_b, min_b,
-        subdiv_b, status, n_valid, n_occ) per frame."""
+        subdiv_b, status, n_valid, n_occ) per frame.  Frames are batched (status 0) at ranks
+        1..64; above that every frame takes the single-frame path (status 1)."""
         if not isinstance(frames, PointFrames):
             frames = self.prepare_point_frames(frames)
         ptrs, ns, on_dev = frames.ptrs, frames.ns, frames.on_device
@@ -417,7 +419,7 @@ class Context:
         return 32 if n_frames >= 256 else 64
 
     def set_pipeline(self, on):
-        """run_frames scheduling: True = pipelined tick launches, False = lanes."""
+        """run_frames scheduling: True = pipelined tick launches (ranks 1..64), False = lanes."""
         self._chk(self.lib.c3h_set_pipeline(self.h, int(bool(on))), "set_pipeline")
 
     def compressed(self):

@@ -489,6 +489,21 @@ struct ReplayModes {
 hipError_t launch_replay(const double* scores, const ReplayModes& modes, int M, int rank,
                          int r1, int r2, int r3, int clean, c3h_det* lists, c3h_det* out2,
                          hipStream_t s);
+// the replay of every frame of a batch in one launch (replay_frames_kernel): frame f reads
+// scores + f * s_scores and updates lists + f * s_lists (and outs[f], nullable)
+struct ReplayFrames {
+  const double* scores;
+  int64_t s_scores;
+  ReplayModes modes;
+  int M, nf, rank;
+  int r1, r2, r3;
+  int clean;  // 0 continue, 1 cleanMax (modes kept), 2 setRank state
+  c3h_det* lists;
+  int64_t s_lists;
+  c3h_det* outs[kMaxBatch];
+};
+bool replay_frames_ok(const ReplayModes& modes, int rank);  // ranks 1 .. 64, 32-bit positions
+hipError_t launch_replay_frames(const ReplayFrames& a, hipStream_t s);
 
 hipError_t launch_clean_lists(c3h_det* lists, int n, hipStream_t s);
 
@@ -666,6 +681,8 @@ struct c3h_ctx {
   c3h::C3Launch cap_c3{};
   c3h::SparseSearch cap_q{};
   c3h::SparseCompress cap_sc{};
+  bool cap_replay = false;      // rank > 1: the batched replay follows the batch's score role
+  c3h::ReplayFrames cap_rp{};
 
   // the software pipeline of c3h_run_frames / c3h_stream_frames: batches whose later
   // stages are still to run, each tagged with the tick role it runs next (1 tile,
@@ -682,6 +699,8 @@ struct c3h_ctx {
     std::vector<int64_t> layout;  // its score-array layout, recorded there once its gate is enqueued
     bool fix = false;             // points-in batch: the off-cell fixup runs after its tile role
     c3h::PointFixup fx{};
+    bool replay = false;          // rank > 1: the batched replay runs after its score role
+    c3h::ReplayFrames rp{};
   };
   struct PipeKey {
     int32_t div_b[3], min_b[3];

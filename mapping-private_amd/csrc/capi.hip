@@ -576,12 +576,32 @@ int search_frames(c3h_ctx* ctx, int nf, const int32_t range[3], int32_t thr, int
       ctx->g_valid = true;
       ctx->g_sparse = true;
     }
+    // rank > 1: every frame's lists in one launch over the written scores
+    c3h::ReplayFrames rp{};
+    const bool replay_batched = !use_argmax && c3h::replay_frames_ok(rm, ctx->rank);
+    if (replay_batched) {
+      rp.scores = ctx->scores.p;
+      rp.s_scores = q.s_scores;
+      rp.modes = rm;
+      rp.M = ctx->M;
+      rp.nf = nf;
+      rp.rank = ctx->rank;
+      rp.r1 = range[0];
+      rp.r2 = range[1];
+      rp.r3 = range[2];
+      rp.clean = clean;
+      rp.lists = ctx->d_lists.p;
+      rp.s_lists = (int64_t)per_lists;
+      for (int f = 0; f < c3h::kMaxBatch; ++f) rp.outs[f] = q.outs[f];
+    }
     if (ctx->capture) {  // pipelined c3h_run_frames: the tick kernel runs these stages
       ctx->cap_layout.swap(layout);  // recorded by pipe_tick when the gate role is enqueued
       ctx->cap_q = q;
       ctx->cap_sc = sc;
       ctx->cap_sparse_g = sparse_g;
       ctx->cap_argmax = use_argmax;
+      ctx->cap_replay = replay_batched;  // the replay's arguments, launched behind the score role
+      ctx->cap_rp = rp;
       ctx->cap_search_valid = true;
       ctx->pending_clean = false;
       ctx->lists_host_valid = false;
@@ -604,7 +624,9 @@ int search_frames(c3h_ctx* ctx, int nf, const int32_t range[3], int32_t thr, int
     }
     if (!use_argmax) {
       Timed t(ctx, 4, nf);
-      for (int f = 0; f < nf; ++f) {
+      const bool one_launch = nf > 1 && replay_batched;  // a batch at ranks up to 64
+      if (one_launch) HIPCHK(c3h::launch_replay_frames(rp, ctx->stream));
+      for (int f = 0; !one_launch && f < nf; ++f) {
         c3h::ReplayModes rmf = rm;
         for (int i = 0; i < rmf.n; ++i) rmf.m[i].offset += f * q.s_scores;
         HIPCHK(c3h::launch_replay(ctx->scores.p, rmf, ctx->M, ctx->rank, range[0], range[1], range[2], clean,
@@ -2274,6 +2296,11 @@ int pipe_tick(c3h_ctx* ctx, const c3h_ctx::PipeBatch* fresh) {
     if (e != hipSuccess) return hip_fail(ctx, "launch_tick", e);
   }
   for (auto& b : ctx->pipe) {
+    if (b.age == 3 && b.replay) {  // its score role ran in this tick: the lists of its frames
+      Timed tm(ctx, 4, b.nf);
+      hipError_t e = c3h::launch_replay_frames(b.rp, ctx->stream);
+      if (e != hipSuccess) return hip_fail(ctx, "launch_replay_frames", e);
+    }
     if (b.age == 2 && b.set) b.set->scores_layout = b.layout;  // this tick enqueued its gate
     if (b.age == 1 && b.fix) {  // its tile role ran in this tick: the off-cell fixup before its compress
       hipError_t e = c3h::launch_point_fixup(b.fx, ctx->stream);
@@ -2332,7 +2359,10 @@ int pipe_prepare(c3h_ctx* ctx, const uint32_t* const* grids, c3h_det* const* out
     if (c != ctx) ctx->err = c->err;
     return rc;
   }
-  const bool fits = c->cap_c3_valid && c->cap_search_valid && c->cap_sparse_g && c->cap_argmax &&
+  // rank 1: the score role's fused argmax; ranks 2 .. 64: the score role writes the scores
+  // only and the batched replay follows it
+  const bool ranked = c->cap_argmax || (c->cap_replay && c->rank >= 2 && !c->cap_q.lists && !c->cap_q.partials);
+  const bool fits = c->cap_c3_valid && c->cap_search_valid && c->cap_sparse_g && ranked &&
                     c3h::tick_ok(c->cap_c3);
   if (!fits) {  // one geometry per stream: decided on its first batch
     if (!ctx->pipe.empty()) return fail(ctx, C3H_ERR_STATE, "pipeline: internal: geometry changed");
@@ -2342,6 +2372,8 @@ int pipe_prepare(c3h_ctx* ctx, const uint32_t* const* grids, c3h_det* const* out
   *fresh = c3h_ctx::PipeBatch{c->cap_c3, c->cap_q, c->cap_sc, nb, 0};
   fresh->set = c;
   fresh->layout = c->cap_layout;
+  fresh->replay = !c->cap_argmax;
+  fresh->rp = c->cap_rp;
   return rc;
 }
 
@@ -2394,7 +2426,7 @@ c3h_ctx::PipeKey pipe_key(c3h_ctx* ctx, const int32_t div_b[3], const int32_t mi
 }
 
 bool pipelinable(const c3h_ctx* ctx) {
-  return ctx->pipeline && ctx->rank == 1 && c3h::score_fast_ok(ctx->D, ctx->r);
+  return ctx->pipeline && ctx->rank >= 1 && ctx->rank <= 64 && c3h::score_fast_ok(ctx->D, ctx->r);
 }
 
 // Runs nframes through the pipeline in batches of B.  drain: run the fill/drain ticks so

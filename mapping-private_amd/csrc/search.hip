@@ -14,8 +14,10 @@
 // replay: the order-dependent rank update with checkOverlap (search.cpp:327-376,
 //   464-474) replayed exactly, one wave per model, scanning positions in the
 //   reference's (mode, z, y, x) order; only candidates above the current rank-th score
-//   (the lists only grow) are visited serially.
+//   (the lists only grow) are visited serially.  replay_frames_kernel does the same for
+//   every frame of a batch in one launch, at ranks up to 64 (the list on the lanes of a wave).
 #include "c3h_internal.h"
+#include "rank_list.h"
 #include "search_dev.h"
 
 namespace c3h {
@@ -829,47 +831,7 @@ __global__ __launch_bounds__(kBlock) void score_list_kernel(SparseSearch b) {
 }
 
 // ---------------------------------------------------------------- rank replay
-__device__ __forceinline__ void get_range(int mode, int r1, int r2, int r3, int& xr, int& yr,
-                                          int& zr) {
-  switch (mode) {  // search.cpp:218-251
-    case 0: xr = r1; yr = r2; zr = r3; break;
-    case 1: xr = r1; yr = r3; zr = r2; break;
-    case 2: xr = r2; yr = r1; zr = r3; break;
-    case 3: xr = r2; yr = r3; zr = r1; break;
-    case 4: xr = r3; yr = r1; zr = r2; break;
-    default: xr = r3; yr = r2; zr = r1; break;
-  }
-}
-
-// rank update of searchPart (search.cpp:464-474) incl. checkOverlap (:327-356)
-__device__ void rank_update(c3h_det* L, int rank, double cs, int x, int y, int z, int mode,
-                            int xr, int yr, int zr, int r1, int r2, int r3) {
-  for (int i = 0; i < rank; i++) {
-    if (cs > L[i].score) {
-      int num;
-      for (num = 0; num < rank - 1; num++) {
-        int oxr, oyr, ozr;
-        get_range(L[num].mode, r1, r2, r3, oxr, oyr, ozr);
-        int v1 = L[num].x - x;
-        v1 = v1 < 0 ? -v1 - oxr : v1 - xr;
-        int v2 = L[num].y - y;
-        v2 = v2 < 0 ? -v2 - oyr : v2 - yr;
-        int v3 = L[num].z - z;
-        v3 = v3 < 0 ? -v3 - ozr : v3 - zr;
-        if (v1 <= 0 && v2 <= 0 && v3 <= 0) break;
-      }
-      for (int q = 0; q < num - i; q++) L[num - q] = L[num - 1 - q];
-      if (i <= num) {
-        L[i].score = cs;
-        L[i].x = x;
-        L[i].y = y;
-        L[i].z = z;
-        L[i].mode = mode;
-      }
-      break;
-    }
-  }
-}
+// get_range, rank_update and the per-slot form of the update: rank_list.h
 
 // general rank: one wave per model scans the scores in (mode, z, y, x) order, eight
 // 64-position chunks per load batch; only candidates above the current rank-th score
@@ -929,6 +891,150 @@ __global__ __launch_bounds__(64) void replay_kernel(const double* __restrict__ s
   for (int i = lane; i < rank; i += 64) {
     gl[i] = L[i];
     if (out2) out2[(int64_t)m * rank + i] = L[i];
+  }
+}
+
+// Ranks 1 .. 64 of a whole batch in one launch: workgroup (m, f) replays model m of frame f.
+// The (mode, z, y, x) scan goes in chunks of kRfChunk positions, each thread's eight
+// coalesced loads of the next chunk in flight while this one is worked on (unconditional
+// loads, rf_load: the filter waits with vmcnt(15 .. 8), the prefetch is waited for after the
+// iteration's last barrier; profiles/r9/rank_batch/replay_frames_waits.txt):
+//   filter  all four waves keep the positions whose score exceeds T, the rank-th score as of
+//           the chunk's start (it never decreases, so a stale T only lets more through), and
+//           compact them in ascending position order into an LDS queue: a ballot per 64
+//           positions, a scan over the 32 segment counts, barriers only;
+//   update  wave 0 walks the queue with list slot j on lane j (rank_list.h's per-slot form):
+//           64 queue entries are read and decoded at once, then one by one broadcast, checked
+//           against the current T (lane rank - 1) and applied with two ballots and a shift by
+//           one lane -- no barrier and no LDS list inside the walk.
+constexpr int kRfChunk = 2048, kRfLoads = kRfChunk / kBlock, kRfSegs = kRfChunk / 64;
+
+__device__ __forceinline__ double rf_bcast(double v, int src) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src),
+                          __builtin_amdgcn_readlane(__double2loint(v), src));
+}
+
+// a thread's loads of one chunk.  Unconditional: a position past the row's end reads the row's
+// last score (the filter tests p < P itself), so no load sits in a branch and the compiler
+// waits for this chunk with a counted vmcnt while the next chunk's loads stay in flight
+__device__ __forceinline__ void rf_load(const double* __restrict__ sc, int P, int b0, int tid,
+                                        double (&s)[kRfLoads]) {
+#pragma unroll
+  for (int j = 0; j < kRfLoads; ++j) s[j] = sc[min(b0 + j * kBlock + tid, P - 1)];
+}
+
+__global__ __launch_bounds__(kBlock) void replay_frames_kernel(ReplayFrames a) {
+  __shared__ double q_score[kRfChunk];
+  __shared__ int q_pos[kRfChunk];
+  __shared__ int seg_cnt[kRfSegs];
+  __shared__ double s_T;
+  const int m = blockIdx.x, f = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int rank = a.rank, r1 = a.r1, r2 = a.r2, r3 = a.r3;
+  const double* __restrict__ fscores = a.scores + f * a.s_scores;
+  c3h_det* gl = a.lists + f * a.s_lists + (int64_t)m * rank;
+  c3h_det e{};  // wave 0: list slot `lane`
+  if (w == 0) {
+    if (lane < rank && a.clean != 2) e = gl[lane];
+    if (a.clean) {  // 1: cleanMax (modes kept); 2: setRank state
+      e.score = 0.0;
+      e.x = e.y = e.z = 0;
+      if (a.clean == 2) e.mode = 0;
+    }
+    if (lane == rank - 1) s_T = e.score;
+  }
+  int mi = 0, b0 = 0;  // the chunk being worked on
+  double cur[kRfLoads];
+  if (a.modes.n > 0) rf_load(fscores + a.modes.m[0].offset + (int64_t)m * a.modes.m[0].P, (int)a.modes.m[0].P, 0, tid, cur);
+  lds_barrier();
+  while (mi < a.modes.n) {
+    const int P = (int)a.modes.m[mi].P, xe = a.modes.m[mi].xe, mode = a.modes.m[mi].mode;
+    const int xye = xe * a.modes.m[mi].ye;
+    int mi2 = mi, b2 = b0 + kRfChunk;
+    if (b2 >= P) {
+      ++mi2;
+      b2 = 0;
+    }
+    // the next chunk's loads go out before this chunk is touched.  After the last chunk there
+    // is none: this one is loaded again (unused), since a path without loads would make the
+    // compiler wait for this chunk with the count of that path, i.e. for the prefetch as well
+    double nxt[kRfLoads];
+    {
+      const bool more = mi2 < a.modes.n;
+      const int ml = more ? mi2 : mi, bl = more ? b2 : b0;
+      rf_load(fscores + a.modes.m[ml].offset + (int64_t)m * a.modes.m[ml].P, (int)a.modes.m[ml].P, bl, tid, nxt);
+    }
+    // filter: position order within the chunk is (load j, wave, lane) = segment 4 j + w
+    const double T = s_T;
+    unsigned long long keep[kRfLoads];
+#pragma unroll
+    for (int j = 0; j < kRfLoads; ++j) {
+      keep[j] = __ballot(b0 + j * kBlock + tid < P && cur[j] > T);
+      if (lane == 0) seg_cnt[4 * j + w] = __popcll(keep[j]);
+    }
+    lds_barrier();
+    int incl = seg_cnt[lane & (kRfSegs - 1)];  // lanes 0 .. 31: inclusive scan of the segment counts
+    const int own = incl;
+#pragma unroll
+    for (int d = 1; d < kRfSegs; d <<= 1) {
+      const int up = __shfl_up(incl, d, 64);
+      if ((lane & (kRfSegs - 1)) >= d) incl += up;
+    }
+    const int total = __builtin_amdgcn_readlane(incl, kRfSegs - 1);
+    const int excl = incl - own;
+#pragma unroll
+    for (int j = 0; j < kRfLoads; ++j) {
+      const int base = __shfl(excl, 4 * j + w, 64);
+      if (keep[j] >> lane & 1) {
+        const int k = base + __popcll(keep[j] & ((1ull << lane) - 1));
+        q_score[k] = cur[j];
+        q_pos[k] = b0 + j * kBlock + tid;
+      }
+    }
+    lds_barrier();
+    if (w == 0) {
+      int xr, yr, zr;
+      get_range(mode, r1, r2, r3, xr, yr, zr);
+      for (int k0 = 0; k0 < total; k0 += 64) {
+        const int n = min(64, total - k0);
+        double cs_l = -1.0;
+        int x_l = 0, y_l = 0, z_l = 0;
+        if (lane < n) {
+          cs_l = q_score[k0 + lane];
+          const int p = q_pos[k0 + lane];
+          z_l = p / xye;
+          const int rem = p - z_l * xye;
+          y_l = rem / xe;
+          x_l = rem - y_l * xe;
+        }
+        for (int t = 0; t < n; ++t) {
+          const double cs = rf_bcast(cs_l, t);
+          if (!(cs > rf_bcast(e.score, rank - 1))) continue;  // the list grew since the filter
+          const int x = __builtin_amdgcn_readlane(x_l, t), y = __builtin_amdgcn_readlane(y_l, t),
+                    z = __builtin_amdgcn_readlane(z_l, t);
+          const int i = rank_first_greater(__ballot(cs > e.score), rank);
+          const int num = rank_stop_slot(__ballot(rank_overlaps(e, x, y, z, xr, yr, zr, r1, r2, r3)), rank);
+          if (i < 0 || i > num) continue;
+          c3h_det below;
+          below.score = __shfl_up(e.score, 1, 64);
+          below.x = __shfl_up(e.x, 1, 64);
+          below.y = __shfl_up(e.y, 1, 64);
+          below.z = __shfl_up(e.z, 1, 64);
+          below.mode = __shfl_up(e.mode, 1, 64);
+          e = rank_slot_update(lane, e, below, i, num, cs, x, y, z, mode);
+        }
+      }
+      if (lane == rank - 1) s_T = e.score;
+    }
+    lds_barrier();  // s_T for the next filter; the queue and the counts are free again
+#pragma unroll
+    for (int j = 0; j < kRfLoads; ++j) cur[j] = nxt[j];
+    mi = mi2;
+    b0 = b2;
+  }
+  if (w == 0 && lane < rank) {
+    gl[lane] = e;
+    c3h_det* out = a.outs[f];
+    if (out) out[(int64_t)m * rank + lane] = e;
   }
 }
 
@@ -1110,5 +1216,19 @@ hipError_t launch_replay(const double* scores, const ReplayModes& modes, int M, 
   return hipGetLastError();
 }
 
+// list slots live on the lanes of one wave, positions and their products are 32-bit
+bool replay_frames_ok(const ReplayModes& modes, int rank) {
+  if (rank < 1 || rank > 64) return false;
+  for (int i = 0; i < modes.n; ++i)
+    if (modes.m[i].P > INT32_MAX - 2 * kRfChunk) return false;
+  return true;
+}
+
+hipError_t launch_replay_frames(const ReplayFrames& a, hipStream_t s) {
+  if (!replay_frames_ok(a.modes, a.rank) || a.nf > kMaxBatch) return hipErrorInvalidValue;
+  if (a.M < 1 || a.nf < 1) return hipSuccess;
+  replay_frames_kernel<<<dim3((unsigned)a.M, (unsigned)a.nf), kBlock, 0, s>>>(a);
+  return hipGetLastError();
+}
 
 }  // namespace c3h
