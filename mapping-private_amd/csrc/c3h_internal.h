@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/c3hlac_mi355x.h"
+#include "occ_sched.h"
 
 namespace c3h {
 
@@ -328,6 +329,10 @@ struct C3Launch {
   const uint32_t* vl_words = nullptr;
   const int32_t* vl_counts = nullptr;
   int vl_nseg = 0, vl_seg = 0, vl_count_stride = 0;
+  // segment-occupancy map of the buffer set (occ_sched.h), frame f at segmap + f * s_segmap
+  // entries; only the pipelined tick reads or writes it (launch_tick), nullptr elsewhere
+  occ_seg_t* segmap = nullptr;
+  int64_t s_segmap = 0;
 };
 
 int64_t c3hlac_grid(const C3Launch& a);  // persistent grid of the tile kernel
@@ -511,6 +516,7 @@ hipError_t launch_clean_lists(c3h_det* lists, int n, hipStream_t s);
 struct TickParts {
   const C3Launch* occ = nullptr;        // batch t: occupancy stream
   const C3Launch* tile = nullptr;       // batch t-1: C3 tile pass
+  bool tile_mapped = false;             //   its occupancy role ran in the previous tick (segment map written)
   const SparseSearch* gate = nullptr;   // batch t-2: exist gate ...
   const SparseCompress* comp = nullptr; //   ... + sparse compress
   const SparseSearch* score = nullptr;  // batch t-3: list scoring + rank-1 argmax
@@ -604,6 +610,7 @@ struct c3h_ctx {
   std::vector<int16_t> h_axmap;
   c3h::DevBuf<uint32_t> tileflags;  // [2] reserved | [2] work counters | [ntiles] stamps
   c3h::DevBuf<int32_t> work;        // non-empty tiles of the last extract
+  c3h::DevBuf<c3h::occ_seg_t> segmap;     // pipelined batches: the segment-occupancy map of this set's grids
   uint32_t tile_epoch = 0;
   int cap_h2d = 0;  // tables / stamp resets extract_frames enqueued (counts; points-in ordering)
   int64_t tf_stride = -1;           // tile-stamp layout the counters were zeroed for
@@ -695,6 +702,7 @@ struct c3h_ctx {
     int nf;
     int age;
     bool stamped = false;  // tile stamps already set (points-in scatter): no occupancy role
+    bool mapped = false;   // its first tick ran its occupancy role (which fills the segment map)
     c3h_ctx* set = nullptr;       // the buffer set (context) the batch was captured on
     std::vector<int64_t> layout;  // its score-array layout, recorded there once its gate is enqueued
     bool fix = false;             // points-in batch: the off-cell fixup runs after its tile role

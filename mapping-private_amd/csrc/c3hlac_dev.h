@@ -138,6 +138,10 @@ struct OccArgs {
   // stand-alone large grids: dense_probe_kernel's verdict (non-zero: every tile was listed
   // and stamped, the stream is skipped); nullptr elsewhere (the tick)
   const uint32_t* dense = nullptr;
+  // segment-occupancy map (occ_sched.h), frame f at segmap + f * s_segmap entries: written by
+  // the tick's row-wave stream for the next tick's tile role; nullptr everywhere else
+  occ_seg_t* segmap = nullptr;
+  int64_t s_segmap = 0;
 };
 
 // Bitmap variant (every tile one bit of LDS, ntiles <= kOccBitsMax): an occupied centre
@@ -335,6 +339,8 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
         occ_sched(n4, kRow, gdx, oa.contiguous, oa.steal_from, oa.steal_unit, oa.steal_units, oa.nframes);
     const int64_t nch = sc.nch, nstat = sc.nstat;
     uint4 w[kRow];
+    static_assert(kRow <= 64, "one lane per row of a chunk holds the row's map entry");
+    occ_seg_t* smap = oa.segmap ? oa.segmap + f * oa.s_segmap : nullptr;  // this frame's map (uniform)
     auto chunk_of = [&](int64_t i) { return occ_chunk_of(sc, bx, i); };
     // Whole chunks (all but a frame's last, if that is partial) take unclamped, unpredicated
     // loads: the chunk's base and the step per load are wave-uniform (scalar registers), the
@@ -381,8 +387,24 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
     };
     // rows are mostly empty: skip a row unless some lane of the wave holds a voxel of it
     // (one ballot), look its (y, z) segment up only then
-    auto proc = [&](uint32_t row0) {
+    // The map: row j's ballot (one bit per 16-byte quad) goes to lane j as it is (blo, bhi;
+    // empty rows leave 0); after the chunk's rows, lanes 0 .. kRow-1 fold theirs to 16 bits and
+    // store the wave's kRow entries (one 128-byte line per wave and chunk at depth 16).
+    // Measured and not kept: the fold and store moved behind the next chunk's loads.  The
+    // first row waits with vmcnt(0), which then covers the store as the youngest access: the
+    // whole tick gained 0.9 % that way against 2.8 % with the store ahead of the loads
+    // (profiles/r10/seg_map/).
+    auto proc = [&](uint32_t row0, int64_t c) {
       int y = (int)(row0 % (uint32_t)gy), z = (int)(row0 / (uint32_t)gy);
+      uint32_t blo = 0, bhi = 0;
+      // the lane index, opaque per chunk: left visible, the kRow masks lane == j are hoisted out
+      // of the chunk loop into 2 x kRow scalar registers, which spill
+      uint32_t lv = (uint32_t)tid & 63u;
+      asm volatile("" : "+v"(lv));
+      auto put_map = [&] {
+        if (smap && lv < (uint32_t)kRow)
+          smap[c * (kChunkR >> 6) + lv * (kBlock / 64) + wv] = occ_seg_make(((uint64_t)bhi << 32) | blo);
+      };
 #pragma unroll
       for (int j = 0; j < kRow; ++j) {
         const int yj = y, zjj = z;
@@ -392,7 +414,11 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
           ++z;
         }
         const uint32_t ws[4] = {w[j].x, w[j].y, w[j].z, w[j].w};
-        if (__ballot((ws[0] | ws[1] | ws[2] | ws[3]) != 0u) == 0ull || zjj >= gz) continue;
+        const unsigned long long bal = __ballot((ws[0] | ws[1] | ws[2] | ws[3]) != 0u);
+        if (bal == 0ull || zjj >= gz) continue;  // (rows past the grid end were loaded as zeros)
+        // before the non-centre rows leave; unconditional (a test of smap costs as much)
+        blo = lv == (uint32_t)j ? (uint32_t)bal : blo;
+        bhi = lv == (uint32_t)j ? (uint32_t)(bal >> 32) : bhi;
         int a, b;
         if (oa.ar_s) {  // uniform: scalar arithmetic, no LDS round trip
           a = yj >= oa.ar_oy ? (int)__umulhi((uint32_t)(yj - oa.ar_oy), oa.ar_magic) : -1;
@@ -419,6 +445,7 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
           }
         }
       }
+      put_map();
     };
 #if C3H_OCC_RING
     // Rolling ring over whole chunks: slot j of the next chunk is loaded the moment slot j
@@ -530,7 +557,7 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
         continue;
       }
 #endif
-      proc(row0);
+      proc(row0, cidx);
       if constexpr (kOccPipe) {
 #pragma unroll
         for (int j = 0; j < kRow; ++j) w[j] = nx[j];
@@ -559,10 +586,11 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
         for (int i = tid; i < nwords; i += kBlock) s_bits[i] = 0u;
         last = -1;  // another frame's bitmap
         g4 = reinterpret_cast<const uint4*>(oa.grid[fu]);
+        if (smap) smap = oa.segmap + fu * oa.s_segmap;  // a stolen unit fills its own frame's map
         __syncthreads();
         for (int64_t c = un.cb; c < un.ce; ++c) {
           load_any(c);
-          proc((uint32_t)(((uint64_t)c * kChunkR * 4 + (uint64_t)wv * 256) >> lg));
+          proc((uint32_t)(((uint64_t)c * kChunkR * 4 + (uint64_t)wv * 256) >> lg), c);
         }
         __syncthreads();
         occ_flush_bits(s_bits, nwords, s_list, s_wsum, epoch, oa.tf + fu * oa.s_tf + 4,
@@ -679,6 +707,12 @@ struct KArgs {
   int f16s;
   int debug;  // diagnostics only (C3H_C3_DEBUG): 1 stop after the loads, 2 after compaction,
              // 3 skip the tile kernel
+  // segment-occupancy map of these grids (occ_sched.h), frame f at segmap + f * s_segmap:
+  // non-null only in the tick, for a batch whose grids went through the tick's row-wave
+  // stream on this buffer set one tick before; the per-wave 117 body then skips the halo
+  // words of empty 64-byte segments.  nullptr: every halo word is loaded
+  const occ_seg_t* segmap = nullptr;
+  int64_t s_segmap = 0;
 };
 
 constexpr int kMaxLoads = 4;  // uint4 tile loads per thread kept in flight together
@@ -1140,21 +1174,84 @@ __device__ __forceinline__ W117Geom w117_geom(const KArgs& a, const int32_t* seg
   return g;
 }
 
+// The segment map of a tile's halo.  The halo is TY * (lz + 1) row pieces of lx + 2 <= 16
+// words; a piece lies in one grid row, whose spans are whole (gx a multiple of 256).  Lane l
+// fetches the map words of pieces l, l + 64, l + 128 (kW117MapRegs pieces per lane) and,
+// a tile later, puts one table word per piece into a wave-private LDS table
+// (w117_put_map): bit (xx >> 4) - w117_map_sb(xs) of it is the segment of the piece's word
+// xx, xs the piece's first in-grid x.  The lanes that load the words read it back.
+//   raw entries (C3H_SEG_RAW): a grid row's entries are 8 * gx / 256 consecutive bytes, two
+//     segments (nibbles) per byte; the piece's at most two segments lie in the two bytes
+//     from byte xs >> 5 (clamped to the row), fetched as one 2-byte load at any byte
+//     address -- one register per piece, as many as the folded format: a dword pair per
+//     piece spilled 3 VGPRs -- and folded to 4 segment bits here, off the stream's row loop;
+//   folded entries: the span of xs | the span of the piece's last word << 16.
+constexpr int kW117MapRegs = 3;
+// 1: a halo load instruction whose 64 lanes are all gated out is skipped (one uniform test
+// per load).  Off: no vmcnt wait appears among the loads, but five branches per load do, and
+// the tick is no faster (0.8114 against 0.8126 ms, inside the spread: DESIGN §8 round 10)
+#ifndef C3H_W117_SKIP
+#define C3H_W117_SKIP 0
+#endif
+constexpr int kW117MapWords = kW117MapRegs;  // registers in flight per lane
+__host__ __device__ inline bool w117_map_fits(int lx, int ly, int lz) {
+  return (ly + 2) * (lz + 1) <= 64 * kW117MapRegs && lx + 2 <= 16;
+}
+__device__ __forceinline__ int w117_map_off(int xs, int gx) { return min(xs >> 5, (gx >> 5) - 2); }  // raw: first byte in the row
+__device__ __forceinline__ int w117_map_sb(int xs, int gx) { return C3H_SEG_RAW ? 2 * w117_map_off(xs, gx) : (xs >> 8) << 4; }
+__device__ __forceinline__ void w117_load_map(const KArgs& a, const occ_seg_t* __restrict__ fmap, const W117Geom& g,
+                                              int lane, uint32_t (&me)[kW117MapWords]) {
+  const int TY = g.ly + 2, np = TY * (g.lz + 1);
+  const int rs = a.gx >> 8;  // spans per grid row
+  const int xs = max(g.x0 - 1, 0), xe = min(g.x0 + g.lx, a.gx - 1);
+#pragma unroll
+  for (int i = 0; i < kW117MapRegs; ++i) {
+    const int q = lane + 64 * i;
+    const int yy = g.y0 - 1 + q % TY, zz = g.z0 - 1 + q / TY;
+    const bool in = q < np && (unsigned)yy < (unsigned)a.gy && (unsigned)zz < (unsigned)a.gz;
+    const int64_t row = in ? ((int64_t)zz * a.gy + yy) * rs : 0;  // clamped: the entry is unused then
+#if C3H_SEG_RAW
+    uint16_t two;
+    __builtin_memcpy(&two, reinterpret_cast<const uint8_t*>(fmap) + 8 * row + w117_map_off(xs, a.gx), 2);
+    me[i] = two;
+    (void)xe;
+#else
+    uint32_t e = fmap[row + (xs >> 8)];
+    if (rs > 1) e |= (uint32_t)fmap[row + (xe >> 8)] << 16;  // uniform: a row of several spans
+    me[i] = e;
+#endif
+  }
+}
+// the table words of this tile's pieces (read back by w117_load_halo)
+__device__ __forceinline__ void w117_put_map(uint32_t* s_map, int lane, const uint32_t (&me)[kW117MapWords]) {
+#pragma unroll
+  for (int i = 0; i < kW117MapRegs; ++i)
+    s_map[lane + 64 * i] = C3H_SEG_RAW ? occ_seg_fold32(me[i]) & 15u : me[i];  // raw: 4 nibbles -> 4 segment bits
+  __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
 // issue the halo loads of tile g into registers (element e = lane + 64 j, row-major
-// (z, y, x) over (lz+1) x (ly+2) x (lx+2) from (z0-1, y0-1, x0-1); off-grid words 0)
+// (z, y, x) over (lz+1) x (ly+2) x (lx+2) from (z0-1, y0-1, x0-1); off-grid words 0).
+// s_map (nullable, uniform): the tile's segment-map table; a word of an empty segment is
+// not fetched, it is the 0 it would have loaded
 __device__ __forceinline__ void w117_load_halo(const KArgs& a, const uint32_t* __restrict__ fgrid, const W117Geom& g,
-                                               bool valid, int lane, uint32_t (&hv)[kW117HaloRegs]) {
+                                               bool valid, int lane, uint32_t (&hv)[kW117HaloRegs],
+                                               const uint32_t* s_map = nullptr) {
   const int TX = g.lx + 2, TY = g.ly + 2, n = valid ? TX * TY * (g.lz + 1) : 0;
   int q = lane / TX, r = lane - (lane / TX) * TX;  // e -> (row q, col r), stepped by 64
   const int sq = 64 / TX, sr = 64 - sq * TX;
+  const int sb = w117_map_sb(max(g.x0 - 1, 0), a.gx);  // segment of the table word's bit 0
 #pragma unroll
   for (int j = 0; j < kW117HaloRegs; ++j) {
     const int e = lane + 64 * j;
     const int yy = g.y0 - 1 + q % TY, zz = g.z0 - 1 + q / TY, xx = g.x0 - 1 + r;
-    const bool in = e < n && (unsigned)xx < (unsigned)a.gx && (unsigned)yy < (unsigned)a.gy &&
-                    (unsigned)zz < (unsigned)a.gz;
+    bool in = e < n && (unsigned)xx < (unsigned)a.gx && (unsigned)yy < (unsigned)a.gy &&
+              (unsigned)zz < (unsigned)a.gz;
+    if (s_map) in = in && ((s_map[e < n ? q : 0] >> (((xx >> 4) - sb) & 31)) & 1u);  // uniform test, no branch per load
     // clamped address + select: a "load or zero" per element would be a branch per load
-    const uint32_t v = fgrid[in ? ((int64_t)zz * a.gy + yy) * a.gx + xx : 0];
+    uint32_t v = 0u;
+    if (!(C3H_W117_SKIP && s_map) || __ballot(in) != 0ull)  // (uniform: see C3H_W117_SKIP)
+      v = fgrid[in ? ((int64_t)zz * a.gy + yy) * a.gx + xx : 0];
     hv[j] = in ? v : 0u;
     q += sq;
     r += sr;
@@ -1227,7 +1324,21 @@ __device__ __forceinline__ void c3hlac_wave117_body(const KArgs& a, int bx, int 
   if (has1) w117_bin_channels(lane + 64, X1, Y1);
   uint32_t hv[kW117HaloRegs];
   W117Geom g = w117_geom(a, segs, t_cur);
-  w117_load_halo(a, fgrid, g, true, lane, hv);
+  // With the segment map (uniform) the look-ahead is one tile longer, so that the map fetch
+  // never sits in series with the halo loads it gates: work-list indices three tiles ahead,
+  // map entries two (me, in flight over a whole tile), halo one.  The table the entries pass
+  // through aliases the channel table, which is dead between two tiles' step 4.
+  const occ_seg_t* __restrict__ fmap = a.segmap ? a.segmap + fy * a.s_segmap : nullptr;
+  uint32_t* s_map = fmap ? s_ch : nullptr;
+  uint32_t me[kW117MapWords] = {};
+  int t_nx2 = 0;
+  if (fmap) {
+    t_nx2 = wi + 2 * NW < a.ntiles ? fwork[wi + 2 * NW] : 0;
+    w117_load_map(a, fmap, g, lane, me);  // the first tile's own: in series, once per wave
+    w117_put_map(s_map, lane, me);
+  }
+  w117_load_halo(a, fgrid, g, true, lane, hv, s_map);
+  if (fmap && wi + NW < nwork) w117_load_map(a, fmap, w117_geom(a, segs, t_nxt), lane, me);
   const int thr_r = a.thr_r, thr_g = a.thr_g, thr_b = a.thr_b;
   for (; wi < nwork; wi += NW) {
     // 1. stage the halo held in registers and, from the same registers, compact the
@@ -1264,12 +1375,20 @@ __device__ __forceinline__ void c3hlac_wave117_body(const KArgs& a, int bx, int 
     // 2. prefetch: the tile after next's index, the next tile's halo (in flight during 4-5)
     const W117Geom gc = g;
     const bool more = wi + NW < nwork;
-    const int t_after = wi + 2 * NW < a.ntiles ? fwork[wi + 2 * NW] : 0;
+    const int ahead = fmap ? 3 : 2;
+    const int t_after = wi + ahead * NW < a.ntiles ? fwork[wi + ahead * NW] : 0;
     if (more) {
       g = w117_geom(a, segs, t_nxt);
-      w117_load_halo(a, fgrid, g, true, lane, hv);
+      if (fmap) w117_put_map(s_map, lane, me);  // fetched during the previous tile
+      w117_load_halo(a, fgrid, g, true, lane, hv, s_map);
+      if (fmap && wi + 2 * NW < nwork) w117_load_map(a, fmap, w117_geom(a, segs, t_nx2), lane, me);
     }
-    t_nxt = t_after;
+    if (fmap) {
+      t_nxt = t_nx2;
+      t_nx2 = t_after;
+    } else {
+      t_nxt = t_after;
+    }
     wave_lds_fence();
     C3H_PROF(2, first);
     C3H_PROF(3, first);

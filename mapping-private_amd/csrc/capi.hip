@@ -14,6 +14,7 @@
 #include <thread>
 
 #include "c3h_internal.h"
+#include "occ_sched.h"
 
 using c3h::DevBuf;
 
@@ -786,6 +787,7 @@ void c3h_destroy(c3h_ctx* ctx) {
   release(ctx->segs);
   release(ctx->axmap);
   release(ctx->tileflags);
+  release(ctx->segmap);
   release(ctx->rows);
   release(ctx->work);
   release(ctx->glist);
@@ -1539,6 +1541,11 @@ int extract_frames(c3h_ctx* ctx, const uint32_t* const* grids, int nf, const c3h
       l.ar_magic = magic;
     }
     ENSURE(ctx->work, (size_t)nf * ntiles);
+    if (ctx->capture && c3h::occ_rowwave(div[0], true)) {  // the tick's row-wave stream fills it, whole chunks per frame
+      l.s_segmap = c3h::occ_seg_entries((int64_t)div[0] * div[1] * div[2] / 4, c3h::kOccRowUnroll);
+      ENSURE(ctx->segmap, (size_t)nf * l.s_segmap);
+      l.segmap = ctx->segmap.p;
+    }
     l.tf = ctx->tileflags.p;
     l.work = ctx->work.p;
     l.rows = nullptr;
@@ -2283,7 +2290,10 @@ int pipe_tick(c3h_ctx* ctx, const c3h_ctx::PipeBatch* fresh) {
   tp.prof = &ctx->prof;
   if (fresh && !fresh->stamped) tp.occ = &fresh->l;
   for (auto& b : ctx->pipe) {
-    if (b.age == 1) tp.tile = &b.l;
+    if (b.age == 1) {
+      tp.tile = &b.l;
+      tp.tile_mapped = b.mapped;
+    }
     if (b.age == 2) {
       tp.gate = &b.q;
       tp.comp = &b.sc;
@@ -2316,6 +2326,7 @@ int pipe_tick(c3h_ctx* ctx, const c3h_ctx::PipeBatch* fresh) {
   if (fresh) {
     next.push_back(*fresh);
     next.back().age = 1;
+    next.back().mapped = tp.occ != nullptr;
   }
   ctx->pipe.swap(next);
   return C3H_OK;

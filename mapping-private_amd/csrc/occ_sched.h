@@ -109,6 +109,52 @@ C3H_SCHED_HD OccUnit occ_unit(const OccSched& s, int u) {
   return r;
 }
 
+// ---- the segment-occupancy map (row-wave path of the tick only)
+// One entry (occ_seg_t, below) per span of 256 consecutive voxels (one wave-wide load: 64 lanes x 16 B):
+// entry = voxel index >> 8, (folded) bit s set iff any of the 16 words of the span's s-th aligned
+// 64-byte segment is non-zero.  gx is a multiple of 256 on this path, so a grid row is
+// gx / 256 whole spans and a voxel's bit depends on its x alone.  The stream writes every
+// span of every chunk in every frame (the map is allocated in whole chunks, so a partial
+// last chunk writes zeros past the grid end); the tile role of the next tick skips the halo
+// words whose bit is clear.
+constexpr int kOccSpanVox = 256;
+C3H_SCHED_HD int64_t occ_seg_entry(int64_t voxel) { return voxel >> 8; }
+C3H_SCHED_HD int occ_seg_bit(int64_t voxel) { return (int)((voxel >> 4) & 15); }
+// spans of a chunk of `depth` loads (4 waves x depth), and the map entries of a frame
+C3H_SCHED_HD int occ_chunk_spans(int depth) { return kOccSchedBlock / 64 * depth; }
+C3H_SCHED_HD int64_t occ_seg_entries(int64_t n4, int depth) { return occ_nchunks(n4, depth) * occ_chunk_spans(depth); }
+// the span wave `wave` reads with load j of chunk c (= occ_word(s, c, j, wave * 64) * 4 >> 8)
+C3H_SCHED_HD int64_t occ_span_of(const OccSched& s, int64_t c, int j, int wave) {
+  return c * (s.chunk4 >> 6) + (int64_t)j * (kOccSchedBlock / 64) + wave;
+}
+// a span's entry from the wave's ballot of non-zero 16-byte quads (lane l = quad l)
+C3H_SCHED_HD uint32_t occ_seg_fold32(uint32_t b) {
+  uint32_t y = (b | (b >> 1) | (b >> 2) | (b >> 3)) & 0x11111111u;  // bit 4s: nibble s non-zero
+  y = (y | (y >> 3)) & 0x03030303u;
+  y = (y | (y >> 6)) & 0x000F000Fu;
+  return (y | (y >> 12)) & 0xFFu;
+}
+C3H_SCHED_HD uint16_t occ_seg_fold(uint64_t ballot) {
+  return (uint16_t)(occ_seg_fold32((uint32_t)ballot) | (occ_seg_fold32((uint32_t)(ballot >> 32)) << 8));
+}
+// What the stream stores per span.  C3H_SEG_RAW 0 (shipped): the folded 16 bits (128 KB per
+// 256^3 frame; the stream folds, ~25 VALU per chunk in its row loop).  1 (measured, slower):
+// the ballot as it is (8 bytes, 512 KB per frame; segment s is nibble s, the reader folds):
+// without the fold the stream alone still ends 55-65 us later than with it, the whole tick
+// 4 % later.
+#ifndef C3H_SEG_RAW
+#define C3H_SEG_RAW 0
+#endif
+#if C3H_SEG_RAW
+typedef uint64_t occ_seg_t;
+C3H_SCHED_HD occ_seg_t occ_seg_make(uint64_t ballot) { return ballot; }
+C3H_SCHED_HD bool occ_seg_test(occ_seg_t e, int64_t voxel) { return ((e >> (4 * occ_seg_bit(voxel))) & 15u) != 0; }
+#else
+typedef uint16_t occ_seg_t;
+C3H_SCHED_HD occ_seg_t occ_seg_make(uint64_t ballot) { return occ_seg_fold(ballot); }
+C3H_SCHED_HD bool occ_seg_test(occ_seg_t e, int64_t voxel) { return ((e >> occ_seg_bit(voxel)) & 1u) != 0; }
+#endif
+
 // host: the last 1/div of every frame's chunks go to the pool in units of `unit` chunks
 struct OccSteal {
   int from, unit, units;  // unit = 0: no pooled tail

@@ -207,6 +207,14 @@ int env_int(const char* name, int dflt) {
   return v && *v ? atoi(v) : dflt;
 }
 
+// The segment-occupancy map (occ_sched.h) links a batch's occupancy role to its tile role one
+// tick later: both sides decide from the batch's own launch, so they always agree.  It needs
+// the row-wave stream (whose loads are whole spans) and the per-wave 117 tile body.
+bool tick_segmap_ok(const C3Launch& l, const C3Args& c) {
+  return l.segmap && !C3H_OCC_RING && c.bits && occ_rowwave(l.gx, c.ax) && c.ka.wave117 &&
+         w117_map_fits(l.lmax[0], l.lmax[1], l.lmax[2]);
+}
+
 }  // namespace
 
 bool tick_ok(const C3Launch& l) {
@@ -288,6 +296,10 @@ hipError_t launch_tick(const TickParts& p, hipStream_t s) {
     const int work = std::max(1, std::min(c.tgrid - c.ka.zblocks, env_int("C3H_TICK_TILE", 48)));
     t.ka.zblocks = std::min(c.ka.zblocks, env_int("C3H_TICK_ZERO", 8));
     t.t_grid = t.ka.zblocks + work;
+    if (p.tile_mapped && tick_segmap_ok(*p.tile, c)) {
+      t.ka.segmap = p.tile->segmap;
+      t.ka.s_segmap = p.tile->s_segmap;
+    }
     t.n_tile = t.t_grid * c.nframes;
     lds = std::max(lds, c.tile_lds);
   }
@@ -298,6 +310,10 @@ hipError_t launch_tick(const TickParts& p, hipStream_t s) {
     // roles then see a short HBM queue and the whole tick is shortest
     // (profiles/r1/v1_occ_variants.log, v8/v9: at 32 frames per tick 12.8 us/frame with 256,
     // 14.3 with 384, 15.5 with 192)
+    if (tick_segmap_ok(*p.occ, c)) {
+      t.oa.segmap = p.occ->segmap;
+      t.oa.s_segmap = p.occ->s_segmap;
+    }
     t.o_grid = std::max(1, std::min(c.g1, env_int("C3H_TICK_OCC", std::max(1, 256 / std::max(1, c.nframes)))));
     t.n_occ = t.o_grid * c.nframes;
     lds = std::max(lds, c.occ_lds);
@@ -330,6 +346,7 @@ hipError_t launch_tick(const TickParts& p, hipStream_t s) {
     if (!(mask & 2)) t.n_cg = 0;
     if (!(mask & 4)) t.n_tile = 0;
     if (!(mask & 8)) t.n_occ = 0;
+    if (!(mask & 8)) t.ka.segmap = nullptr;  // no stream, no map
   }
   const int total = t.n_score + t.n_cg + t.n_tile + t.n_occ;
   if (total == 0) return hipSuccess;
