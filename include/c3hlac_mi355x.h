@@ -282,7 +282,10 @@ int c3h_clean_max(c3h_ctx* ctx);
  * (search.cpp:384-480, 539-658, 915-968) on the features of the last extract; the
  * lists continue from their current state.  Writes M x rank detections to `out` (host)
  * and, when remove_overlap != 0, applies SearchObjMulti::removeOverlap
- * (search.cpp:972-992) first.  Returns the number of scheduled modes (>0) or an error. */
+ * (search.cpp:972-992) first.  A scheduled mode whose box does not fit the subdivisions is
+ * skipped (searchPart's loops are empty); when none fits the search finds no candidate and
+ * hands out the lists as they stand (a pending cleanMax applied), on the batch entry points
+ * the setRank state.  Returns the number of scheduled modes (>0) or an error. */
 int c3h_search(c3h_ctx* ctx, const int32_t range[3], int32_t exist_threshold,
                int32_t rotate, int32_t remove_overlap, c3h_det* out);
 /* Asynchronous variant for device-resident pipelines: no host sync; copies the M x rank

@@ -824,6 +824,14 @@ __global__ __launch_bounds__(kBlock) void argmax_finalize_kernel(SparseSearch a,
   argmax_finalize(a, a.partials, a.lists, a.outs[0], nparts, blockIdx.x * (kBlock / 64), gridDim.x * (kBlock / 64));
 }
 unsigned finalize_blocks(int M) { return (unsigned)std::max(1, (M + kBlock / 64 - 1) / (kBlock / 64)); }
+// rank 1 with no position (no scheduled mode fits the subdivisions): no candidate, but every
+// frame's lists still take the clean and go to its output, as the rank replay of zero modes
+// does at higher ranks (blockIdx.y = frame)
+__global__ __launch_bounds__(kBlock) void empty_finalize_kernel(SparseSearch a) {
+  const int64_t f = blockIdx.y;
+  argmax_finalize(a, nullptr, a.lists + f * a.s_lists, a.outs[f], 0, blockIdx.x * (kBlock / 64),
+                  gridDim.x * (kBlock / 64));
+}
 
 __global__ __launch_bounds__(kBlock) void score_list_kernel(SparseSearch b) {
   extern __shared__ __attribute__((aligned(16))) float sl_smem[];
@@ -1114,7 +1122,11 @@ int64_t sparse_score_blocks(const SparseSearch& a) { return (a.pstart[a.nmodes] 
 
 hipError_t launch_sparse_search(const SparseSearch& a, const SparseCompress* sc, hipStream_t s) {
   const int64_t ptot = a.pstart[a.nmodes];
-  if (ptot <= 0) return hipSuccess;
+  if (ptot <= 0) {
+    if (!a.lists) return hipSuccess;  // (rank > 1: the caller's replay writes the lists)
+    empty_finalize_kernel<<<dim3(finalize_blocks(a.M), (unsigned)a.nframes), kBlock, 0, s>>>(a);
+    return hipGetLastError();
+  }
   const unsigned ngate = (unsigned)((ptot + kBlock - 1) / kBlock);
   const unsigned nf = (unsigned)a.nframes;
   if (sc) {  // compress (non-empty rows) and gate in one launch
