@@ -132,14 +132,10 @@ struct VoxArgs {
   int64_t grid_cap;
   int par;                  // epoch parity of this frame
   int clear_grid;           // clear the grid words the previous frame listed
-  int blk0;                 // first accumulate block of this launch (chunked host input)
+  int blk0;                 // first accumulate block of this launch (0: a launch covers the whole frame)
   long long* prof;          // diagnostics builds only (C3H_PROF): per-block phase timestamps
 };
 hipError_t launch_voxelize(const VoxArgs& a, hipStream_t s);
-// the accumulate pass over blocks [a.blk0, a.blk0 + nblocks) only (host frames copied in
-// chunks: each chunk's blocks start when its copy lands; the first launch (blk0 0) resets
-// the counters and clears the previous frame's words)
-hipError_t launch_vox_accum(const VoxArgs& a, int nblocks, hipStream_t s);
 // f16 feature rows -> f32 rows when *flag (device-side check: no host sync)
 hipError_t launch_feat16_to_f32(const _Float16* f16, int f16s, const uint32_t* flag, int64_t H, int F, float* out,
                                 hipStream_t s);
@@ -740,10 +736,6 @@ struct c3h_ctx {
   // the batched voxeliser runs on its own stream, one batch ahead of the tick that consumes
   // it (events: a batch's voxels are done / the tick that last read a buffer set is done)
   hipStream_t pb_vstream = nullptr;
-  // c3h_voxelize of host frames: the chunked H2D's stream, its start and per-chunk events
-  hipStream_t vcopy = nullptr;
-  hipEvent_t vcopy_start = nullptr;
-  std::vector<hipEvent_t> vcopy_ev;
   hipEvent_t pb_vox_ev = nullptr, pb_tick_ev[4] = {nullptr, nullptr, nullptr, nullptr};
 
   std::vector<PipeBatch> pipe;   // in flight, oldest first

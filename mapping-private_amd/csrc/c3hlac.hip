@@ -750,7 +750,7 @@ C3Args build_c3_args(const C3Launch& l) {
   oa.gy = l.gy;
   oa.gz = l.gz;
   oa.axmap = l.axmap;
-  oa.ar_s = kOccArith ? l.ar_s : 0;
+  oa.ar_s = l.ar_s;
   oa.ar_oy = l.ar_oy;
   oa.ar_oz = l.ar_oz;
   oa.ar_magic = l.ar_magic;
@@ -867,10 +867,7 @@ hipError_t launch_c3hlac(const C3Launch& l, hipStream_t s) {
   // matrix-core body is not launched (round 6: its early exit cost a launch, ~4.5 us)
   const bool mf = mfma_ok(l) && !(l.vl_words && l.nframes == 1);
   c.ka.mfma = mf ? 1 : 0;
-#ifndef C3H_OCC_CONTIG
-#define C3H_OCC_CONTIG 1
-#endif
-  c.oa.contiguous = C3H_OCC_CONTIG && l.ntiles >= 65536 ? 1 : 0;  // large grids (config 5): contiguous chunk ranges
+  c.oa.contiguous = l.ntiles >= 65536 ? 1 : 0;  // large grids (config 5): contiguous chunk ranges
   const dim3 g1d((unsigned)c.g1, (unsigned)l.nframes);
   if (l.vl_words && l.nframes == 1) {  // the voxeliser's list of occupied voxels
     if (l.vl_nseg > 0)

@@ -155,27 +155,11 @@ constexpr int kOccBitsMax = 1 << 18;  // 32 KB of LDS bits (512^3 at S >= 8)
 // flight as 2 x 8 pipelined, 4 % shorter tick (profiles/r1/v2_occ_variants.log, v3).  The
 // depths (C3H_OCC_UNROLL: general path, C3H_OCC_ROW_UNROLL: row-wave path) and the chunk
 // schedule are in occ_sched.h, shared with the host.
-#ifndef C3H_OCC_PIPE
-#define C3H_OCC_PIPE 0
-#endif
-// occupied rows: a row's (y, z) subdivision by scalar arithmetic when the maps are uniform
-#ifndef C3H_OCC_ARITH
-#define C3H_OCC_ARITH 1
-#endif
-constexpr bool kOccArith = C3H_OCC_ARITH;
-// occupied rows: a lane's (at most two) subdivisions precomputed (row-wave fast path)
-#ifndef C3H_OCC_PAIR
-#define C3H_OCC_PAIR 1
-#endif
-// rolling load ring over the whole chunks of the row-wave fast path (see there): 1 buffer
-// loads, 2 global loads.  Off: the stream alone gets 1.3 % faster with it, but the whole
+// Measured and removed: a rolling load ring over the row-wave path's whole chunks (a lane's
+// loads never drain at a chunk end).  The stream alone got 1.3 % faster with it, the whole
 // tick 5-8 % slower -- a stream that never drains keeps the HBM queue longer for the
 // latency-bound roles (profiles/r3/occ_ring_ab/)
-#ifndef C3H_OCC_RING
-#define C3H_OCC_RING 0
-#endif
 static_assert(kOccSchedBlock == kBlock, "occ_sched.h: threads per streaming workgroup");
-constexpr bool kOccPipe = C3H_OCC_PIPE;         // next chunk's loads issued before this one is used
 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 constexpr int kAxLds = 3072;  // axis-map entries kept in LDS (gx + gy + gz <= 3072)
 
@@ -279,8 +263,7 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
   // consecutive j of one thread are kBlock*4 voxels apart: step (x, y, z) incrementally
   const int dxs = (kBlock * 4) % gx, drs = (kBlock * 4) / gx;
   int last = -1;
-  // kOccBitsUnroll 16-B loads per lane issued together (with kOccPipe, chunk c+1's loads
-  // are issued before chunk c is processed: 2 x kOccBitsUnroll in flight).  Non-temporal: the grid
+  // kOccBitsUnroll 16-B loads per lane issued together.  Non-temporal: the grid
   // is read once here (the tile pass re-reads only the occupied tiles' halos); measured
   // 6.9-7.0 TB/s vs 6.0-6.3 for default-policy loads.  Past the grid end the address is
   // clamped and the value zeroed (no per-element branch around the load).
@@ -327,7 +310,7 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
         cplx = true;
       }
     }
-    const bool pair_ok = C3H_OCC_PAIR && __ballot(cplx) == 0ull;  // uniform
+    const bool pair_ok = __ballot(cplx) == 0ull;  // uniform
     // The chunk schedule (occ_sched.h): a workgroup's own chunks are rotated over the frame,
     // or, for large stand-alone grids, one contiguous range (a tile's 10 planes meet few
     // workgroups, so the flush stamps each tile ~2.5x fewer times on a dense 512^3 frame);
@@ -337,7 +320,7 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
     const int lg = gx == 256 ? 8 : gx == 512 ? 9 : 10;
     const OccSched sc =
         occ_sched(n4, kRow, gdx, oa.contiguous, oa.steal_from, oa.steal_unit, oa.steal_units, oa.nframes);
-    const int64_t nch = sc.nch, nstat = sc.nstat;
+    const int64_t nstat = sc.nstat;
     uint4 w[kRow];
     static_assert(kRow <= 64, "one lane per row of a chunk holds the row's map entry");
     occ_seg_t* smap = oa.segmap ? oa.segmap + f * oa.s_segmap : nullptr;  // this frame's map (uniform)
@@ -447,104 +430,11 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
       }
       put_map();
     };
-#if C3H_OCC_RING
-    // Rolling ring over whole chunks: slot j of the next chunk is loaded the moment slot j
-    // of this chunk has been read, so each lane keeps kRow loads in flight all
-    // the time (the oldest is always the one waited for: vmcnt(unroll - 1)) instead of
-    // draining to zero at every chunk end.  The loads carry no predicate (whole chunks
-    // only), so none is sunk into a branch (a predicated load forces vmcnt(0) before the
-    // first use).  A partial last chunk, if any, takes the loop below.
-    const int64_t nfull = min(n4 / kChunkR, nstat);  // whole chunks of this frame's own share
-    int64_t ri = 0;
-    if (chunk_of(0) < nfull) {
-      // buffer loads off a per-chunk descriptor: one address VGPR (tid * 16) for all
-      // slots, the slot offset j * 4 KB in an SGPR, non-temporal (aux 2)
-#if C3H_OCC_RING == 2  // diagnostics: global loads off a per-chunk base
-      auto chunk_rsrc = [&](int64_t c) { return reinterpret_cast<const char*>(g4 + c * kChunkR); };
-      auto ring_load = [&](const char* r, int j) {
-        return __builtin_nontemporal_load(reinterpret_cast<const v4u*>(r + voff + j * kBlock * 16));
-      };
-#else
-      auto chunk_rsrc = [&](int64_t c) {
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(g4 + c * kChunkR), (short)0, kChunkR * 16, 0x00020000);
-      };
-      auto ring_load = [&](__amdgpu_buffer_rsrc_t r, int j) {
-        return __builtin_amdgcn_raw_buffer_load_b128(r, voff, j * kBlock * 16, 2);
-      };
-#endif
-      int64_t cur = chunk_of(0);
-      {
-        const auto r = chunk_rsrc(cur);
-#pragma unroll
-        for (int j = 0; j < kRow; ++j) {
-          const v4u t = ring_load(r, j);
-          w[j] = make_uint4(t.x, t.y, t.z, t.w);
-        }
-      }
-      // one chunk; kIssue: slot j of chunk nxt is loaded right after slot j is read
-      auto run_chunk = [&](auto issue, int64_t c, int64_t nxt) {
-        const uint32_t row0 = (uint32_t)(((uint64_t)c * kChunkR * 4 + (uint64_t)wv * 256) >> lg);
-        int y = (int)(row0 % (uint32_t)gy), z = (int)(row0 / (uint32_t)gy);
-        const auto rn = chunk_rsrc(decltype(issue)::value ? nxt : c);
-        auto refill = [&](int j) {  // slot j of the next chunk, once slot j is consumed
-          if constexpr (decltype(issue)::value) {
-            const v4u t = ring_load(rn, j);
-            w[j] = make_uint4(t.x, t.y, t.z, t.w);
-          }
-        };
-#pragma unroll
-        for (int j = 0; j < kRow; ++j) {
-          if (j > 0) refill(j - 1);  // the previous slot is dead: its registers are reused
-          const uint32_t ws[4] = {w[j].x, w[j].y, w[j].z, w[j].w};
-          const int yj = y, zjj = z;
-          y += rpj;
-          while (y >= gy) {
-            y -= gy;
-            ++z;
-          }
-          if (__ballot((ws[0] | ws[1] | ws[2] | ws[3]) != 0u) == 0ull || zjj >= gz) continue;
-          const int a = __builtin_amdgcn_readfirstlane(my[yj]), b = __builtin_amdgcn_readfirstlane(mz[zjj]);
-          if (a < 0 || b < 0) continue;  // uniform: not a centre row
-          const int tyz = ns0 * (a + ns1 * b);
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const int t = tx0[k] + tyz;
-            if (ws[k] && tx0[k] >= 0 && t != last) {
-              last = t;
-              atomicOr(&s_bits[t >> 5], 1u << (t & 31));
-            }
-          }
-        }
-        refill(kRow - 1);
-      };
-      for (;;) {  // chunk_of is increasing: the ring covers exactly the chunks below nfull
-        const int64_t nxt = chunk_of(ri + 1);
-        ++ri;
-        if (nxt < nfull) {  // uniform
-          run_chunk(std::true_type{}, cur, nxt);
-          cur = nxt;
-        } else {
-          run_chunk(std::false_type{}, cur, 0);
-          break;
-        }
-      }
-    }
-    for (int64_t i = ri; i < sc.per; ++i) {
-      if (chunk_of(i) < nfull) continue;  // streamed by the ring (uniform)
-#else
-    if (kOccPipe && chunk_of(0) < nch) load_chunk(w, chunk_of(0) * kChunkR);
     for (int64_t i = 0; i < sc.per; ++i) {
-#endif
       const int64_t cidx = chunk_of(i);
       if (cidx >= nstat) continue;  // uniform: the last, partial round / the pooled tail
       const int64_t c0 = cidx * kChunkR;
-      uint4 nx[kRow];
-      if constexpr (kOccPipe) {  // the next chunk's loads in flight while this one is processed
-        const int64_t cn = chunk_of(i + 1);
-        if (cn < nch) load_chunk(nx, cn * kChunkR);
-      } else {
-        load_any(cidx);
-      }
+      load_any(cidx);
       // uniform 32-bit row arithmetic (rows < 2^24: nvox < 2^32 is host-checked): the
       // chunk's first row, then (y, z) stepped by whole rows per j
       const uint32_t row0 = (uint32_t)(((uint64_t)c0 * 4 + (uint64_t)wv * 256) >> lg);
@@ -558,10 +448,6 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
       }
 #endif
       proc(row0, cidx);
-      if constexpr (kOccPipe) {
-#pragma unroll
-        for (int j = 0; j < kRow; ++j) w[j] = nx[j];
-      }
     }
     __syncthreads();
     occ_flush_bits(s_bits, nwords, s_list, s_wsum, epoch, flags, cnt, work);
@@ -603,8 +489,6 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
   int64_t c0 = bx * (int64_t)kChunk4;
   if (c0 < n4) load_chunk(w, c0);
   for (; c0 < n4; c0 += cstride) {
-    uint4 nx[kOccBitsUnroll];
-    if (kOccPipe && c0 + cstride < n4) load_chunk(nx, c0 + cstride);
     const uint32_t v0 = (uint32_t)((c0 + tid) << 2);  // nvox < 2^32 (host-checked)
     const uint32_t row0 = v0 / (uint32_t)gx;
     int x = (int)(v0 - row0 * (uint32_t)gx);
@@ -649,12 +533,7 @@ __device__ __forceinline__ void occupancy_bits_body(const OccArgs& oa, int bx, i
         atomicOr(&s_bits[t >> 5], 1u << (t & 31));  // result unused: ds_or_b32, no wait
       }
     }
-    if (kOccPipe) {
-#pragma unroll
-      for (int j = 0; j < kOccBitsUnroll; ++j) w[j] = nx[j];
-    } else if (c0 + cstride < n4) {
-      load_chunk(w, c0 + cstride);
-    }
+    if (c0 + cstride < n4) load_chunk(w, c0 + cstride);
   }
   __syncthreads();
   occ_flush_bits(s_bits, nwords, s_list, s_wsum, epoch, flags, cnt, work);
@@ -717,19 +596,6 @@ struct KArgs {
 
 constexpr int kMaxLoads = 4;  // uint4 tile loads per thread kept in flight together
 constexpr int kSegLds = 64;   // segment tables up to 64 segments per axis live in LDS
-#ifndef C3H_TILE_PREFETCH
-#define C3H_TILE_PREFETCH 0  // 1: the next tile's halo into LDS by global_load_lds during this tile's dot4 + epilogue (measured neutral, round 6: DESIGN §8)
-#endif
-// 16 zero bytes: the LDS-DMA source of halo words outside the grid (a lane's LDS-DMA
-// destination is fixed by its lane index, so it cannot be skipped, only pointed at zeros)
-static __device__ const uint4 kHaloZero16 = {0u, 0u, 0u, 0u};
-
-// The (vec-path) halo geometry of a tile: its rows of q4 16-byte pieces starting at x = xs
-struct HaloGeo {
-  int y0, z0, ly, TY, q4, n, xs;
-  bool vec;
-};
-__device__ __forceinline__ HaloGeo halo_geo(const KArgs& a, const int32_t* segs, int tile);
 
 // Persistent workgroups.  Phase Z zero-fills the feature rows of the tiles pass 1 left
 // unflagged (direct mode); phase T walks the work list: stage the (lx+2)x(ly+2)x(lz+1)
@@ -737,26 +603,6 @@ __device__ __forceinline__ HaloGeo halo_geo(const KArgs& a, const int32_t* segs,
 // centres, build the packed dot4 operands and accumulate exactly (see the header).
 #define C3H_PROF(k, cond) \
   if (fprof && tid == 0 && (cond)) fprof[bx * 8 + (k)] = (long long)wall_clock64()
-
-__device__ __forceinline__ HaloGeo halo_geo(const KArgs& a, const int32_t* segs, int tile) {
-  const int ix = tile % a.ns0, iy = (tile / a.ns0) % a.ns1, iz = tile / (a.ns0 * a.ns1);
-  const int32_t* sx = segs + 3 * ix;
-  const int32_t* sy = segs + 3 * (a.seg_stride + iy);
-  const int32_t* sz = segs + 3 * (2 * a.seg_stride + iz);
-  HaloGeo g;
-  const int x0 = sx[0], lx = sx[1];
-  g.y0 = sy[0];
-  g.ly = sy[1];
-  g.z0 = sz[0];
-  const int lz = sz[1];
-  g.vec = (a.gx & 3) == 0 && x0 >= 1 && ((x0 + lx + 1 + 3) & ~3) <= a.gx;
-  g.xs = g.vec ? ((x0 - 1) & ~3) : x0 - 1;
-  const int TX = g.vec ? (((x0 + lx + 1 - g.xs) + 3) & ~3) : lx + 2;
-  g.TY = g.ly + 2;
-  g.q4 = TX >> 2;
-  g.n = g.TY * (lz + 1) * g.q4;
-  return g;
-}
 
 // block bx of gdx for frame fy; smem: c3hlac_lds_bytes(tw_max, list_max) bytes
 __device__ __forceinline__ void c3hlac_tile_body(const KArgs& a, int bx, int fy_, int gdx, uint32_t* smem) {
@@ -825,7 +671,6 @@ __device__ __forceinline__ void c3hlac_tile_body(const KArgs& a, int bx, int fy_
   C3H_PROF(1, true);
 
   if (a.mfma && 2 * nwork >= a.ntiles) return;  // dense frame: c3hlac_mfma_body takes it
-  bool pre = false;  // s_tile already holds this tile's halo (prefetched by the previous tile)
   for (; wi < (a.debug == 4 ? 0 : nwork); wi += G) {
     const int tile = tile_next;
     if (wi + G < nwork) tile_next = fwork[wi + G];
@@ -842,11 +687,10 @@ __device__ __forceinline__ void c3hlac_tile_body(const KArgs& a, int bx, int fy_
     const int nrows = TY * (lz + 1);
     if (tid == 0) s_misc[0] = 0;
 
-    // 1. halo tile; every load of a thread is issued before its first LDS store (or, when
-    //    the previous tile prefetched it, the LDS-DMA retired here)
-    if (pre) {
-      __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else if (vec) {
+    // 1. halo tile; every load of a thread is issued before its first LDS store.  Measured
+    //    and removed (round 6): the next tile's halo prefetched into s_tile by
+    //    LDS-DMA during this tile's dot4 and epilogue -- neutral
+    if (vec) {
       const int q4 = TX >> 2, n = nrows * q4;
       uint4 w[kMaxLoads];
       int idx[kMaxLoads];
@@ -892,7 +736,6 @@ __device__ __forceinline__ void c3hlac_tile_body(const KArgs& a, int bx, int fy_
       }
     }
     lds_barrier();
-    pre = false;  // consumed; the last chunk below may prefetch the next tile
     C3H_PROF(3, wi == bx - a.zblocks);
     if (a.debug == 1) {
       if (tid == 0 && s_tile[0] == 0xdeadbeefu) fexist[0] = 1;  // keep the loads live
@@ -1007,41 +850,6 @@ __device__ __forceinline__ void c3hlac_tile_body(const KArgs& a, int bx, int fy_
       }
       lds_barrier();
       C3H_PROF(2, c0 == 0 && wi == bx - a.zblocks);
-      if (c0 + kChunk >= nlist) {
-        // the last chunk's operands are built: s_tile is free, so the next tile's halo goes
-        // into it by LDS-DMA while this tile's dot4 and epilogue run (round 6; the halo's
-        // global latency was ~2 of ~6.6 us per surface tile).  Retired by the vmcnt wait
-        // at the next tile's phase 1; lds_barrier keeps it in flight (no vmcnt).
-        if (C3H_TILE_PREFETCH && wi + G < nwork) {
-          const HaloGeo g = halo_geo(a, segs, tile_next);
-          if (g.vec && g.n <= kMaxLoads * kBlock) {
-            pre = true;
-            int q = tid / g.q4, r = tid - q * g.q4;
-            const int sq = kBlock / g.q4, sr = kBlock - sq * g.q4;
-#pragma unroll
-            for (int j = 0; j < kMaxLoads; ++j) {
-              const int e = tid + j * kBlock;
-              if (j * kBlock >= g.n) break;  // uniform
-              if (e < g.n) {
-                const int gy = g.y0 - 1 + q % g.TY, gz = g.z0 - 1 + q / g.TY;
-                const uint4* src = ((unsigned)gy < (unsigned)a.gy && (unsigned)gz < (unsigned)a.gz)
-                                       ? reinterpret_cast<const uint4*>(fgrid + ((int64_t)gz * a.gy + gy) * a.gx + g.xs + 4 * r)
-                                       : &kHaloZero16;
-                // wave-uniform LDS base + lane * 16: element e lands at s_tile[4 e]
-                __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(src),
-                                                 reinterpret_cast<void*>(s_tile + 4 * (j * kBlock + (tid & ~63))),
-                                                 16, 0, 0);
-              }
-              q += sq;
-              r += sr;
-              if (r >= g.q4) {
-                r -= g.q4;
-                ++q;
-              }
-            }
-          }
-        }
-      }
       // 4. exact integer accumulation: acc[c] += sum_g dot4(A_c[g], N_{k,n}[g])
       if (tid < 180) {
         const int ng = (min(nlist - c0, kChunk) + 3) >> 2;
@@ -1180,25 +988,16 @@ __device__ __forceinline__ W117Geom w117_geom(const KArgs& a, const int32_t* seg
 // a tile later, puts one table word per piece into a wave-private LDS table
 // (w117_put_map): bit (xx >> 4) - w117_map_sb(xs) of it is the segment of the piece's word
 // xx, xs the piece's first in-grid x.  The lanes that load the words read it back.
-//   raw entries (C3H_SEG_RAW): a grid row's entries are 8 * gx / 256 consecutive bytes, two
-//     segments (nibbles) per byte; the piece's at most two segments lie in the two bytes
-//     from byte xs >> 5 (clamped to the row), fetched as one 2-byte load at any byte
-//     address -- one register per piece, as many as the folded format: a dword pair per
-//     piece spilled 3 VGPRs -- and folded to 4 segment bits here, off the stream's row loop;
-//   folded entries: the span of xs | the span of the piece's last word << 16.
+// A table word is the span entry of xs | the span entry of the piece's last word << 16.
+// Measured and removed: skipping a halo load instruction whose 64 lanes
+// are all gated out (one uniform test per load) -- no vmcnt wait appears among the loads,
+// but five branches per load do, and the tick was no faster (0.8114 against 0.8126 ms).
 constexpr int kW117MapRegs = 3;
-// 1: a halo load instruction whose 64 lanes are all gated out is skipped (one uniform test
-// per load).  Off: no vmcnt wait appears among the loads, but five branches per load do, and
-// the tick is no faster (0.8114 against 0.8126 ms, inside the spread: DESIGN §8 round 10)
-#ifndef C3H_W117_SKIP
-#define C3H_W117_SKIP 0
-#endif
 constexpr int kW117MapWords = kW117MapRegs;  // registers in flight per lane
 __host__ __device__ inline bool w117_map_fits(int lx, int ly, int lz) {
   return (ly + 2) * (lz + 1) <= 64 * kW117MapRegs && lx + 2 <= 16;
 }
-__device__ __forceinline__ int w117_map_off(int xs, int gx) { return min(xs >> 5, (gx >> 5) - 2); }  // raw: first byte in the row
-__device__ __forceinline__ int w117_map_sb(int xs, int gx) { return C3H_SEG_RAW ? 2 * w117_map_off(xs, gx) : (xs >> 8) << 4; }
+__device__ __forceinline__ int w117_map_sb(int xs) { return (xs >> 8) << 4; }
 __device__ __forceinline__ void w117_load_map(const KArgs& a, const occ_seg_t* __restrict__ fmap, const W117Geom& g,
                                               int lane, uint32_t (&me)[kW117MapWords]) {
   const int TY = g.ly + 2, np = TY * (g.lz + 1);
@@ -1210,23 +1009,16 @@ __device__ __forceinline__ void w117_load_map(const KArgs& a, const occ_seg_t* _
     const int yy = g.y0 - 1 + q % TY, zz = g.z0 - 1 + q / TY;
     const bool in = q < np && (unsigned)yy < (unsigned)a.gy && (unsigned)zz < (unsigned)a.gz;
     const int64_t row = in ? ((int64_t)zz * a.gy + yy) * rs : 0;  // clamped: the entry is unused then
-#if C3H_SEG_RAW
-    uint16_t two;
-    __builtin_memcpy(&two, reinterpret_cast<const uint8_t*>(fmap) + 8 * row + w117_map_off(xs, a.gx), 2);
-    me[i] = two;
-    (void)xe;
-#else
     uint32_t e = fmap[row + (xs >> 8)];
     if (rs > 1) e |= (uint32_t)fmap[row + (xe >> 8)] << 16;  // uniform: a row of several spans
     me[i] = e;
-#endif
   }
 }
 // the table words of this tile's pieces (read back by w117_load_halo)
 __device__ __forceinline__ void w117_put_map(uint32_t* s_map, int lane, const uint32_t (&me)[kW117MapWords]) {
 #pragma unroll
   for (int i = 0; i < kW117MapRegs; ++i)
-    s_map[lane + 64 * i] = C3H_SEG_RAW ? occ_seg_fold32(me[i]) & 15u : me[i];  // raw: 4 nibbles -> 4 segment bits
+    s_map[lane + 64 * i] = me[i];
   __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
 
@@ -1240,7 +1032,7 @@ __device__ __forceinline__ void w117_load_halo(const KArgs& a, const uint32_t* _
   const int TX = g.lx + 2, TY = g.ly + 2, n = valid ? TX * TY * (g.lz + 1) : 0;
   int q = lane / TX, r = lane - (lane / TX) * TX;  // e -> (row q, col r), stepped by 64
   const int sq = 64 / TX, sr = 64 - sq * TX;
-  const int sb = w117_map_sb(max(g.x0 - 1, 0), a.gx);  // segment of the table word's bit 0
+  const int sb = w117_map_sb(max(g.x0 - 1, 0));  // segment of the table word's bit 0
 #pragma unroll
   for (int j = 0; j < kW117HaloRegs; ++j) {
     const int e = lane + 64 * j;
@@ -1249,9 +1041,7 @@ __device__ __forceinline__ void w117_load_halo(const KArgs& a, const uint32_t* _
               (unsigned)zz < (unsigned)a.gz;
     if (s_map) in = in && ((s_map[e < n ? q : 0] >> (((xx >> 4) - sb) & 31)) & 1u);  // uniform test, no branch per load
     // clamped address + select: a "load or zero" per element would be a branch per load
-    uint32_t v = 0u;
-    if (!(C3H_W117_SKIP && s_map) || __ballot(in) != 0ull)  // (uniform: see C3H_W117_SKIP)
-      v = fgrid[in ? ((int64_t)zz * a.gy + yy) * a.gx + xx : 0];
+    const uint32_t v = fgrid[in ? ((int64_t)zz * a.gy + yy) * a.gx + xx : 0];
     hv[j] = in ? v : 0u;
     q += sq;
     r += sr;

@@ -34,7 +34,8 @@
 // Round 6: tiles of two-step layers (S <= 10, pitch 12: every interior tile of config 5)
 // hold each layer as a voxel-major record image instead of channel planes and read the
 // operands back through ds_read_b64_tr_b8 (mf_layer_ksteps_tr): the conversion needs no
-// byte transpose, and the dx shifts are immediate address offsets.
+// byte transpose, and the dx shifts are immediate address offsets.  The planar two-step
+// K steps it replaced (rounds 3 to 5) are removed: DESIGN.md, "Retired variants".
 #pragma once
 #include "c3hlac_dev.h"
 
@@ -45,12 +46,6 @@ constexpr int kMfWaves = kBlock / 64;
 constexpr int kMfCh = 12;
 constexpr int kMfK = 14;    // 13 offsets + the centre's own channels
 constexpr int kMfLoad = 2;  // (row, dword) items per lane of a layer (<= 18 rows x 5 dwords)
-#ifndef C3H_MF_TWO
-#define C3H_MF_TWO 1  // two-step layers with the lane-group-contiguous position map
-#endif
-#ifndef C3H_MF_GAP
-#define C3H_MF_GAP 16  // diagnostics: 0 = the round-3 plane placement of the two-step layers
-#endif
 #ifndef C3H_MF_EXP
 #define C3H_MF_EXP 0  // diagnostics variants: 1 no K steps, 2 no conversion, 4 no bin epilogue, 8 no layer loads
 #endif
@@ -74,13 +69,9 @@ __host__ __device__ inline int mf_plane_bytes(int lx, int ly) {
   return ((m - 32 + 255) & ~255) + 32;
 }
 __host__ __device__ inline int mf_r256(int x) { return (x + 255) & ~255; }
-// (+16: the two-step layers put planes 4..11 one 16-byte block further, see mf_layer_ksteps2)
-__host__ __device__ inline int mf_slot_stride(int pb) { return mf_r256(kMfCh * pb + 16); }
-#ifndef C3H_MF_SLOTS
-#define C3H_MF_SLOTS 3  // layer slots per wave (2: layer z + 2 reuses layer z's slot after its K steps)
-#endif
-constexpr int kMfSlots = C3H_MF_SLOTS;
-static_assert(kMfSlots == 2 || kMfSlots == 3, "layer slots");
+// (a plane is 32 mod 256 bytes, so the 12 planes of a slot end at 128 mod 256)
+__host__ __device__ inline int mf_slot_stride(int pb) { return mf_r256(kMfCh * pb); }
+constexpr int kMfSlots = 3;  // layer slots per wave
 __host__ __device__ inline int mf_wave_stride(int pb) { return kMfSlots * mf_slot_stride(pb) + mf_r256(pb); }
 __host__ __device__ inline int mf_const_bytes(int pb) { return mf_r256(128 + 3 * pb); }
 // 3 x 256 channel-byte tables | 128 B | 3 constant planes (0x00, 0x01, 0xff) | per-wave
@@ -196,348 +187,6 @@ __device__ __forceinline__ void mf_layer_ksteps(const uint8_t* pp, const uint8_t
   }
 }
 
-// Layers of exactly two K steps (S <= 10 tiles: pitch 12, 12 rows -> 128 positions): lane
-// group h takes the 32 consecutive positions 32 h .. 32 h + 31 over both steps (K step ks
-// gets 32 h + 16 ks + i; the position -> (step, lane group, byte) map is a bijection and A,
-// B and the mask use the same one, so the integer sums are unchanged).  A plane row then
-// costs NB = 3-4 ds_read_b128 for both steps instead of 2 x 2-3: 16 instead of 22 reads
-// per layer, and the centre mask (the same plane for every layer) stays in registers.
-// Banks: lane (h, n) reads plane n at 32 h, so with planes at a 288-byte stride (18 blocks
-// of 16 B) the 4-bank block of every lane is even and a ds_read_b128 lane group (lanes
-// {0-3, 12-15, 20-27} = (h 0, n 0-3 / 12-15), (h 1, n 4-11), ...) met its own blocks twice
-// (2-way, every read).  Planes 4..11 then sit one block further (odd blocks): the 12 real
-// lanes of each group hit 12 distinct blocks and the constant planes (blocks 8, 10) the
-// rest.  The one-step layout (16 h) is conflict-free without the shift.
-template <int DYR, int DXLO, int DXHI>
-struct MfRow2 {
-  static constexpr int B0 = mf_fdiv16(DYR + DXLO), NB = mf_fdiv16(DYR + DXHI + 31) - B0 + 1;
-  uint32_t w[4 * NB];
-  mf_u4 q[NB];
-  __device__ __forceinline__ void load(const uint8_t* row) {
-    const uint8_t* p = static_cast<const uint8_t*>(__builtin_assume_aligned(row, 16));
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      mf_u4 v = *reinterpret_cast<const mf_u4*>(p + 16 * (B0 + b));
-      __asm__("" : "+v"(v));  // keep the whole block: a narrowed ds_read_b32 bank-conflicts
-      w[4 * b] = v.x; w[4 * b + 1] = v.y; w[4 * b + 2] = v.z; w[4 * b + 3] = v.w;
-    }
-  }
-  // prefetch: issue() the reads, pin() where the row is first used -- the whole-block
-  // barrier then sits after the work issued in between, which hides the LDS latency
-  __device__ __forceinline__ void issue(const uint8_t* row) {
-    const uint8_t* p = static_cast<const uint8_t*>(__builtin_assume_aligned(row, 16));
-#pragma unroll
-    for (int b = 0; b < NB; ++b) q[b] = *reinterpret_cast<const mf_u4*>(p + 16 * (B0 + b));
-  }
-  __device__ __forceinline__ void pin() {
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      mf_u4 v = q[b];
-      __asm__("" : "+v"(v));
-      w[4 * b] = v.x; w[4 * b + 1] = v.y; w[4 * b + 2] = v.z; w[4 * b + 3] = v.w;
-    }
-  }
-  template <int DX, int KS>
-  __device__ __forceinline__ mf_v4i frag() const {
-    constexpr int e = DYR + DX + 16 * KS - 16 * B0, d = e >> 2, sh = e & 3;
-    mf_v4i f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      f[i] = sh ? (int)__builtin_amdgcn_alignbyte(w[d + i + 1], w[d + i], sh) : (int)w[d + i];
-    return f;
-  }
-};
-
-#ifndef C3H_MF_PREFETCH
-#define C3H_MF_PREFETCH 1  // two-step layers: each plane row's reads issued one row ahead
-#endif
-#ifndef C3H_MF_ASHIFT
-#define C3H_MF_ASHIFT 1  // two-step layers: the dx shifts on the centre operand (round 5)
-#endif
-
-// Two-step layers with the x shifts moved to the centre operand (round 5).  An offset
-// (dx, R) pairs the centre at position v with the neighbour at v + dx + R; written over
-// K = v + dx, that is A_s[K] = Xm(K + s) with s = -dx against the UNSHIFTED neighbour row
-// B[K] = Y(K + R).  The three dx of a row then share one B fragment, and only the masked
-// centre row is shifted: per K step two 4-dword v_alignbyte sets (A_{+1}, A_{-1}) instead
-// of two per neighbour row, and the centre mask is applied once, to the 10 dwords a lane
-// group's positions and their +-1 bytes span (mk: the tile's mask words, once per tile).
-// Each A_s still visits every centre exactly once: centres lie at K positions 1 ..
-// (ly - 1) PW + lx <= 118 of 0 .. 127, so A_{+1} (positions 1 .. 128) and A_{-1} (-1 ..
-// 126) cover them, and the positions a shift moves in or out (-1, 0, 127, 128) are
-// never centres: every A_s has the same row sums (the epilogue's rs) and
-// sum (A'+128)(B'+128) over K is the exact sum over centres, whatever B holds elsewhere.
-template <int R>
-__device__ __forceinline__ void mf_layer_ksteps2s(const uint8_t* pp, const uint8_t* pc, const uint32_t (&mk)[10],
-                                                  int pw16, int h4, mf_v4i (&acc)[kMfK]) {
-  const int o = 32 * h4;
-  MfRow2<0, -1, 1> c0;   // dz = 0, dy = 0: bytes -16 .. +48 around the lane group's 32
-  MfRow2<-R, 0, 0> cm;   // dz = 0, dy = -1 (k = 9 + dx + 1)
-  c0.issue(pc + o);
-  cm.issue(pc + o - pw16);
-  c0.pin();
-  // masked centre words am[j] = bytes 32 h + 4 (j - 1) .. + 3 (c0.w index j + 3: B0 = -1)
-  uint32_t am[10];
-#pragma unroll
-  for (int j = 0; j < 10; ++j) am[j] = (c0.w[j + 3] & mk[j]) | (0x80808080u & ~mk[j]);
-  mf_v4i A[3][2];  // [s + 1][ks]: A_s of K step ks
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int j = 4 * ks + i + 1;
-      A[1][ks][i] = (int)am[j];
-      A[2][ks][i] = (int)__builtin_amdgcn_alignbyte(am[j + 1], am[j], 1);  // s = +1
-      A[0][ks][i] = (int)__builtin_amdgcn_alignbyte(am[j], am[j - 1], 3);  // s = -1
-    }
-  // offset k of a row with dx = -1, 0, +1 uses A_{+1}, A_0, A_{-1}
-#define C3H_MF3(BF, K0, KS)                                                                              \
-  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                     \
-    const mf_v4i b = ks ? BF.template frag<0, 1>() : BF.template frag<0, 0>();                          \
-    acc[K0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[2][ks], b, acc[K0], 0, 0, 0);                     \
-    acc[K0 + KS] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[1][ks], b, acc[K0 + KS], 0, 0, 0);          \
-    acc[K0 + 2 * KS] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[0][ks], b, acc[K0 + 2 * KS], 0, 0, 0);  \
-  }
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-    acc[13] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[1][ks], A[1][ks], acc[13], 0, 0, 0);  // own channels
-    // (-1, 0, 0): the unshifted dz = 0 row against A_{+1}
-    acc[12] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[2][ks], ks ? c0.template frag<0, 1>() : c0.template frag<0, 0>(),
-                                                   acc[12], 0, 0, 0);
-  }
-  MfRow2<-R, 0, 0> rm;  // dz = -1, dy = -1: k = 3 (dx + 1)
-  rm.issue(pp + o - pw16);
-  cm.pin();
-  C3H_MF3(cm, 9, 1)
-  MfRow2<0, 0, 0> r0;  // dz = -1, dy = 0: k = 3 (dx + 1) + 1
-  r0.issue(pp + o);
-  rm.pin();
-  C3H_MF3(rm, 0, 3)
-  MfRow2<R, 0, 0> rp;  // dz = -1, dy = +1: k = 3 (dx + 1) + 2
-  rp.issue(pp + o + pw16);
-  r0.pin();
-  C3H_MF3(r0, 1, 3)
-  rp.pin();
-  C3H_MF3(rp, 2, 3)
-#undef C3H_MF3
-}
-template <int R>
-__device__ __forceinline__ void mf_layer_ksteps2(const uint8_t* pp, const uint8_t* pc, const mf_u4 (&mk)[2],
-                                                 int pw16, int h4, mf_v4i (&acc)[kMfK]) {
-  const int o = 32 * h4;
-  mf_v4i A0, A1;
-#define C3H_MF2(ROW, DX, K)                                                                                 \
-  acc[K] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A0, ROW.template frag<DX, 0>(), acc[K], 0, 0, 0);      \
-  acc[K] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A1, ROW.template frag<DX, 1>(), acc[K], 0, 0, 0);
-  if (C3H_MF_PREFETCH) {
-    MfRow2<0, -1, 0> c0;   // dz = 0, dy = 0: the centres and dx = -1
-    MfRow2<-R, -1, 1> cm;  // dz = 0, dy = -1: k = 9 + dx + 1
-    c0.issue(pc + o);
-    cm.issue(pc + o - pw16);
-    c0.pin();
-    const mf_v4i a0 = c0.template frag<0, 0>(), a1 = c0.template frag<0, 1>();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      A0[i] = (int)(((uint32_t)a0[i] & mk[0][i]) | (0x80808080u & ~mk[0][i]));
-      A1[i] = (int)(((uint32_t)a1[i] & mk[1][i]) | (0x80808080u & ~mk[1][i]));
-    }
-    acc[13] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A0, A0, acc[13], 0, 0, 0);  // own channels
-    acc[13] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A1, A1, acc[13], 0, 0, 0);
-    acc[12] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A0, c0.template frag<-1, 0>(), acc[12], 0, 0, 0);  // (-1, 0, 0)
-    acc[12] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A1, c0.template frag<-1, 1>(), acc[12], 0, 0, 0);
-    MfRow2<-R, -1, 1> rm;  // dz = -1, dy = -1: k = 3 (dx + 1)
-    rm.issue(pp + o - pw16);
-    cm.pin();
-    C3H_MF2(cm, -1, 9)
-    C3H_MF2(cm, 0, 10)
-    C3H_MF2(cm, 1, 11)
-    MfRow2<0, -1, 1> r0;  // dz = -1, dy = 0
-    r0.issue(pp + o);
-    rm.pin();
-    C3H_MF2(rm, -1, 0)
-    C3H_MF2(rm, 0, 3)
-    C3H_MF2(rm, 1, 6)
-    MfRow2<R, -1, 1> rp;  // dz = -1, dy = +1
-    rp.issue(pp + o + pw16);
-    r0.pin();
-    C3H_MF2(r0, -1, 1)
-    C3H_MF2(r0, 0, 4)
-    C3H_MF2(r0, 1, 7)
-    rp.pin();
-    C3H_MF2(rp, -1, 2)
-    C3H_MF2(rp, 0, 5)
-    C3H_MF2(rp, 1, 8)
-    return;
-  }
-  {
-    // dz = 0: row 0 (the centres and dx = -1)
-    MfRow2<0, -1, 0> c0;
-    c0.load(pc + o);
-    const mf_v4i a0 = c0.template frag<0, 0>(), a1 = c0.template frag<0, 1>();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      A0[i] = (int)(((uint32_t)a0[i] & mk[0][i]) | (0x80808080u & ~mk[0][i]));
-      A1[i] = (int)(((uint32_t)a1[i] & mk[1][i]) | (0x80808080u & ~mk[1][i]));
-    }
-    acc[13] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A0, A0, acc[13], 0, 0, 0);  // own channels
-    acc[13] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A1, A1, acc[13], 0, 0, 0);
-    acc[12] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A0, c0.template frag<-1, 0>(), acc[12], 0, 0, 0);  // (-1, 0, 0)
-    acc[12] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A1, c0.template frag<-1, 1>(), acc[12], 0, 0, 0);
-  }
-  {
-    MfRow2<-R, -1, 1> cm;  // dz = 0, dy = -1: k = 9 + dx + 1
-    cm.load(pc + o - pw16);
-    C3H_MF2(cm, -1, 9)
-    C3H_MF2(cm, 0, 10)
-    C3H_MF2(cm, 1, 11)
-  }
-  {
-    MfRow2<-R, -1, 1> r;  // dz = -1, dy = -1: k = 3 (dx + 1)
-    r.load(pp + o - pw16);
-    C3H_MF2(r, -1, 0)
-    C3H_MF2(r, 0, 3)
-    C3H_MF2(r, 1, 6)
-  }
-  {
-    MfRow2<0, -1, 1> r;  // dz = -1, dy = 0
-    r.load(pp + o);
-    C3H_MF2(r, -1, 1)
-    C3H_MF2(r, 0, 4)
-    C3H_MF2(r, 1, 7)
-  }
-  {
-    MfRow2<R, -1, 1> r;  // dz = -1, dy = +1
-    r.load(pp + o + pw16);
-    C3H_MF2(r, -1, 2)
-    C3H_MF2(r, 0, 5)
-    C3H_MF2(r, 1, 8)
-  }
-#undef C3H_MF2
-}
-
-#ifndef C3H_MF_OCCMASK
-#define C3H_MF_OCCMASK 1  // layer conversion: empty voxels restored by a per-dword mask, not a per-read select
-#endif
-#ifndef C3H_MF_PBASE
-#define C3H_MF_PBASE 1  // per-item grid offsets formed once per tile (layer L adds L x the z stride; 2.5 % on config 5)
-#endif
-#ifndef C3H_MF_SHAPE_CACHE
-#define C3H_MF_SHAPE_CACHE 1  // the tile shape's mask and item map kept across same-shape tiles
-#endif
-#ifndef C3H_MF_LOADX4
-#define C3H_MF_LOADX4 1  // a layer item whose 4 words all lie in the grid: one 16-B load
-#endif
-#ifndef C3H_MF_U32
-#define C3H_MF_U32 0  // two-step layers: dx = +-1 and unaligned fragments as byte-offset ds_read_b32
-#endif
-// Diagnostics: the two-step layers with every fragment not on a 16-byte boundary read as
-// four 32-bit LDS loads at its byte offset (each fenced from its neighbours so the compiler
-// does not merge them) instead of whole blocks + v_alignbyte: 68 fewer VALU per layer, but
-// a ds_read_b32 off a 4-byte boundary is replayed, and config 5 took 11.2 ms instead of
-// 1.43 (profiles/r4/config5_ab/): the alignbyte form stays.
-typedef uint32_t __attribute__((aligned(1))) mf_u32_ua;
-__device__ __forceinline__ uint32_t mf_ld32(const uint8_t* p) {
-  const uint32_t v = *reinterpret_cast<const mf_u32_ua*>(p);
-  mf_compiler_fence();
-  return v;
-}
-template <int OFF>
-__device__ __forceinline__ mf_v4i mf_frag32(const uint8_t* row) {
-  if constexpr ((OFF & 15) == 0) {
-    const mf_u4 v = *reinterpret_cast<const mf_u4*>(__builtin_assume_aligned(row + OFF, 16));
-    return mf_v4i{(int)v.x, (int)v.y, (int)v.z, (int)v.w};
-  } else {
-    mf_v4i f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) f[i] = (int)mf_ld32(row + OFF + 4 * i);
-    return f;
-  }
-}
-// a plane row's fragments dx = -1 .. NDX - 2 of both K steps: 8 NDX loads issued together
-// (from row + DYR - 1, so every offset is a non-negative immediate)
-template <int DYR, int NDX>
-__device__ __forceinline__ void mf_rowu(const uint8_t* row, mf_v4i (&f)[NDX][2]) {
-  const uint8_t* b = row + DYR - 1;
-#pragma unroll
-  for (int d = 0; d < NDX; ++d)
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) f[d][ks][i] = (int)mf_ld32(b + d + 16 * ks + 4 * i);
-}
-template <int R>
-__device__ __forceinline__ void mf_layer_ksteps2u(const uint8_t* pp, const uint8_t* pc, const mf_u4 (&mk)[2],
-                                                  int pw16, int h4, mf_v4i (&acc)[kMfK]) {
-  const int o = 32 * h4;
-  const uint8_t* c0 = static_cast<const uint8_t*>(__builtin_assume_aligned(pc + o, 16));
-  mf_v4i A0, A1;
-  {
-    const mf_u4 a0 = *reinterpret_cast<const mf_u4*>(c0), a1 = *reinterpret_cast<const mf_u4*>(c0 + 16);
-    mf_v4i fl[1][2];
-    mf_rowu<0, 1>(c0, fl);  // dx = -1
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      A0[i] = (int)((a0[i] & mk[0][i]) | (0x80808080u & ~mk[0][i]));
-      A1[i] = (int)((a1[i] & mk[1][i]) | (0x80808080u & ~mk[1][i]));
-    }
-    acc[13] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A0, A0, acc[13], 0, 0, 0);  // own channels
-    acc[13] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A1, A1, acc[13], 0, 0, 0);
-    acc[12] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A0, fl[0][0], acc[12], 0, 0, 0);  // (-1, 0, 0)
-    acc[12] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A1, fl[0][1], acc[12], 0, 0, 0);
-  }
-  auto row3 = [&](const mf_v4i (&f)[3][2], int k0, int kstep) {
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      acc[k0 + kstep * d] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A0, f[d][0], acc[k0 + kstep * d], 0, 0, 0);
-      acc[k0 + kstep * d] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A1, f[d][1], acc[k0 + kstep * d], 0, 0, 0);
-    }
-  };
-  {
-    mf_v4i f[3][2];
-    mf_rowu<-R, 3>(pc + o - pw16, f);  // dz = 0, dy = -1: k = 9 + dx + 1
-    row3(f, 9, 1);
-  }
-  {
-    mf_v4i f[3][2];
-    mf_rowu<-R, 3>(pp + o - pw16, f);  // dz = -1, dy = -1: k = 3 (dx + 1)
-    row3(f, 0, 3);
-  }
-  {
-    mf_v4i f[3][2];
-    mf_rowu<0, 3>(pp + o, f);  // dz = -1, dy = 0
-    row3(f, 1, 3);
-  }
-  {
-    mf_v4i f[3][2];
-    mf_rowu<R, 3>(pp + o + pw16, f);  // dz = -1, dy = +1
-    row3(f, 2, 3);
-  }
-}
-
-#ifndef C3H_MF_TR
-#define C3H_MF_TR 1  // two-step layers as a record image read by ds_read_b64_tr_b8 (round 6)
-#endif
-#ifndef C3H_MF_BFI
-#define C3H_MF_BFI 1  // record path: the centre masks as one v_bfi_b32 per dword
-#endif
-#ifndef C3H_MF_B96
-#define C3H_MF_B96 0  // record path: 12-byte record stores, the padding dword written once per tile (slower: 1.09 vs 1.01 ms)
-#endif
-#ifndef C3H_MF_BUFLD
-#define C3H_MF_BUFLD 1  // record path: branch-free raw buffer loads of the layer words
-#endif
-#ifndef C3H_MF_PLSWAP
-#define C3H_MF_PLSWAP 0  // epilogue: row 15's column sums broadcast by two permlane swaps, not ds_bpermute (correct, measured neutral)
-#endif
-#ifndef C3H_MF_ST16
-#define C3H_MF_ST16 1  // fp16 rows: the epilogue stages halves (8-byte LDS stores) instead of floats
-#endif
-#ifndef C3H_MF_SRC2
-#define C3H_MF_SRC2 1  // f16 epilogue: the bin -> stage table read as u16 pairs (one LDS read per pair)
-#endif
-#ifndef C3H_MF_UNIWID
-#define C3H_MF_UNIWID 1  // the wave index through readfirstlane (scalar tile loop)
-#endif
 // Record image (round 6).  A two-step layer (pitch 12, 12 rows) is held voxel-major: the
 // voxel at position p = row * 12 + col has the 16-byte record at byte 16 p of the slot,
 // bytes 0..11 = its 12 channel bytes (per colour the setColor table dword {sin, cos, beta,
@@ -557,26 +206,12 @@ __device__ __forceinline__ void mf_layer_ksteps2u(const uint8_t* pp, const uint8
 // Records 144..151 of a slot (read by the dy = +1 rows beyond the window's centres) are
 // constant padding records.
 constexpr int kMfRecPos = 152;
-#ifndef C3H_MF_TRFENCE
-#define C3H_MF_TRFENCE 1  // record K steps: compiler fences hold each row's reads one row ahead
-#endif
-#ifndef C3H_MF_KSMAJOR
-#define C3H_MF_KSMAJOR 1  // record K steps: K step 0's 14 MFMAs, then step 1's (0: row by row, reads one row ahead)
-#endif
-#define C3H_MFT_FENCE() \
-  do {                  \
-    if (C3H_MF_TRFENCE) mf_compiler_fence(); \
-  } while (0)
 typedef int mf_v2i __attribute__((ext_vector_type(2)));
 // (x & m) | (0x80808080 & ~m): one v_bfi_b32 (the compiler split it into two bit ops)
 __device__ __forceinline__ int mf_bfi80(uint32_t m, uint32_t x) {
-#if C3H_MF_BFI
   uint32_t r;
   __asm__("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(m), "v"(x), "v"(0x80808080u));
   return (int)r;
-#else
-  return (int)((x & m) | (0x80808080u & ~m));
-#endif
 }
 typedef mf_v2i __attribute__((address_space(3))) * mf_lds_v2i;
 template <int OFF>
@@ -594,8 +229,6 @@ __device__ __forceinline__ mf_v4i mf_trrow(const uint8_t* b) {
 }
 __device__ __forceinline__ void mf_layer_ksteps_tr(const uint8_t* pp, const uint8_t* pc, const uint32_t (&mk)[3][2][4],
                                                    mf_v4i (&acc)[kMfK]) {
-  // the reads are issued one row ahead of the MFMAs that use them (compiler fences keep
-  // the scheduler from hoisting every read of the layer, which spilled)
   mf_v4i A[3][2], X0[2];
   {
     const mf_v4i xm[2] = {mf_trrow<-1, 0>(pc), mf_trrow<-1, 1>(pc)};
@@ -611,8 +244,8 @@ __device__ __forceinline__ void mf_layer_ksteps_tr(const uint8_t* pp, const uint
         A[2][ks][i] = mf_bfi80(mk[2][ks][i], (uint32_t)xp[ks][i]);
       }
   }
-#if C3H_MF_KSMAJOR
   // every K step's 14 MFMAs before the next step's: 14 MFMAs between two into one accumulator
+  // (offset k of a row with dx = -1, 0, +1 uses A_{+1}, A_0, A_{-1})
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
     const mf_v4i bcm = ks ? mf_trrow<-12, 1>(pc) : mf_trrow<-12, 0>(pc);
@@ -631,47 +264,12 @@ __device__ __forceinline__ void mf_layer_ksteps_tr(const uint8_t* pp, const uint
     C3H_MFK(brp, 2, 3)
 #undef C3H_MFK
   }
-  return;
-#endif
-  mf_v4i b0[2] = {mf_trrow<-12, 0>(pc), mf_trrow<-12, 1>(pc)};  // dz = 0, dy = -1
-  C3H_MFT_FENCE();
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-    acc[13] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[1][ks], A[1][ks], acc[13], 0, 0, 0);  // own channels
-    acc[12] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[2][ks], X0[ks], acc[12], 0, 0, 0);    // (-1, 0, 0)
-  }
-  // offset k of a row with dx = -1, 0, +1 uses A_{+1}, A_0, A_{-1}
-#define C3H_MFT3(B, K0, KS)                                                                               \
-  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                      \
-    acc[K0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[2][ks], B[ks], acc[K0], 0, 0, 0);                  \
-    acc[K0 + KS] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[1][ks], B[ks], acc[K0 + KS], 0, 0, 0);       \
-    acc[K0 + 2 * KS] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[0][ks], B[ks], acc[K0 + 2 * KS], 0, 0, 0); \
-  }
-  mf_v4i b1[2] = {mf_trrow<-12, 0>(pp), mf_trrow<-12, 1>(pp)};  // dz = -1, dy = -1
-  C3H_MFT_FENCE();
-  C3H_MFT3(b0, 9, 1)  // dz = 0, dy = -1: k = 9 + dx + 1
-  b0[0] = mf_trrow<0, 0>(pp);  // dz = -1, dy = 0
-  b0[1] = mf_trrow<0, 1>(pp);
-  C3H_MFT_FENCE();
-  C3H_MFT3(b1, 0, 3)  // dz = -1, dy = -1: k = 3 (dx + 1)
-  b1[0] = mf_trrow<12, 0>(pp);  // dz = -1, dy = +1
-  b1[1] = mf_trrow<12, 1>(pp);
-  C3H_MFT_FENCE();
-  C3H_MFT3(b0, 1, 3)  // dz = -1, dy = 0
-  C3H_MFT3(b1, 2, 3)  // dz = -1, dy = +1
-#undef C3H_MFT3
 }
 
 // lane l gets x of lane 48 + (l & 15) (the accumulator's row 15 to every lane group); every
-// lane active
+// lane active.  Measured and removed: two permlane swaps instead of the ds_bpermute (neutral)
 __device__ __forceinline__ uint32_t mf_row3_bcast(uint32_t x) {
-#if C3H_MF_PLSWAP
-  const auto a = __builtin_amdgcn_permlane32_swap(x, x, false, false);     // [1]: rows 2 3 2 3
-  const auto b = __builtin_amdgcn_permlane16_swap(a[1], a[1], false, false);  // [1]: rows 3 3 3 3
-  return b[1];
-#else
   return (uint32_t)__shfl((int)x, 48 + (int)(threadIdx.x & 15), 64);
-#endif
 }
 
 // plane p -> (type, reference channel); p >= 12 is padding
@@ -686,7 +284,7 @@ __device__ __forceinline__ void c3hlac_mfma_body(const KArgs& a, int wid_, int n
   const int64_t fy = fy_;
   // the wave index is wave-uniform: the tile loop's loads and the record path's buffer
   // descriptors stay scalar
-  const int wid = C3H_MF_UNIWID ? __builtin_amdgcn_readfirstlane(wid_) : wid_;
+  const int wid = __builtin_amdgcn_readfirstlane(wid_);
   const uint32_t* __restrict__ fgrid = a.grids[fy];
   float* __restrict__ ffeat = a.feat + fy * a.s_feat;
   int32_t* __restrict__ fexist = a.exist + fy * a.s_h;
@@ -743,7 +341,7 @@ __device__ __forceinline__ void c3hlac_mfma_body(const KArgs& a, int wid_, int n
   const int h4k = lane >> 4, nk = lane & 15;
   const bool realk = nk < kMfCh;
 
-  int shape_prev = -1;  // the tile shape whose mask and item map are current (C3H_MF_SHAPE_CACHE)
+  int shape_prev = -1;  // the tile shape whose mask and item map are current
   int it_row[LOAD], it_q[LOAD];
   uint32_t it_xs[LOAD];
   for (int wi = wid; wi < nwork; wi += nw) {
@@ -758,18 +356,17 @@ __device__ __forceinline__ void c3hlac_mfma_body(const KArgs& a, int wid_, int n
     const int PB = mf_plane_bytes(lx, ly);
     const int ipr = PW >> 2, nitem = TY * ipr;
     const int SS = mf_slot_stride(PB);
-    const bool two = C3H_MF_TWO && nks == 2 && (PW & 15) == 12;  // mf_layer_ksteps2's layers
-    const int gap = two ? C3H_MF_GAP : 0;  // planes 4..11 shifted (banks, see mf_layer_ksteps2)
+    // two-step layers (pitch 12): record image + transposed reads (mf_layer_ksteps_tr)
+    const bool rec = nks == 2 && (PW & 15) == 12;
     uint8_t* mask = wl + kMfSlots * SS;
-    const bool trp = C3H_MF_TR && two;  // record image + transposed reads (mf_layer_ksteps_tr)
     // The tile shape's centre mask and item map (divisions by the pitch: ~300 VALU) are
     // built when the shape differs from this wave's previous tile; S-uniform grids give
     // every interior tile one shape (the mask stays in the wave's LDS region, past the
     // epilogue's staging)
     const int shape = lx | (ly << 8);
-    if (!C3H_MF_SHAPE_CACHE || shape != shape_prev) {
+    if (shape != shape_prev) {
       shape_prev = shape;
-      if (trp) {
+      if (rec) {
         // record path: per lane group h, 24 mask words (s + 1, ks, i) at mask + 96 h; byte
         // b of word i: position 12 + 64 ks + 32 (j >> 3) + 8 h + (j & 7) + s, j = 4 i + b
         for (int d = lane; d < 96; d += 64) {
@@ -785,7 +382,8 @@ __device__ __forceinline__ void c3hlac_mfma_body(const KArgs& a, int wid_, int n
         }
       } else
       // centre mask of the K positions PW + 4 j + b: rows 1..ly, columns 1..lx
-      // (one word more on each side: the shifted centre rows of mf_layer_ksteps2s read them)
+      // (one word more on each side, which only the removed planar two-step K steps read:
+      // with the tight bounds the LOAD = 2 kernel allocates 168 VGPRs instead of 167)
       for (int j = lane - 1; j < 16 * nks + 1; j += 64) {
         uint32_t m = 0;
 #pragma unroll
@@ -822,13 +420,11 @@ __device__ __forceinline__ void c3hlac_mfma_body(const KArgs& a, int wid_, int n
       it_xm[i] = xm;
     }
     uint32_t wv[2][LOAD][4];
-#if C3H_MF_PBASE
-    // each item's word at layer 0, once per tile (layer L adds L x the z stride)
+    // each item's word at layer 0, once per tile (layer L adds L x the z stride; 2.5 % on config 5)
     const int64_t zst = (int64_t)a.gy * a.gx;
     int64_t it_base[LOAD];
 #pragma unroll
     for (int i = 0; i < LOAD; ++i) it_base[i] = ((int64_t)(z0 - 1) * a.gy + it_gy[i]) * a.gx + it_x[i];
-#endif
     auto load_layer = [&](int L, uint32_t (&w)[LOAD][4]) {
 #if C3H_MF_EXP & 8
       if (L >= 4) return;  // diagnostics: layers 4.. convert stale words (no loads in the layer loop)
@@ -838,12 +434,8 @@ __device__ __forceinline__ void c3hlac_mfma_body(const KArgs& a, int wid_, int n
 #pragma unroll
       for (int i = 0; i < LOAD; ++i) {
         const bool rowin = zin && it_gy[i] >= 0;
-#if C3H_MF_PBASE
         const uint32_t* src = fgrid + (it_base[i] + L * zst);
-#else
-        const uint32_t* src = fgrid + (((int64_t)gz * a.gy + it_gy[i]) * a.gx + it_x[i]);
-#endif
-        if (C3H_MF_LOADX4 && rowin && it_xm[i] == 15u) {  // the item's 4 words in the grid: one load
+        if (rowin && it_xm[i] == 15u) {  // the item's 4 words in the grid: one load
           typedef uint32_t u4a4 __attribute__((ext_vector_type(4), aligned(4)));
           const u4a4 v = *reinterpret_cast<const u4a4*>(src);
           w[i][0] = v.x; w[i][1] = v.y; w[i][2] = v.z; w[i][3] = v.w;
@@ -855,22 +447,15 @@ __device__ __forceinline__ void c3hlac_mfma_body(const KArgs& a, int wid_, int n
     };
     // 12 channel planes of layer L: per voxel and colour one table read gives the 4 channel
     // bytes, a 4 x 4 byte transpose packs them per channel (4 voxels per dword)
-    // PBC: the plane stride as a compile-time constant (two-step tiles: 288 bytes, planes
-    // 4..11 16 bytes further), so the 12 plane stores take immediate offsets; 0 = runtime
-    auto store_layer_t = [&](int L, const uint32_t (&w)[LOAD][4], auto pbc) {
+    auto store_layer = [&](int L, const uint32_t (&w)[LOAD][4]) {
 #if C3H_MF_EXP & 2
       return;
 #endif
-      constexpr int PBC = decltype(pbc)::value;
-      const int PBv = PBC ? PBC : PB, gapv = PBC ? C3H_MF_GAP : gap;
-      const int SSv = PBC ? mf_slot_stride(PBC) : SS;
-      uint8_t* slot = wl + (L % kMfSlots) * SSv;
+      uint8_t* slot = wl + (L % kMfSlots) * SS;
 #pragma unroll
       for (int i = 0; i < LOAD; ++i) {
         if (it_dst[i] < 0) continue;
-        // empty voxels read entry 768 (all channels 0, i.e. 0x80 each)
         uint32_t t[3][4];
-#if C3H_MF_OCCMASK
         // every voxel reads its colour bytes' entries (an empty word reads entry 0); the empty
         // voxels' bytes are put back to 0x80 per plane dword by the occupancy mask (byte j =
         // 0xff when voxel j's word has its occupancy byte)
@@ -894,13 +479,6 @@ __device__ __forceinline__ void c3hlac_mfma_body(const KArgs& a, int wid_, int n
         uint32_t occ8 = occ << 8;
         __asm__("" : "+v"(occ8));  // x 255 as a shift and a subtract, not a v_mul_lo_u32
         const uint32_t om = occ8 - occ;
-#else
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int col = 0; col < 3; ++col)
-            t[col][j] = s_tab[w[i][j] ? col * 256 + ((w[i][j] >> (16 - 8 * col)) & 0xffu) : 768u];
-#endif
         uint8_t* dst = slot + it_dst[i];
 #pragma unroll
         for (int col = 0; col < 3; ++col) {
@@ -910,32 +488,21 @@ __device__ __forceinline__ void c3hlac_mfma_body(const KArgs& a, int wid_, int n
           const uint32_t u3 = __builtin_amdgcn_perm(t[col][3], t[col][2], 0x07030602u);
           uint32_t o[4] = {__builtin_amdgcn_perm(u2, u0, 0x05040100u), __builtin_amdgcn_perm(u2, u0, 0x07060302u),
                            __builtin_amdgcn_perm(u3, u1, 0x05040100u), __builtin_amdgcn_perm(u3, u1, 0x07060302u)};
-#if C3H_MF_OCCMASK
 #pragma unroll
           for (int s2 = 0; s2 < 4; ++s2) o[s2] = (o[s2] & om) | (0x80808080u & ~om);
-#endif
 #pragma unroll
-          for (int s2 = 0; s2 < 4; ++s2) *reinterpret_cast<uint32_t*>(dst + (4 * col + s2) * PBv + (col ? gapv : 0)) = o[s2];
+          for (int s2 = 0; s2 < 4; ++s2) *reinterpret_cast<uint32_t*>(dst + (4 * col + s2) * PB) = o[s2];
         }
       }
-    };
-    auto store_layer = [&](int L, const uint32_t (&w)[LOAD][4]) {
-      if (two && PB == 288) store_layer_t(L, w, std::integral_constant<int, 288>{});
-      else store_layer_t(L, w, std::integral_constant<int, 0>{});
     };
     mf_v4i acc[kMfK];
 #pragma unroll
     for (int k = 0; k < kMfK; ++k) acc[k] = mf_v4i{0, 0, 0, 0};
-    if (trp) {
+    if (rec) {
       // every record's padding dword {0, 0, 0, 1} and the padding records 144..151 of the
       // three slots (the previous tile's staging overwrote them; the conversion writes only
       // a record's 12 channel bytes)
       mf_compiler_fence();
-      if (C3H_MF_B96)
-        for (int r = lane; r < kMfSlots * kMfRecPos; r += 64) {
-          const int sl = r / kMfRecPos, p = r - sl * kMfRecPos;
-          *reinterpret_cast<uint32_t*>(wl + sl * SS + 16 * p + 12) = 0x01000000u;
-        }
       if (lane < 3 * (kMfRecPos - 144))
         *reinterpret_cast<mf_u4*>(wl + (lane >> 3) * SS + 16 * (144 + (lane & 7))) =
             mf_u4{0x80808080u, 0x80808080u, 0x80808080u, 0x01000000u};
@@ -976,18 +543,10 @@ __device__ __forceinline__ void c3hlac_mfma_body(const KArgs& a, int wid_, int n
         const uint64_t lbu = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(lb >> 32)) << 32) |
                              (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)lb);
         const int nrec = __builtin_amdgcn_readfirstlane(zin ? 0x7ffffff0 : 0);
-#if C3H_MF_BUFLD
         const __amdgpu_buffer_rsrc_t r =
             __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(lbu), (short)0, nrec, 0x00020000);
 #pragma unroll
         for (int i = 0; i < 3; ++i) w[i] = __builtin_amdgcn_raw_buffer_load_b32(r, 4 * ro[i], 0, 0);
-#else
-        (void)lbu;
-        (void)nrec;
-        const uint32_t* lp = tbase + L * zst;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) w[i] = zin && ro[i] >= 0 ? lp[ro[i]] : 0u;
-#endif
       };
       auto store_rec = [&](int L, const uint32_t (&w)[3]) {
         uint8_t* slot = wl + (L % kMfSlots) * SS;
@@ -1007,14 +566,10 @@ __device__ __forceinline__ void c3hlac_mfma_body(const KArgs& a, int wid_, int n
           const uint32_t t1 = *reinterpret_cast<const uint32_t*>(tb + 1024 + ag);
           const uint32_t t2 = *reinterpret_cast<const uint32_t*>(tb + 2048 + ab);
           const bool occ = (w[i] >> 24) != 0u;
-#if C3H_MF_B96
-          typedef uint32_t mf_u3 __attribute__((ext_vector_type(3)));
-          *reinterpret_cast<mf_u3*>(slot + 16 * e) =
-              mf_u3{occ ? t0 : 0x80808080u, occ ? t1 : 0x80808080u, occ ? t2 : 0x80808080u};
-#else
+          // (measured and removed: 12-byte record stores with the padding dword written once
+          // per tile -- 1.09 against 1.01 ms)
           *reinterpret_cast<mf_u4*>(slot + 16 * e) =
               mf_u4{occ ? t0 : 0x80808080u, occ ? t1 : 0x80808080u, occ ? t2 : 0x80808080u, 0x01000000u};
-#endif
         }
       };
       uint32_t wr[2][3];
@@ -1053,35 +608,21 @@ __device__ __forceinline__ void c3hlac_mfma_body(const KArgs& a, int wid_, int n
     const uint8_t* cpad = cplanes + (nk == 15 ? PBM : 0) + korg;
     const uint8_t* pmask = realk ? mask + korg : cplanes + 2 * PBM + korg;
     const int pw16 = PW & ~15;
-    mf_u4 mk2[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};  // two-step layers: the mask, once per tile
-    uint32_t mk10[10];  // C3H_MF_ASHIFT: the mask words of bytes 32 h - 4 .. 32 h + 36
-    if (nks == 2) {
-      mf_compiler_fence();  // the mask plane was written above by this wave
-      if (C3H_MF_ASHIFT) {
-#pragma unroll
-        for (int j = 0; j < 10; ++j) mk10[j] = *reinterpret_cast<const uint32_t*>(pmask + 32 * h4k + 4 * (j - 1));
-      } else {
-        mk2[0] = *reinterpret_cast<const mf_u4*>(__builtin_assume_aligned(pmask + 32 * h4k, 16));
-        mk2[1] = *reinterpret_cast<const mf_u4*>(__builtin_assume_aligned(pmask + 32 * h4k + 16, 16));
-      }
-    }
+    // (redundant with the loop's first fence, and kept from the removed two-step code: without
+    // it both instances are allocated differently -- 4 more scratch reloads at LOAD = 1, config 5
+    // measured about 1 % later, profiles/r12/retire_variants/)
+    if (nks == 2) mf_compiler_fence();
     for (int z = 0; z < lz; ++z) {
       mf_compiler_fence();  // same-wave LDS accesses complete in order; keep the compiler's too
-      const int pn = nk * PB + (nk >= 4 ? gap : 0) + korg;
+      const int pn = nk * PB + korg;
       const uint8_t* pp = realk ? wl + ((z % kMfSlots) * SS + pn) : cpad;        // dz = -1
       const uint8_t* pc = realk ? wl + (((z + 1) % kMfSlots) * SS + pn) : cpad;  // dz = 0
 #if !(C3H_MF_EXP & 1)
-      if (two) {  // S <= 10 tiles: pitch 12
-        if (C3H_MF_ASHIFT) mf_layer_ksteps2s<12>(pp, pc, mk10, pw16, h4k, acc);
-        else if (C3H_MF_U32) mf_layer_ksteps2u<12>(pp, pc, mk2, pw16, h4k, acc);
-        else mf_layer_ksteps2<12>(pp, pc, mk2, pw16, h4k, acc);
-      } else {
-        switch (PW & 15) {
-          case 0: mf_layer_ksteps<0>(pp, pc, pmask, pw16, nks, h4k, acc); break;
-          case 4: mf_layer_ksteps<4>(pp, pc, pmask, pw16, nks, h4k, acc); break;
-          case 8: mf_layer_ksteps<8>(pp, pc, pmask, pw16, nks, h4k, acc); break;
-          default: mf_layer_ksteps<12>(pp, pc, pmask, pw16, nks, h4k, acc); break;
-        }
+      switch (PW & 15) {
+        case 0: mf_layer_ksteps<0>(pp, pc, pmask, pw16, nks, h4k, acc); break;
+        case 4: mf_layer_ksteps<4>(pp, pc, pmask, pw16, nks, h4k, acc); break;
+        case 8: mf_layer_ksteps<8>(pp, pc, pmask, pw16, nks, h4k, acc); break;
+        default: mf_layer_ksteps<12>(pp, pc, pmask, pw16, nks, h4k, acc); break;
       }
 #endif
       mf_compiler_fence();
@@ -1128,7 +669,6 @@ __device__ __forceinline__ void c3hlac_mfma_body(const KArgs& a, int wid_, int n
       float* sf = reinterpret_cast<float*>(wl);
       mf_compiler_fence();
       const bool slot = real && h4 < 3;
-#if C3H_MF_ST16
       if (a.feat16) {  // fp16 rows: every value rounded once (RNE), as the float stage's gather did
         _Float16* sh = reinterpret_cast<_Float16*>(wl);
         auto put4 = [&](_Float16* dst, float x, float y, float z, float w) {
@@ -1175,7 +715,6 @@ __device__ __forceinline__ void c3hlac_mfma_body(const KArgs& a, int wid_, int n
         mf_compiler_fence();  // the next tile's layers overwrite the stage after these reads
         goto staged_done;
       }
-#endif
       {
       float* sl = sf + (h4 * 12 + n) * 4;
       uint32_t base[4];
@@ -1211,14 +750,9 @@ __device__ __forceinline__ void c3hlac_mfma_body(const KArgs& a, int wid_, int n
         uint32_t* out2 = reinterpret_cast<uint32_t*>(a.feat16 + h * a.f16s);
 #pragma unroll 2
         for (int i = lane; i < (a.f16s >> 1); i += 64) {  // the padding to f16s as zeros
-#if C3H_MF_SRC2
           const uint32_t sp = 2 * i + 1 < 982 ? reinterpret_cast<const uint32_t*>(s_src)[i] : 0u;
           const _Float16 lo = 2 * i < 981 ? (_Float16)sf[sp & 0xffffu] : (_Float16)0.0f;
           const _Float16 hi = 2 * i + 1 < 981 ? (_Float16)sf[sp >> 16] : (_Float16)0.0f;
-#else
-          const _Float16 lo = 2 * i < 981 ? (_Float16)sf[s_src[2 * i]] : (_Float16)0.0f;
-          const _Float16 hi = 2 * i + 1 < 981 ? (_Float16)sf[s_src[2 * i + 1]] : (_Float16)0.0f;
-#endif
           out2[i] = (uint32_t)__builtin_bit_cast(uint16_t, lo) | ((uint32_t)__builtin_bit_cast(uint16_t, hi) << 16);
         }
         if (wid == 0 && lane == 0) *a.feat16_flag = 1u;
@@ -1229,9 +763,7 @@ __device__ __forceinline__ void c3hlac_mfma_body(const KArgs& a, int wid_, int n
       }
       mf_compiler_fence();  // the next tile's planes overwrite sf after these reads
       }
-#if C3H_MF_ST16
     staged_done:;
-#endif
     } else if (a.atomic || F == 981) {
       float* out = ffeat + h * F;
       unsigned long long* hacc = a.atomic ? facc + h * 981 : nullptr;

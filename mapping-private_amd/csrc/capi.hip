@@ -361,11 +361,6 @@ int sync_host_lists(c3h_ctx* ctx) {
 // f * stride; d_out + f * M * rank).  clean: 0 = continue from the lists, 1 = cleanMax
 // first, 2 = reset the lists as setRank does (batched frames start fresh).
 // gate: -1 fill only for positions not already gated out (0: every gated-out position)
-#ifndef C3H_SPARSE_SCORES
-#define C3H_SPARSE_SCORES 1
-#endif
-constexpr int kSparseScores = C3H_SPARSE_SCORES;
-
 // The f32 feature rows of the last extract when it wrote them as f16 (fp16 search precision
 // on a large dense grid): converted on the device if the MFMA body set the flag.
 int feat_rows_f32(c3h_ctx* ctx) {
@@ -501,7 +496,7 @@ int search_frames(c3h_ctx* ctx, int nf, const int32_t range[3], int32_t thr, int
     q.Opad = ctx->Opad;
     q.mpg = std::max(1, 64 / ctx->r);
     q.scores = ctx->scores.p;
-    q.sparse_scores = same_layout ? kSparseScores : 0;
+    q.sparse_scores = same_layout ? 1 : 0;
     q.nmodes = rm.n;
     q.score_mfma = mf ? 1 : 0;
     q.skip_empty = ctx->exist_gates_rows ? 1 : 0;
@@ -739,12 +734,6 @@ void c3h_destroy(c3h_ctx* ctx) {
     (void)hipStreamDestroy(ctx->pb_vstream);
   }
   if (ctx->pb_vox_ev) (void)hipEventDestroy(ctx->pb_vox_ev);
-  if (ctx->vcopy) {
-    (void)hipStreamSynchronize(ctx->vcopy);
-    (void)hipStreamDestroy(ctx->vcopy);
-  }
-  if (ctx->vcopy_start) (void)hipEventDestroy(ctx->vcopy_start);
-  for (hipEvent_t e : ctx->vcopy_ev) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->pb_tick_ev)
     if (e) (void)hipEventDestroy(e);
   release(ctx->grid);
@@ -858,16 +847,6 @@ int c3h_synchronize(c3h_ctx* ctx) {
 
 const char* c3h_last_error(const c3h_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
-// c3h_voxelize of host frames: chunked copy + accumulate overlap (0: one copy, then the pass)
-#ifndef C3H_VOX_CHUNKED_COPY
-#define C3H_VOX_CHUNKED_COPY 0  // measured round 6: the pageable chunk copies leave ~25 us gaps (0.45 -> 0.53 ms)
-#endif
-constexpr bool kVoxChunkedCopy = C3H_VOX_CHUNKED_COPY;
-#ifndef C3H_VOX_COPY_CHUNK_BLOCKS
-#define C3H_VOX_COPY_CHUNK_BLOCKS 64  // accumulate blocks (of 4,096 points) per copied chunk
-#endif
-constexpr int kVoxCopyChunkBlocks = C3H_VOX_COPY_CHUNK_BLOCKS;
-
 int c3h_voxelize(c3h_ctx* ctx, const float* xyzrgb, int64_t n, int on_device, float leaf,
                  float z_limit, c3h_grid_info* info) {
   if (!ctx) return C3H_ERR_ARG;
@@ -889,18 +868,16 @@ int c3h_voxelize(c3h_ctx* ctx, const float* xyzrgb, int64_t n, int on_device, fl
   gi.leaf = leaf;
   gi.inv_leaf = 1.0f / leaf;
   const float4* d_pts = nullptr;
-  // host frames of >= 2 chunks go over PCIe in chunks on a copy stream, and each chunk's
-  // accumulate blocks start as soon as it lands: the accumulate pass hides under the copy
-  // (a 1M-point frame: 4 chunks of 64 accumulate blocks)
-  const int64_t chunk_pts = (int64_t)kVoxCopyChunkBlocks * c3h::vox_positions(1);
-  const bool chunked = kVoxChunkedCopy && n > 0 && !on_device && n >= 2 * chunk_pts;
+  // A host frame goes over in one copy, then the pass.  Measured and removed (round 6,
+  // profiles/r6/single_frame/): the copy in chunks on a second stream with each chunk's
+  // accumulate blocks started as it lands -- the pageable chunk copies left ~25 us gaps
+  // (0.45 -> 0.53 ms)
   if (n > 0) {
     if (on_device) {
       d_pts = reinterpret_cast<const float4*>(xyzrgb);
     } else {
       ENSURE(ctx->pts, (size_t)n * 4);
-      if (!chunked)
-        HIPCHK(hipMemcpyAsync(ctx->pts.p, xyzrgb, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
+      HIPCHK(hipMemcpyAsync(ctx->pts.p, xyzrgb, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
       d_pts = reinterpret_cast<const float4*>(ctx->pts.p);
     }
   }
@@ -975,43 +952,16 @@ int c3h_voxelize(c3h_ctx* ctx, const float* xyzrgb, int64_t n, int on_device, fl
     a.par = ctx->vpar;
     a.clear_grid = clear_grid ? 1 : 0;
     acc_guard.armed = true;
-    if (chunked && attempt == 0) {
-      const int nch = (int)((n + chunk_pts - 1) / chunk_pts);
-      if (!ctx->vcopy) HIPCHK(hipStreamCreateWithFlags(&ctx->vcopy, hipStreamNonBlocking));
-      if (!ctx->vcopy_start) HIPCHK(hipEventCreateWithFlags(&ctx->vcopy_start, hipEventDisableTiming));
-      while ((int)ctx->vcopy_ev.size() < nch) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        ctx->vcopy_ev.push_back(e);
-      }
-      // the copies overwrite ctx->pts: after everything queued that may read it
-      HIPCHK(hipEventRecord(ctx->vcopy_start, ctx->stream));
-      HIPCHK(hipStreamWaitEvent(ctx->vcopy, ctx->vcopy_start, 0));
+    int rc = prof_prepare(ctx, std::max(a.nblk, 1), &a.prof);  // diagnostics builds (C3H_PROF)
+    if (rc != C3H_OK) return rc;
+    {
       Timed t(ctx, 0);
-      for (int k = 0; k < nch; ++k) {
-        const int64_t off = k * chunk_pts, cnt = std::min<int64_t>(chunk_pts, n - off);
-        HIPCHK(hipMemcpyAsync(ctx->pts.p + 4 * off, xyzrgb + 4 * off, (size_t)cnt * 16, hipMemcpyHostToDevice,
-                              ctx->vcopy));
-        HIPCHK(hipEventRecord(ctx->vcopy_ev[k], ctx->vcopy));
-        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->vcopy_ev[k], 0));
-        c3h::VoxArgs ak = a;
-        ak.blk0 = (int)(off / c3h::vox_positions(1));
-        ak.clear_grid = k == 0 ? a.clear_grid : 0;
-        HIPCHK(c3h::launch_vox_accum(ak, (int)c3h::vox_blocks(cnt), ctx->stream));
-      }
-      HIPCHK(c3h::launch_vox_scatter(a, ctx->stream));
-    } else {
-      int rc = prof_prepare(ctx, std::max(a.nblk, 1), &a.prof);  // diagnostics builds (C3H_PROF)
+      HIPCHK(c3h::launch_voxelize(a, ctx->stream));
+    }
+    if (a.prof) {
+      rc = prof_dump(ctx, "vox_accum_kernel", std::max(a.nblk, 1));
       if (rc != C3H_OK) return rc;
-      {
-        Timed t(ctx, 0);
-        HIPCHK(c3h::launch_voxelize(a, ctx->stream));
-      }
-      if (a.prof) {
-        rc = prof_dump(ctx, "vox_accum_kernel", std::max(a.nblk, 1));
-        if (rc != C3H_OK) return rc;
-        a.prof = nullptr;
-      }
+      a.prof = nullptr;
     }
     HIPCHK(hipMemcpyAsync(hc, ctx->vcnt.p, c3h::kVcWords * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1336,17 +1286,9 @@ int c3h_set_grid(c3h_ctx* ctx, const uint32_t* words, const int32_t div_b[3],
 // C3HLAC{981,117}Estimation::setVoxelFilter + compute for nf frames of one geometry
 // (grids[f], dims / min_b / leaf of ctx->info) in one set of launches; frame f's
 // per-frame buffers (features, exist, tile stamps, work / row lists) sit at f * stride.
-// large stand-alone extracts: the sampled density probe may skip the occupancy stream
-#ifndef C3H_DENSE_PROBE
-#define C3H_DENSE_PROBE 1
-#endif
-constexpr bool kDenseProbe = C3H_DENSE_PROBE;
-// the extract after a c3h_voxelize stamps its tiles from the voxeliser's list (round 6;
-// 0: stream the grid, as round 5)
-#ifndef C3H_VOX_LIST_STAMP
-#define C3H_VOX_LIST_STAMP 1
-#endif
-constexpr bool kVoxListStamp = C3H_VOX_LIST_STAMP;
+// Large stand-alone extracts: the sampled density probe may skip the occupancy stream.
+// The extract after a c3h_voxelize stamps its tiles from the voxeliser's list (round 6);
+// any other extract streams the grid.
 
 static bool extract_params_ok(const c3h_extract_params* p) {
   return (p->variant == 981 || p->variant == 117) && p->color_mode >= C3H_COLOR_C3_FLOAT &&
@@ -1567,7 +1509,7 @@ int extract_frames(c3h_ctx* ctx, const uint32_t* const* grids, int nf, const c3h
     // the grid of the last c3h_voxelize: its occupied voxels are listed (vox_scatter / the
     // sorted path), so the tiles are stamped from the list instead of the 4 B/voxel stream
     // (sparse frames: 16 B of list work per occupied voxel below the grid's 4 B per voxel)
-    const bool from_list = kVoxListStamp && !ctx->capture && nf == 1 && ctx->table_valid &&
+    const bool from_list = !ctx->capture && nf == 1 && ctx->table_valid &&
                            ctx->grid_ptr == ctx->grid.p && ctx->vargs.lists &&
                            (int64_t)ctx->vns * 16 < (int64_t)div[0] * div[1] * div[2];
     if (from_list) {
@@ -1578,7 +1520,7 @@ int extract_frames(c3h_ctx* ctx, const uint32_t* const* grids, int nf, const c3h
       l.vl_seg = (int)c3h::vox_positions(1);
       l.vl_nseg = va.nblk;
     }
-    if (!from_list && !ctx->capture && nf == 1 && ntiles >= 65536 && l.zero_empty && !atomic && kDenseProbe) {
+    if (!from_list && !ctx->capture && nf == 1 && ntiles >= 65536 && l.zero_empty && !atomic) {
       ENSURE(ctx->dense_flag, 1);
       l.dense = ctx->dense_flag.p;
     }
@@ -2619,20 +2561,9 @@ int point_frame_single(c3h_ctx* ctx, const float* pts, int64_t n, int on_device,
 
 extern "C" {
 
-// points-in batches: the scatter stamps the tick's tiles (0: the tick streams the canvases)
-#ifndef C3H_POINT_STAMP
-#define C3H_POINT_STAMP 1
-#endif
-constexpr bool kPointStamp = C3H_POINT_STAMP;
-#ifndef C3H_POINT_VOX_PRIO
-#define C3H_POINT_VOX_PRIO 1
-#endif
-// points-in batches: flagged voxels summed exactly and off-cell voxels fixed up in the batch
-// (0: frames with flagged voxels take the single-frame path, as in round 3)
-#ifndef C3H_POINT_EXACT
-#define C3H_POINT_EXACT 1
-#endif
-constexpr bool kPointExact = C3H_POINT_EXACT;
+// Points-in batches: the scatter stamps the tick's tiles (a canvas that does not match the
+// grid: the tick streams the canvases), and flagged voxels are summed exactly and off-cell
+// voxels fixed up in the batch.
 
 int c3h_run_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t nframes, int on_device,
                          float leaf, float z_limit, const int32_t canvas[3], const c3h_extract_params* p,
@@ -2724,9 +2655,9 @@ int c3h_run_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n
     if (!ctx->pb_vstream) {
       // the voxeliser's stream is the points-in call's critical path (its accumulate runs
       // beside the tick of the batches before, which has slack): high priority, so its
-      // workgroups are dispatched first as CUs free up (C3H_POINT_VOX_PRIO 0: default)
+      // workgroups are dispatched first as CUs free up
       int lo = 0, hi = 0;
-      if (C3H_POINT_VOX_PRIO && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo)
+      if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo)
         HIPCHK(hipStreamCreateWithPriority(&ctx->pb_vstream, hipStreamNonBlocking, hi));
       else
         HIPCHK(hipStreamCreateWithFlags(&ctx->pb_vstream, hipStreamNonBlocking));
@@ -2861,7 +2792,7 @@ int c3h_run_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n
       if (rc == 0) rc = fail(ctx, C3H_ERR_STATE, "c3h_run_point_frames: the canvas does not fit the pipeline");
       if (rc < 0) break;
       const c3h::C3Launch& cl = fresh.l;
-      va.stamp = (kPointStamp && cl.gx == canvas[0] && cl.gy == canvas[1] && cl.gz == canvas[2] &&
+      va.stamp = (cl.gx == canvas[0] && cl.gy == canvas[1] && cl.gz == canvas[2] &&
                   cl.ntiles <= ((int64_t)1 << 18)) ? 1 : 0;
       va.axmap = cl.axmap;
       va.ns0 = cl.nseg[0];
@@ -2874,7 +2805,7 @@ int c3h_run_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n
       va.s_work = cl.s_work;
       // the exact pass + off-cell fixup: the tick's direct mode (a row list, one tile per
       // subdivision) on the canvas itself; otherwise flagged frames take the single-frame path
-      const bool exact = kPointExact && cl.rows && cl.axmap && cl.gx == canvas[0] && cl.gy == canvas[1] &&
+      const bool exact = cl.rows && cl.axmap && cl.gx == canvas[0] && cl.gy == canvas[1] &&
                          cl.gz == canvas[2] && c3h::point_fixup_fits(cl.lmax);
       if (exact) {
         va.flags = c->pb_flags.p;

@@ -137,23 +137,13 @@ C3H_SCHED_HD uint32_t occ_seg_fold32(uint32_t b) {
 C3H_SCHED_HD uint16_t occ_seg_fold(uint64_t ballot) {
   return (uint16_t)(occ_seg_fold32((uint32_t)ballot) | (occ_seg_fold32((uint32_t)(ballot >> 32)) << 8));
 }
-// What the stream stores per span.  C3H_SEG_RAW 0 (shipped): the folded 16 bits (128 KB per
-// 256^3 frame; the stream folds, ~25 VALU per chunk in its row loop).  1 (measured, slower):
-// the ballot as it is (8 bytes, 512 KB per frame; segment s is nibble s, the reader folds):
-// without the fold the stream alone still ends 55-65 us later than with it, the whole tick
-// 4 % later.
-#ifndef C3H_SEG_RAW
-#define C3H_SEG_RAW 0
-#endif
-#if C3H_SEG_RAW
-typedef uint64_t occ_seg_t;
-C3H_SCHED_HD occ_seg_t occ_seg_make(uint64_t ballot) { return ballot; }
-C3H_SCHED_HD bool occ_seg_test(occ_seg_t e, int64_t voxel) { return ((e >> (4 * occ_seg_bit(voxel))) & 15u) != 0; }
-#else
+// What the stream stores per span: the folded 16 bits (128 KB per 256^3 frame; the stream
+// folds, ~25 VALU per chunk in its row loop).  Measured and removed: the ballot stored as it
+// is (8 bytes, 512 KB per frame, the reader folds) -- without the fold the stream alone still
+// ended 55-65 us later than with it, the whole tick 4 % later.
 typedef uint16_t occ_seg_t;
 C3H_SCHED_HD occ_seg_t occ_seg_make(uint64_t ballot) { return occ_seg_fold(ballot); }
 C3H_SCHED_HD bool occ_seg_test(occ_seg_t e, int64_t voxel) { return ((e >> occ_seg_bit(voxel)) & 1u) != 0; }
-#endif
 
 // host: the last 1/div of every frame's chunks go to the pool in units of `unit` chunks
 struct OccSteal {

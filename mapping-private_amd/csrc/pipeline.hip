@@ -211,7 +211,7 @@ int env_int(const char* name, int dflt) {
 // tick later: both sides decide from the batch's own launch, so they always agree.  It needs
 // the row-wave stream (whose loads are whole spans) and the per-wave 117 tile body.
 bool tick_segmap_ok(const C3Launch& l, const C3Args& c) {
-  return l.segmap && !C3H_OCC_RING && c.bits && occ_rowwave(l.gx, c.ax) && c.ka.wave117 &&
+  return l.segmap && c.bits && occ_rowwave(l.gx, c.ax) && c.ka.wave117 &&
          w117_map_fits(l.lmax[0], l.lmax[1], l.lmax[2]);
 }
 
@@ -247,9 +247,6 @@ hipError_t launch_tick(const TickParts& p, hipStream_t s) {
     // one workgroup per list chunk running every model group over one box-sum pass (the
     // gathers were repeated per group): the projections then alias the basis window, which
     // must hold them
-#ifndef C3H_TICK_GROUP_LOOP
-#define C3H_TICK_GROUP_LOOP 1
-#endif
     // the projection on the matrix cores (round 8, score_tick_mfma_body): one workgroup per
     // list chunk covers every model, no basis window and no group loop.  Taken when there is
     // more than one model group (a single group has no window to re-stage); c3h_set_score_engine
@@ -261,7 +258,7 @@ hipError_t launch_tick(const TickParts& p, hipStream_t s) {
         (t.s_groups > 1 || a.score_engine == 2)) {
       t.s_mpp = score_tick_mpp(a.D, a.M, a.r, a.mpg);
       t.s_groups = 1;
-    } else if (C3H_TICK_GROUP_LOOP && t.s_groups > 1 && a.D * kOC >= kFP * (kOC + 1)) {
+    } else if (t.s_groups > 1 && a.D * kOC >= kFP * (kOC + 1)) {
       t.sq.group_loop = 1;
       t.s_groups = 1;
     }

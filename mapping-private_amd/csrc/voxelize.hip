@@ -69,9 +69,6 @@ constexpr int kVoxPer = kVoxChunk / kVB;
 #ifndef C3H_VOX_SLOTS
 #define C3H_VOX_SLOTS 2048
 #endif
-#ifndef C3H_VOX_MERGE
-#define C3H_VOX_MERGE 1  // the run merge (0: every point updates the LDS table itself)
-#endif
 // the owner's read and clear of a voxel's sums (one 16-B load and store; the adds are a
 // previous launch's)
 __device__ __forceinline__ ulonglong2 take_acc(ulonglong2* p) {
@@ -271,7 +268,7 @@ __global__ __launch_bounds__(kVB) void vox_accum_kernel(VoxArgs a) {
     // reads 0 and would join a run of key 0 (round 5 bug: cell 0's voxel took its
     // neighbour lane's point)
     const uint32_t tp = vrow_shr<1>(t);
-    const bool head = !C3H_VOX_MERGE || !valid || (lane & 15) == 0 || tp != t;
+    const bool head = !valid || (lane & 15) == 0 || tp != t;
     const uint64_t hm = __ballot(head);
     const int o0 = lane - (63 - __clzll(hm & le));  // lanes before this one in its run
     uint32_t s0, s1, sm;
@@ -918,9 +915,6 @@ static_assert(kBChunk % kBT == 0 && (kBSlots & (kBSlots - 1)) == 0, "batch voxel
 #ifndef C3H_VB_ATOM_SCOPE
 #define C3H_VB_ATOM_SCOPE __HIP_MEMORY_SCOPE_AGENT  // diagnostics: workgroup scope times L2-local atomics
 #endif
-#ifndef C3H_VB_MERGE
-#define C3H_VB_MERGE 1  // the run merge (0: every point inserts into the LDS hash itself)
-#endif
 
 __device__ __forceinline__ int vb_frame(const int* blk0, int nf, int b) {
   int lo = 0, hi = nf;  // blk0[lo] <= b < blk0[hi]
@@ -1019,7 +1013,7 @@ __global__ __launch_bounds__(kBT) void voxb_accum_kernel(VoxBatchArgs a) {
     // runs of equal keys inside each 16-lane row: a lane starts a run when it is invalid,
     // the row's first lane, or its key differs from the previous lane's
     const uint32_t tp = vrow_shr<1>(t);
-    const bool head = !C3H_VB_MERGE || !valid || (lane & 15) == 0 || tp != t;
+    const bool head = !valid || (lane & 15) == 0 || tp != t;
     const uint64_t hm = __ballot(head);
     const int hpos = 63 - __clzll(hm & le);  // this lane's run start
     const int o0 = lane - hpos;              // lanes before this one in its run
@@ -1188,9 +1182,6 @@ __global__ __launch_bounds__(kBlock) void voxb_reduce_kernel(VoxBatchArgs a) {
     for (int k = 0; k < 4; ++k) a.xcnt[4 * f + k] = 0u;
 }
 
-#ifndef C3H_VB_STAMP_DEDUP
-#define C3H_VB_STAMP_DEDUP 1  // the scatter's tile stamps deduplicated per workgroup in LDS
-#endif
 __global__ __launch_bounds__(kBlock) void voxb_scatter_kernel(VoxBatchArgs a) {
   const int b = blockIdx.x, tid = threadIdx.x;
   const int f = vb_frame(a.blk0, a.nf, b);
@@ -1263,11 +1254,9 @@ __global__ __launch_bounds__(kBlock) void voxb_scatter_kernel(VoxBatchArgs a) {
       // neighbouring entries were first touched by neighbouring points: mostly one tile
       const int tp = __shfl_up(tile, 1, 64);
       bool cand = tile >= 0 && !(lane > 0 && tp == tile);
-      if (C3H_VB_STAMP_DEDUP && cand) {
+      if (cand) {  // the tile stamps deduplicated per workgroup in LDS
         const uint32_t bit = 1u << (tile & 31);
         cand = (atomicOr(&vb_stamped[tile >> 5], bit) & bit) == 0u;
-      } else if (cand) {  // (diagnostics: a plain read of the stamp instead)
-        cand = flags[tile] != a.epoch;
       }
       const bool fresh = cand && atomicExch(&flags[tile], a.epoch) != a.epoch;
       const unsigned long long bm = __ballot(fresh);
@@ -1517,12 +1506,6 @@ hipError_t launch_voxelize(const VoxArgs& a, hipStream_t s) {
   // at least one accum block: it also clears the previous frame and resets the totals
   vox_accum_kernel<<<(unsigned)std::max(a.nblk, 1), kVB, 0, s>>>(a);
   if (a.nblk > 0) vox_scatter_kernel<<<(unsigned)a.nblk, kBlock, 0, s>>>(a);
-  return hipGetLastError();
-}
-
-
-hipError_t launch_vox_accum(const VoxArgs& a, int nblocks, hipStream_t s) {
-  if (nblocks > 0) vox_accum_kernel<<<(unsigned)nblocks, kVB, 0, s>>>(a);
   return hipGetLastError();
 }
 
