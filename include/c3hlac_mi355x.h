@@ -267,8 +267,11 @@ int c3h_set_search_precision(c3h_ctx* ctx, int32_t fp16);
  * 2 = matrix cores (score_mfma_kernel, v_mfma_f32_32x32x2_f32; D <= 160).
  * Pipelined searches (c3h_run_frames / c3h_stream_frames with c3h_set_pipeline): 0 = the
  * matrix cores when the models span more than one 64-column group (M * r > 64), the VALU
- * score role otherwise; 1 = VALU; 2 = matrix cores whatever the group count.  Batches on
- * the lanes path always use the VALU kernel.
+ * score role otherwise; 1 = VALU; 2 = matrix cores whatever the group count.  Models with
+ * r > 64 (up to 256 columns per model) are pipelined on the matrix cores at 0 and 2, their
+ * score role a launch of its own behind the tick; at 1 there is no batched role for them and
+ * the frames take the lanes one at a time.  Batches on the lanes path always use the VALU
+ * kernel.
  * Both engines form every product as the same k-ordered fp32 fma chain, so the scores are
  * bit-identical. */
 int c3h_set_score_engine(c3h_ctx* ctx, int32_t engine);
@@ -300,7 +303,11 @@ int c3h_search_async(c3h_ctx* ctx, const int32_t range[3], int32_t exist_thresho
  * Ranks 1 .. 64 (c3h_set_rank) run through the software pipeline (c3h_set_pipeline); above
  * rank 1 one replay launch per batch follows the batch's scoring and updates every frame's
  * lists (searchPart's order-dependent update with checkOverlap, exact).  Ranks above 64
- * take the lanes with one replay launch per frame.  One host call, no host synchronisation. */
+ * take the lanes with one replay launch per frame.  Models with r > 64 are pipelined too
+ * (c3h_set_score_engine 0 or 2; records and scores byte-identical to c3h_search at engine
+ * 2); where the pipeline declines such a batch the lanes run it one frame per launch.  With
+ * c3h_set_remove_overlap each frame's records pass through removeOverlap before the frame
+ * is complete.  One host call, no host synchronisation. */
 int c3h_run_frames(c3h_ctx* ctx, const uint32_t* const* d_grids, int32_t nframes,
                    const int32_t div_b[3], const int32_t min_b[3], float leaf,
                    const c3h_extract_params* p, const int32_t range[3], int32_t exist_threshold,
@@ -318,9 +325,11 @@ int c3h_set_lanes(c3h_ctx* ctx, int32_t lanes);
  * d_out must stay valid until then.  A call with a different geometry / parameter set,
  * and every other entry point that touches this context's buffers, drains the open
  * stream first.  Ranks 1 .. 64 stream (above rank 1 a batch's lists are written by the
- * replay launch behind its scoring tick: the same completion rule).  Configurations the
- * pipeline does not cover (rank > 64, a search off the fast path, split subdivisions)
- * complete synchronously as in c3h_run_frames.  Returns the number of searched modes. */
+ * replay launch behind its scoring tick: the same completion rule, which also holds for the
+ * score launch of models with r > 64 and for c3h_set_remove_overlap's launch).
+ * Configurations the pipeline does not cover (rank > 64, a search off the fast path -- r > 64
+ * with c3h_set_score_engine(1), D > 160 --, split subdivisions) complete synchronously as in
+ * c3h_run_frames.  Returns the number of searched modes. */
 int c3h_stream_frames(c3h_ctx* ctx, const uint32_t* const* d_grids, int32_t nframes,
                       const int32_t div_b[3], const int32_t min_b[3], float leaf,
                       const c3h_extract_params* p, const int32_t range[3], int32_t exist_threshold,
@@ -350,8 +359,10 @@ int c3h_stream_flush(c3h_ctx* ctx);
  * NULL): the frame's VoxelGrid geometry, getSubdivNum, point and voxel counts and status
  * (0 batched, 1 single-frame path, < 0 the C3H_ERR_* that frame failed with; its lists are
  * the fresh setRank state).  One host synchronisation per call (the frames' records).
- * Ranks 1 .. 64 on the fast search path (else every frame takes the single-frame path).
- * Returns the number of searched modes or an error. */
+ * Ranks 1 .. 64 on the fast search path, models with r > 64 included at
+ * c3h_set_score_engine 0 or 2 (else every frame takes the single-frame path).  With
+ * c3h_set_remove_overlap the records of every frame, batched or not, pass through
+ * removeOverlap.  Returns the number of searched modes or an error. */
 typedef struct {
   int32_t div_b[3], min_b[3], subdiv_b[3];
   int32_t status;
@@ -370,8 +381,24 @@ int c3h_set_batch(c3h_ctx* ctx, int32_t frames);
  * fused launch per tick running occupancy (batch t) | tile (t-1) | compress+gate (t-2) |
  * score + rank-1 argmax (t-3), at ranks 2 .. 64 followed by one replay launch for the batch
  * scored in that tick; applies to ranks 1 .. 64 on the fast search path without split
- * subdivisions, other configurations use the lanes.  0 = lanes only. */
+ * subdivisions, other configurations use the lanes.  For models with r > 64 the tick of the
+ * batch's score slot carries no score role: their projection (the matrix cores, passes of
+ * whole 32-column tiles) is a launch of its own behind that tick, ahead of the replay.
+ * 0 = lanes only. */
 int c3h_set_pipeline(c3h_ctx* ctx, int32_t enable);
+/* SearchObjMulti::removeOverlap (search.cpp:972-992) on the batch entry points (default 0:
+ * d_out holds the lists as searched).  1: c3h_run_frames, c3h_stream_frames and
+ * c3h_run_point_frames pass each frame's M x rank records in d_out through removeOverlap on
+ * the device before the frame counts as complete -- the end of every frame of
+ * detect_object_vosch_multi.cpp -- on every route the call takes (pipeline, lanes, the
+ * single-frame path of points-in): one launch per batch behind the batch's replay, one wave
+ * per frame, the same result as c3h_remove_overlap on the downloaded records, byte for byte.
+ * The completion rule of c3h_stream_frames is unchanged.  Rank 1 launches nothing (the
+ * reference's shift loops are empty there); ranks 2 .. 64; with the setting on and a rank
+ * above 64 the three entry points return C3H_ERR_ARG.  Only d_out is rewritten: the
+ * context's own lists (c3h_get_lists, a following c3h_search) stay as searched.  Changing
+ * the setting drains an open stream at the next push. */
+int c3h_set_remove_overlap(c3h_ctx* ctx, int32_t enable);
 /* compressed features (setData before the summed-volume table): hist_num x D floats */
 int c3h_get_compressed(c3h_ctx* ctx, float* out, int on_device);
 /* per-position similarity of the last search, modes x M x P doubles (-1 = gated out).

@@ -228,6 +228,11 @@ class Context:
         the pipelined tick's score role; the scores are bit-identical)."""
         self._chk(self.lib.c3h_set_score_engine(self.h, int(engine)), "set_score_engine")
 
+    def set_remove_overlap(self, enable):
+        """c3h_set_remove_overlap: run_frames, stream_frames and run_point_frames pass each
+        frame's records through SearchObjMulti::removeOverlap on the device (ranks up to 64)."""
+        self._chk(self.lib.c3h_set_remove_overlap(self.h, int(bool(enable))), "set_remove_overlap")
+
     def set_search_precision(self, fp16):
         """c3h_set_search_precision: fp16 matrix-core compress for large grids."""
         self._chk(self.lib.c3h_set_search_precision(self.h, int(bool(fp16))), "set_search_precision")
@@ -302,7 +307,9 @@ class Context:
         """c3h_run_frames (stream=True: c3h_stream_frames, the pipeline stays filled;
         call stream_flush() before reading the last batches): grid_ptrs = uint64 numpy
         array of device pointers.  Ranks 1..64 (set_rank) go through the pipelined tick,
-        above rank 1 with one rank-replay launch per batch; ranks above 64 take the lanes."""
+        above rank 1 with one rank-replay launch per batch; ranks above 64 take the lanes.
+        Models with r > 64 are pipelined too (score engine 0 or 2); set_remove_overlap(True)
+        passes every frame's records through removeOverlap on the device."""
         gp = np.ascontiguousarray(grid_ptrs, dtype=np.uint64)
         fn = self.lib.c3h_stream_frames if stream else self.lib.c3h_run_frames
         p = _capi.ExtractParams()

@@ -454,6 +454,9 @@ struct SparseSearch {
   int score_engine = 0;
 };
 bool score_mfma_ok(int D);  // D fits score_mfma_kernel
+// models with r > 64 that the pipeline scores (score_wide_frames_kernel behind the tick;
+// captured batches only: outside the pipeline such models have no multi-frame search)
+bool score_tick_wide_ok(int D, int M, int r);
 // sparse compress fused into the gate launch (nullable in launch_sparse_search)
 struct SparseCompress {
   const float* feat;
@@ -505,6 +508,15 @@ struct ReplayFrames {
 };
 bool replay_frames_ok(const ReplayModes& modes, int rank);  // ranks 1 .. 64, 32-bit positions
 hipError_t launch_replay_frames(const ReplayFrames& a, hipStream_t s);
+// removeOverlap on the records of every frame of a batch in one launch
+// (remove_overlap_frames_kernel): frame f's M x rank records at outs[f] (nullable), ranks up
+// to 64; rank 1 launches nothing
+struct RemoveOverlapFrames {
+  int M, nf, rank;
+  int r1, r2, r3;
+  c3h_det* outs[kMaxBatch];
+};
+hipError_t launch_remove_overlap_frames(const RemoveOverlapFrames& a, hipStream_t s);
 
 hipError_t launch_clean_lists(c3h_det* lists, int n, hipStream_t s);
 
@@ -515,7 +527,7 @@ struct TickParts {
   bool tile_mapped = false;             //   its occupancy role ran in the previous tick (segment map written)
   const SparseSearch* gate = nullptr;   // batch t-2: exist gate ...
   const SparseCompress* comp = nullptr; //   ... + sparse compress
-  const SparseSearch* score = nullptr;  // batch t-3: list scoring + rank-1 argmax
+  const SparseSearch* score = nullptr;  // batch t-3: list scoring + rank-1 argmax (r > 64: a launch behind the tick)
   DevBuf<long long>* prof = nullptr;    // diagnostics builds: the context's timestamp buffer
 };
 bool tick_ok(const C3Launch& l);  // the C3 launch fits the tick's roles
@@ -646,6 +658,7 @@ struct c3h_ctx {
   bool feat16_pending = false;      // the last extract may have written f16 rows only
   int feat16_s = 0;                 // their row stride (halves)
   int score_engine = 0;             // c3h_set_score_engine: 0 auto, 1 VALU, 2 matrix cores
+  int remove_overlap = 0;           // c3h_set_remove_overlap: the batch entry points' d_out records
   c3h::DevBuf<_Float16> qt16;       // f16 basis for the fp16 matrix-core projection
   int Kq16 = 0;
   c3h::DevBuf<float> axis_q;        // M x r x D
@@ -705,12 +718,14 @@ struct c3h_ctx {
     c3h::PointFixup fx{};
     bool replay = false;          // rank > 1: the batched replay runs after its score role
     c3h::ReplayFrames rp{};
+    bool overlap = false;         // c3h_set_remove_overlap: removeOverlap on d_out follows the replay
+    c3h::RemoveOverlapFrames ro{};
   };
   struct PipeKey {
     int32_t div_b[3], min_b[3];
     float leaf;
     c3h_extract_params p;
-    int32_t range[3], thr, rotate, batch, rank;
+    int32_t range[3], thr, rotate, batch, rank, remove_overlap;
     uint64_t setup_version;
   };
   // points-in batches (c3h_run_point_frames).  Per buffer set: the canvas grids of its frame

@@ -390,7 +390,11 @@ int search_frames(c3h_ctx* ctx, int nf, const int32_t range[3], int32_t thr, int
   const bool mf = nf == 1 && !ctx->capture && c3h::score_mfma_ok(ctx->D) &&
                   (ctx->score_engine == 2 ||
                    (ctx->score_engine == 0 && (!valu_fast || H >= c3h::kBoxsumRows)));
-  const bool fast = valu_fast || mf;  // the sparse (gate list) search
+  // a captured batch of wide models (r > 64): the matrix-core launch behind the tick of its
+  // score slot projects it (a buffer set's engine is the one of the context the caller set it on)
+  const bool wide = ctx->capture && (ctx->parent ? ctx->parent : ctx)->score_engine != 1 &&
+                    c3h::score_tick_wide_ok(ctx->D, ctx->M, ctx->r);
+  const bool fast = valu_fast || mf || wide;  // the sparse (gate list) search
   if (nf > 1 && !fast) return fail(ctx, C3H_ERR_STATE, "search: batched frames need the fast path");
   int modes[6];
   const int nm = mode_schedule(range[0], range[1], range[2], rotate, modes);
@@ -1938,6 +1942,14 @@ int c3h_set_score_engine(c3h_ctx* ctx, int32_t engine) {
   return C3H_OK;
 }
 
+// (no drain here: the setting is part of the stream's key, so the next push drains an open
+// stream, and the batches in flight keep the setting they were pushed with)
+int c3h_set_remove_overlap(c3h_ctx* ctx, int32_t enable) {
+  if (!ctx) return C3H_ERR_ARG;
+  ctx->remove_overlap = enable ? 1 : 0;
+  return C3H_OK;
+}
+
 // the bases on the device (D a multiple of 4 when D <= 160; see c3h_search_setup)
 static int search_setup_dev(c3h_ctx* ctx, const float* axis_p, const float* var, int32_t D, int32_t F,
                             const float* axis_q, int32_t M, int32_t r, const float* feature_max,
@@ -2182,6 +2194,29 @@ int ensure_lanes(c3h_ctx* ctx, int n) {
   return C3H_OK;
 }
 
+// c3h_set_remove_overlap: the launch that passes the records of nb searched frames (outs)
+// through removeOverlap; it goes behind those searches on their stream
+c3h::RemoveOverlapFrames overlap_args(const c3h_ctx* ctx, const int32_t range[3], c3h_det* const* outs, int nb) {
+  c3h::RemoveOverlapFrames ro{};
+  ro.M = std::max(ctx->M, 1);
+  ro.nf = nb;
+  ro.rank = ctx->rank;
+  ro.r1 = range[0];
+  ro.r2 = range[1];
+  ro.r3 = range[2];
+  for (int f = 0; f < nb; ++f) ro.outs[f] = outs[f];
+  return ro;
+}
+
+bool overlap_wanted(const c3h_ctx* ctx) { return ctx->remove_overlap && ctx->rank >= 2; }
+
+// the batch entry points' limit: the per-slot form holds a list on the lanes of one wave
+int overlap_rank_check(c3h_ctx* ctx, const char* who) {
+  if (ctx->remove_overlap && ctx->rank > 64)
+    return fail(ctx, C3H_ERR_ARG, std::string(who) + ": c3h_set_remove_overlap needs rank <= 64");
+  return C3H_OK;
+}
+
 // frames of chunk ch (B per chunk); the last chunk puts its last frame in slot 0, so the
 // context that runs it ends up holding the last frame's state
 int chunk_frames(const uint32_t* const* d_grids, c3h_det* d_out, size_t per_frame, int nframes, int B,
@@ -2252,6 +2287,10 @@ int pipe_tick(c3h_ctx* ctx, const c3h_ctx::PipeBatch* fresh) {
       Timed tm(ctx, 4, b.nf);
       hipError_t e = c3h::launch_replay_frames(b.rp, ctx->stream);
       if (e != hipSuccess) return hip_fail(ctx, "launch_replay_frames", e);
+    }
+    if (b.age == 3 && b.overlap) {  // removeOverlap on its frames' records, behind the replay
+      hipError_t e = c3h::launch_remove_overlap_frames(b.ro, ctx->stream);
+      if (e != hipSuccess) return hip_fail(ctx, "launch_remove_overlap_frames", e);
     }
     if (b.age == 2 && b.set) b.set->scores_layout = b.layout;  // this tick enqueued its gate
     if (b.age == 1 && b.fix) {  // its tile role ran in this tick: the off-cell fixup before its compress
@@ -2327,6 +2366,8 @@ int pipe_prepare(c3h_ctx* ctx, const uint32_t* const* grids, c3h_det* const* out
   fresh->layout = c->cap_layout;
   fresh->replay = !c->cap_argmax;
   fresh->rp = c->cap_rp;
+  fresh->overlap = overlap_wanted(ctx);
+  if (fresh->overlap) fresh->ro = overlap_args(ctx, k.range, outs, nb);
   return rc;
 }
 
@@ -2374,12 +2415,20 @@ c3h_ctx::PipeKey pipe_key(c3h_ctx* ctx, const int32_t div_b[3], const int32_t mi
   k.rotate = rotate ? 1 : 0;
   k.batch = B;
   k.rank = ctx->rank;
+  k.remove_overlap = ctx->remove_overlap;
   k.setup_version = ctx->setup_version;
   return k;
 }
 
+// models the tick's score role takes: r <= 64 (either engine), or wide ones on the matrix
+// cores (with c3h_set_score_engine(1) there is no VALU role for them: the lanes)
+bool tick_models_ok(const c3h_ctx* ctx) {
+  return c3h::score_fast_ok(ctx->D, ctx->r) ||
+         (ctx->score_engine != 1 && c3h::score_tick_wide_ok(ctx->D, ctx->M, ctx->r));
+}
+
 bool pipelinable(const c3h_ctx* ctx) {
-  return ctx->pipeline && ctx->rank >= 1 && ctx->rank <= 64 && c3h::score_fast_ok(ctx->D, ctx->r);
+  return ctx->pipeline && ctx->rank >= 1 && ctx->rank <= 64 && tick_models_ok(ctx);
 }
 
 // Runs nframes through the pipeline in batches of B.  drain: run the fill/drain ticks so
@@ -2439,6 +2488,7 @@ int c3h_run_frames(c3h_ctx* ctx, const uint32_t* const* d_grids, int32_t nframes
     return C3H_ERR_ARG;
   if (!ctx->have_setup) return fail(ctx, C3H_ERR_STATE, "c3h_run_frames: no axes (call c3h_search_setup)");
   if (!extract_params_ok(p)) return fail(ctx, C3H_ERR_ARG, "c3h_run_frames: variant / color_mode");
+  if (int rc = overlap_rank_check(ctx, "c3h_run_frames")) return rc;
   HIPCHK(hipSetDevice(ctx->device));
   {
     int rc = pipe_flush(ctx);  // an open stream completes first
@@ -2447,13 +2497,16 @@ int c3h_run_frames(c3h_ctx* ctx, const uint32_t* const* d_grids, int32_t nframes
   if (nframes == 0) return 0;
   const size_t per_frame = (size_t)std::max(ctx->M, 1) * ctx->rank;
   // frames go in chunks of B (one set of launches per chunk, frame = launch y / z index)
-  const int B = c3h::score_fast_ok(ctx->D, ctx->r) ? std::max(1, std::min(ctx->nbatch, c3h::kMaxBatch)) : 1;
-  const int nchunks = (nframes + B - 1) / B;
+  const int Bset = std::max(1, std::min(ctx->nbatch, c3h::kMaxBatch));
   if (pipelinable(ctx)) {
     const int rc = run_frames_pipelined(ctx, d_grids, nframes, div_b, min_b, leaf, p, range, exist_threshold,
-                                        rotate, d_out, B, true);
+                                        rotate, d_out, Bset, true);
     if (rc != 0) return rc;
   }
+  // the lanes' multi-frame launch is the VALU list kernel's: wide models (r > 64) go one frame
+  // per chunk there, whatever batch the pipeline was offered
+  const int B = c3h::score_fast_ok(ctx->D, ctx->r) ? Bset : 1;
+  const int nchunks = (nframes + B - 1) / B;
   // lanes: chunks are spread over K child contexts on their own streams and host threads
   const int K = std::max(1, std::min(ctx->nlanes, nchunks));
   {
@@ -2476,6 +2529,10 @@ int c3h_run_frames(c3h_ctx* ctx, const uint32_t* const* d_grids, int32_t nframes
       int rc = c3h_set_grid(c, grids[0], div_b, min_b, leaf, 1);
       if (rc == C3H_OK) rc = extract_frames(c, grids, nb, p, nullptr, nullptr);
       if (rc == C3H_OK) rc = search_frames(c, nb, range, exist_threshold, rotate, outs, 2);
+      if (rc >= 0 && overlap_wanted(ctx)) {
+        const hipError_t e = c3h::launch_remove_overlap_frames(overlap_args(ctx, range, outs, nb), c->stream);
+        if (e != hipSuccess) rc = hip_fail(c, "launch_remove_overlap_frames", e);
+      }
       if (rc < 0) {
         lane_rc[lane] = rc;
         return;
@@ -2507,6 +2564,7 @@ int c3h_stream_frames(c3h_ctx* ctx, const uint32_t* const* d_grids, int32_t nfra
     return C3H_ERR_ARG;
   if (!ctx->have_setup) return fail(ctx, C3H_ERR_STATE, "c3h_stream_frames: no axes (call c3h_search_setup)");
   if (!extract_params_ok(p)) return fail(ctx, C3H_ERR_ARG, "c3h_stream_frames: variant / color_mode");
+  if (int rc = overlap_rank_check(ctx, "c3h_stream_frames")) return rc;
   if (nframes == 0) return ctx->pipe_nm;
   HIPCHK(hipSetDevice(ctx->device));
   const int B = std::max(1, std::min(ctx->nbatch, c3h::kMaxBatch));
@@ -2541,6 +2599,10 @@ int point_frame_single(c3h_ctx* ctx, const float* pts, int64_t n, int on_device,
   int32_t sb[3] = {0, 0, 0};
   if (rc == C3H_OK) rc = extract_frames(ctx, &ctx->grid_ptr, 1, p, sb, nullptr);
   if (rc == C3H_OK) rc = search_frames(ctx, 1, range, thr, rotate, &d_out_f, 2);
+  if (rc >= 0 && overlap_wanted(ctx)) {
+    const hipError_t e = c3h::launch_remove_overlap_frames(overlap_args(ctx, range, &d_out_f, 1), ctx->stream);
+    if (e != hipSuccess) rc = hip_fail(ctx, "launch_remove_overlap_frames", e);
+  }
   if (fi) {
     memset(fi, 0, sizeof(*fi));
     if (rc >= 0) {
@@ -2577,6 +2639,7 @@ int c3h_run_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n
   if (p->variant != 981 && p->variant != 117) return fail(ctx, C3H_ERR_ARG, "c3h_run_point_frames: variant");
   if (p->color_mode < C3H_COLOR_C3_FLOAT || p->color_mode > C3H_COLOR_CHLAC)
     return fail(ctx, C3H_ERR_ARG, "c3h_run_point_frames: color_mode");
+  if (int rc = overlap_rank_check(ctx, "c3h_run_point_frames")) return rc;
   int64_t cvox = 1;
   for (int a = 0; a < 3; ++a) {
     if (canvas[a] < 1) return fail(ctx, C3H_ERR_ARG, "c3h_run_point_frames: canvas dims must be >= 1");

@@ -215,6 +215,26 @@ bool tick_segmap_ok(const C3Launch& l, const C3Args& c) {
          w117_map_fits(l.lmax[0], l.lmax[1], l.lmax[2]);
 }
 
+// The score role of a batch of wide models (r > 64) as a kernel of its own: score_tick_wide_body
+// does not fit the tick's 128 VGPRs (19 spilled, 72 B of scratch per lane, where the tick has
+// none to give: DESIGN.md section 8), so the tick of such a batch's score slot carries no score
+// role and this launch follows it on the stream, the way the batched replay follows a tick.
+// Two workgroups per CU leave the body its registers.  Workgroup (x, f): list chunks x, x + gx,
+// ... of frame f.
+constexpr int kWideGridCap = 32;  // workgroups per frame (surface frames pass ~30 list chunks)
+__global__ __launch_bounds__(kBlock, 2) void score_wide_frames_kernel(SparseSearch q, int gx, int tpp) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t wide_smem[];
+  score_tick_wide_body(q, blockIdx.x, blockIdx.y, gx, tpp, reinterpret_cast<float*>(wide_smem));
+}
+
+hipError_t launch_score_wide(const SparseSearch& a, hipStream_t s) {
+  if (a.nframes < 1) return hipSuccess;
+  const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(sparse_score_blocks(a), kWideGridCap));
+  const int tpp = score_tick_wide_tpp(a.D, a.M, a.r);
+  score_wide_frames_kernel<<<dim3((unsigned)gx, (unsigned)a.nframes), kBlock, score_list_lds_bytes(a.D, 1), s>>>(a, gx, tpp);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 bool tick_ok(const C3Launch& l) {
@@ -239,7 +259,13 @@ hipError_t launch_tick(const TickParts& p, hipStream_t s) {
       t.order = 0;
       for (int i = 0; i < 4; ++i) t.order |= (o[i] - '0') << (4 * i);
     }
-  if (p.score) {
+  // Wide models (r > 64) have no VALU body and no role in the tick: their score role is a
+  // kernel of its own behind the tick (score_wide_frames_kernel)
+  const SparseSearch* wide = p.score && p.score->r > kOC ? p.score : nullptr;
+  if (wide && (wide->score_engine == 1 || wide->mpg != 1 || wide->nframes > kMaxBatch ||
+               !score_tick_wide_ok(wide->D, wide->M, wide->r)))
+    return hipErrorInvalidValue;
+  if (p.score && !wide) {
     const SparseSearch& a = *p.score;
     t.sq = a;
     t.s_gx = (int)std::max<int64_t>(1, std::min<int64_t>(sparse_score_blocks(a), env_int("C3H_TICK_SCORE", 16)));
@@ -346,7 +372,7 @@ hipError_t launch_tick(const TickParts& p, hipStream_t s) {
     if (!(mask & 8)) t.ka.segmap = nullptr;  // no stream, no map
   }
   const int total = t.n_score + t.n_cg + t.n_tile + t.n_occ;
-  if (total == 0) return hipSuccess;
+  if (total == 0) return wide ? launch_score_wide(*wide, s) : hipSuccess;
   // XCD placement per role: its frame count a multiple of 8 and its first block at a
   // multiple of 8 in the launch
 #ifndef C3H_TICK_XCD
@@ -377,6 +403,10 @@ hipError_t launch_tick(const TickParts& p, hipStream_t s) {
   }
   c3h_tick_kernel<<<(unsigned)total, kBlock, lds, s>>>(t);
   if (t.prof) tick_prof_dump(t, t.prof, total, s);
+  if (wide) {  // the batch whose score slot this tick is: its scores follow the tick on the stream
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : launch_score_wide(*wide, s);
+  }
   return hipGetLastError();
 }
 

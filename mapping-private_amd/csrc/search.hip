@@ -17,6 +17,7 @@
 //   (the lists only grow) are visited serially.  replay_frames_kernel does the same for
 //   every frame of a batch in one launch, at ranks up to 64 (the list on the lanes of a wave).
 #include "c3h_internal.h"
+#include "overlap_list.h"
 #include "rank_list.h"
 #include "search_dev.h"
 
@@ -1046,6 +1047,74 @@ __global__ __launch_bounds__(kBlock) void replay_frames_kernel(ReplayFrames a) {
   }
 }
 
+// SearchObjMulti::removeOverlap (search.cpp:972-992) on the records of a whole batch: one
+// wave per frame, list slot j on lane j (overlap_list.h's per-slot form).  Model m's list
+// stays in registers over its m2 loop; the m2 lists come from the frame's records, the next
+// kRoAhead of them in flight while a step runs.  A lane only ever loads and stores its own
+// slot of a list and this wave alone writes the frame's lists, so program order keeps every
+// load behind the store it depends on: a step stores list m2 only, the lists in flight are
+// m2 + 1 .. (none is m: its copy is written back after the loop, before the next m's loads).
+constexpr int kRoAhead = 4;
+
+__device__ __forceinline__ c3h_det ro_load(const c3h_det* __restrict__ fl, int m, int rank, int lane) {
+  return fl[m * rank + min(lane, rank - 1)];  // lanes past the list repeat its last slot (never used)
+}
+
+__device__ __forceinline__ c3h_det ro_above(const c3h_det& e) {
+  c3h_det a;
+  a.score = __shfl_down(e.score, 1, 64);
+  a.x = __shfl_down(e.x, 1, 64);
+  a.y = __shfl_down(e.y, 1, 64);
+  a.z = __shfl_down(e.z, 1, 64);
+  a.mode = __shfl_down(e.mode, 1, 64);
+  return a;
+}
+
+__global__ __launch_bounds__(64) void remove_overlap_frames_kernel(RemoveOverlapFrames a) {
+  const int f = blockIdx.x, lane = threadIdx.x;
+  const int M = a.M, rank = a.rank, r1 = a.r1, r2 = a.r2, r3 = a.r3;
+  c3h_det* fl = a.outs[f];
+  const int T = M - 1;  // steps per m: m2 = t + (t >= m)
+  if (!fl || T < 1 || rank < 2 || rank > 64) return;
+  for (int m = 0; m < M; ++m) {
+    c3h_det em = ro_load(fl, m, rank, lane);
+    c3h_det nx[kRoAhead];
+#pragma unroll
+    for (int k = 0; k < kRoAhead; ++k) {
+      const int t = min(k, T - 1);
+      nx[k] = ro_load(fl, t + (t >= m), rank, lane);
+    }
+    for (int t0 = 0; t0 < T; t0 += kRoAhead) {
+#pragma unroll
+      for (int k = 0; k < kRoAhead; ++k) {
+        const int t = t0 + k;
+        if (t >= T) break;
+        const int m2 = t + (t >= m);
+        c3h_det cur = nx[k];
+        {
+          const int tn = min(t + kRoAhead, T - 1);
+          nx[k] = ro_load(fl, tn + (tn >= m), rank, lane);
+        }
+        const double s0 = rf_bcast(em.score, 0);
+        const int x0 = __builtin_amdgcn_readlane(em.x, 0), y0 = __builtin_amdgcn_readlane(em.y, 0),
+                  z0 = __builtin_amdgcn_readlane(em.z, 0), mode0 = __builtin_amdgcn_readlane(em.mode, 0);
+        int xr, yr, zr;
+        get_range(mode0, r1, r2, r3, xr, yr, zr);
+        const int ov = rank_stop_slot(__ballot(rank_overlaps(cur, x0, y0, z0, xr, yr, zr, r1, r2, r3)), rank);
+        if (overlap_m_wins(s0, rf_bcast(cur.score, ov))) {
+          if (ov < rank - 1) {  // (from the last slot on nothing moves)
+            cur = overlap_slot_shift(lane, cur, ro_above(cur), ov, rank);
+            if (lane < rank) fl[m2 * rank + lane] = cur;
+          }
+        } else {
+          em = overlap_slot_shift(lane, em, ro_above(em), 0, rank);
+        }
+      }
+    }
+    if (lane < rank) fl[m * rank + lane] = em;
+  }
+}
+
 }  // namespace
 
 // subdivision counts from which the stand-alone search compresses on the matrix cores
@@ -1098,6 +1167,13 @@ size_t score_lds_bytes(int D, int r, int SP) {
 
 bool score_fast_ok(int D, int r) { return D <= 160 && (D & 3) == 0 && r <= kOC; }
 bool score_mfma_ok(int D) { return D >= 4 && D <= 160 && (D & 3) == 0; }
+// wide models (r > 64: no VALU list body) in the pipeline's matrix-core score launch
+// (score_tick_wide_body): one model spans at most 8 column tiles, and a pass of the role fits
+// the LDS an r <= 64 search at this D allocates
+bool score_tick_wide_ok(int D, int M, int r) {
+  return D >= 4 && D <= 160 && (D & 3) == 0 && M >= 1 && r > kOC && score_tick_tiles(1, r) <= 8 &&
+         (int64_t)M * r <= INT32_MAX / 64 && score_tick_wide_tpp(D, M, r) >= 1;
+}
 
 int64_t score_blocks(const ScoreLaunch& a) {
   const int64_t P = (int64_t)a.xe * a.ye * a.ze;
@@ -1229,6 +1305,16 @@ hipError_t launch_replay_frames(const ReplayFrames& a, hipStream_t s) {
   if (!replay_frames_ok(a.modes, a.rank) || a.nf > kMaxBatch) return hipErrorInvalidValue;
   if (a.M < 1 || a.nf < 1) return hipSuccess;
   replay_frames_kernel<<<dim3((unsigned)a.M, (unsigned)a.nf), kBlock, 0, s>>>(a);
+  return hipGetLastError();
+}
+
+hipError_t launch_remove_overlap_frames(const RemoveOverlapFrames& a, hipStream_t s) {
+  if (a.rank < 1 || a.rank > 64 || a.nf > kMaxBatch || a.r1 < 1 || a.r2 < 1 || a.r3 < 1 ||
+      (int64_t)a.M * a.rank > INT32_MAX)
+    return hipErrorInvalidValue;
+  // rank 1: the reference's shift loops are empty; one model: no pair
+  if (a.rank < 2 || a.M < 2 || a.nf < 1) return hipSuccess;
+  remove_overlap_frames_kernel<<<(unsigned)a.nf, 64, 0, s>>>(a);
   return hipGetLastError();
 }
 

@@ -1171,4 +1171,232 @@ __device__ __forceinline__ void score_tick_mfma_body(const SparseSearch& b, int 
   C3H_SPROF(7);
 }
 
+// The same role for wide models (r > 64: score_tick_wide_ok).  Passes of whole models leave
+// tiles idle there (two models of r = 70 are 4.4 tiles: one wave does two, three do one), so
+// a pass is a run of whole 32-column tiles of the M r columns that ignores model boundaries:
+// tpp tiles (score_tick_wide_tpp: as many as the VALU body's LDS holds, at most 8).  The fold
+// carries the ||Q_m f||^2 partial of the model a pass ends in through LDS (one float per
+// position, double-buffered by pass parity: the model a pass starts in and the one it ends in
+// are folded by different threads) and continues the same ascending-column fmaf chain from it,
+// so the value is bit-for-bit the one-pass value; a model's score, its write and its argmax
+// partial are finished in the pass that holds its last column.  The next pass's first kTickPF
+// B fragments are issued before the fold, so their L2 latency sits under it.  Everything else
+// is score_tick_mfma_body's.
+//
+// LDS: fT (D x kFP), qv (32 tpp columns x kTickQS), ffv, the carry (2 x kFP), the per-chunk
+// scratch, the scores of the models that finish in a pass (at most kTickWideFin: 256 columns,
+// r > 64) -- inside score_list_lds_bytes(D, 1).
+constexpr int kTickWideFin = 4;
+__host__ __device__ inline size_t score_tick_wide_lds_bytes(int D, int tpp) {
+  return sizeof(float) * ((size_t)D * kFP + (size_t)kTickQS * 32 * tpp + kFP + 2 * kFP) + sizeof(int) * 4 * kFP +
+         sizeof(long long) * kFP + sizeof(double) * kFP * kTickWideFin + 16 + 16;
+}
+// tiles per pass; 0: not even one fits
+__host__ __device__ inline int score_tick_wide_tpp(int D, int M, int r) {
+  int tpp = score_tick_tiles(M, r) < 8 ? score_tick_tiles(M, r) : 8;
+  while (tpp > 0 && score_tick_wide_lds_bytes(D, tpp) > score_list_lds_bytes(D, 1)) --tpp;
+  return tpp;
+}
+
+// block bx of gdx workgroups of frame fz_; tpp: score_tick_wide_tpp; smem: score_list_lds_bytes(D, 1)
+__device__ __forceinline__ void score_tick_wide_body(const SparseSearch& b, int bx, int fz_, int gdx, int tpp,
+                                                     float* ssm) {
+  const SparseSearch& a = b;
+  const int64_t fz = fz_;
+  const float* __restrict__ fG = b.G + fz * b.s_G;
+  const int32_t* __restrict__ fexist = b.exist + fz * b.s_exist;
+  double* __restrict__ fscores = b.scores + fz * b.s_scores;
+  const long long* __restrict__ flist = b.list + fz * b.s_list;
+  const uint32_t* fcnt = b.cnt + fz * b.s_cnt;
+  uint32_t* fdone = b.done + fz * b.s_cnt;
+  ScorePartial* fpart = b.partials ? b.partials + fz * b.s_partials : nullptr;
+  c3h_det* flists = b.lists ? b.lists + fz * b.s_lists : nullptr;
+  c3h_det* fout = b.outs[fz];
+  const int D = a.D, Qs = a.Opad, r = a.r;  // qt row stride
+  const int tid = threadIdx.x, lane = tid & 63, hk = lane >> 5, l32 = lane & 31;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // scalar: the tile branches are uniform
+  const int64_t ptot = a.pstart[a.nmodes];
+  long long en_first = -1;
+  if (tid < kFP) en_first = flist[min((int64_t)bx * kFP + tid, ptot - 1)];
+  const int n = (int)fcnt[a.epoch & 1];
+  const int nch = (n + kFP - 1) / kFP;  // list chunks; chunk c -> workgroups c mod gdx
+  if (bx >= nch) {
+    if (n == 0 && flists && bx == 0) argmax_finalize(a, fpart, flists, fout, 0);  // clean / copy out
+    return;
+  }
+  float* fT = ssm;                  // D x kFP (k-major box features)
+  float* qv = ssm + D * kFP;        // a pass's projections, [column][position]
+  float* ffv = qv + kTickQS * 32 * tpp;
+  float* carry = ffv + kFP;         // [pass parity][position]
+  int* gate = reinterpret_cast<int*>(carry + 2 * kFP);
+  int* hrow = gate + kFP;
+  int* rng = hrow + kFP;                       // packed xr | yr << 10 | zr << 20
+  long long* ent = reinterpret_cast<long long*>(rng + kFP + (kFP & 1));
+  double* bsc = reinterpret_cast<double*>(ent + kFP);  // kFP * kTickWideFin
+  const int xyn = a.xn * a.yn;
+  const int KP = D >> 1;  // k-pairs (D % 4 == 0)
+  const int C = a.M * r, NT = (C + 31) >> 5;  // columns, tiles
+  float bc[2][kTickPF], bn[2][kTickPF];
+  // B fragments of k-pairs j0 .. of the wave's tiles t and t + 4 of the pass that starts at tile
+  // t0 (a wave with one tile reads it twice: no branch per load).  Columns past Opad - 1 are
+  // clamped, not masked: they are never folded (qt is finite)
+  auto load_b = [&](float (&v)[2][kTickPF], int t0, bool two, int j0) {
+    const uint32_t v0 = (uint32_t)(hk * Qs + min(32 * (t0 + wave) + l32, Qs - 1));
+    const uint32_t v1 = two ? (uint32_t)(hk * Qs + min(32 * (t0 + wave + 4) + l32, Qs - 1)) : v0;
+#pragma unroll
+    for (int jj = 0; jj < kTickPF; ++jj) {
+      // pairs past D re-read the last pair and are never used
+      const float* __restrict__ rowp = a.qt + (int64_t)min(2 * (j0 + jj), D - 2) * Qs;
+      v[0][jj] = rowp[v0];
+      v[1][jj] = rowp[v1];
+    }
+  };
+  for (int ch = bx; ch < nch; ch += gdx) {
+    const int64_t e0 = (int64_t)ch * kFP;
+    if (tid < kFP) {
+      const int64_t e = e0 + tid;
+      int ok = 0, h = 0, rr = 0;
+      long long en = -1;
+      if (e < n) {
+        en = ch == bx ? en_first : flist[e];
+        const int mi = (int)(en >> 40);
+        const int64_t p = en & ((1ll << 40) - 1);
+        const ModeGeom& md = a.md[mi];
+        const int64_t xye = (int64_t)md.xe * md.ye;
+        const int x = (int)(p % md.xe), y = (int)((p / md.xe) % md.ye), z = (int)(p / xye);
+        h = z * xyn + y * a.xn + x;
+        rr = md.xr | (md.yr << 10) | (md.zr << 20);
+        ok = 1;
+      }
+      gate[tid] = ok;
+      hrow[tid] = h;
+      rng[tid] = rr;
+      ent[tid] = en;
+    }
+    lds_barrier();
+    score_gather_rows(a, fG, fexist, gate, hrow, rng, fT);
+    // the first pass's first B fragments
+    if (wave < min(tpp, NT)) load_b(bc, 0, wave + 4 < min(tpp, NT), 0);
+    lds_barrier();
+    // f.f in ascending d, by the last wave (it has the fewest tiles when they do not divide)
+    if (tid >= kBlock - 64 && lane < kFP) {
+      float s = 0.0f;
+      for (int d = 0; d < D; ++d) s = __builtin_fmaf(fT[d * kFP + lane], fT[d * kFP + lane], s);
+      ffv[lane] = s;
+    }
+    int mA = 0;  // the model that holds the pass's first column
+    for (int t0 = 0, par = 0; t0 < NT; t0 += tpp, par ^= 1) {
+      const int nt = min(tpp, NT - t0);
+      // wave w: tiles w and w + 4 of the pass (at most 8), sharing every A fragment
+      const bool one = wave < nt, two = wave + 4 < nt;  // wave-uniform
+      mf_f32x16 acc0, acc1;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) acc0[q] = acc1[q] = 0.0f;
+      if (one) {
+        for (int j0 = 0; j0 < KP; j0 += kTickPF) {
+          if (j0 + kTickPF < KP) load_b(bn, t0, two, j0 + kTickPF);
+#pragma unroll
+          for (int jj = 0; jj < kTickPF; ++jj) {
+            if (j0 + jj < KP) {  // uniform
+              const float av = fT[(2 * (j0 + jj) + hk) * kFP + l32];
+              acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bc[0][jj], acc0, 0, 0, 0);
+              if (two) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bc[1][jj], acc1, 0, 0, 0);
+            }
+          }
+          if (j0 + kTickPF < KP) {
+#pragma unroll
+            for (int jj = 0; jj < kTickPF; ++jj) {
+              bc[0][jj] = bn[0][jj];
+              bc[1][jj] = bn[1][jj];
+            }
+          }
+        }
+      }
+      // the next pass's first B fragments: in flight over this pass's fold
+      if (t0 + tpp < NT) {
+        const int ntn = min(tpp, NT - t0 - tpp);
+        if (wave < ntn) load_b(bc, t0 + tpp, wave + 4 < ntn, 0);
+      }
+      lds_barrier();  // the previous pass's fold is done with qv; ffv is written
+      // C/D map: column l32, row (q & 3) + 8 (q >> 2) + 4 hk
+      if (one) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) qv[(32 * wave + l32) * kTickQS + 4 * hk + (q & 3) + 8 * (q >> 2)] = acc0[q];
+      }
+      if (two) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+          qv[(32 * (wave + 4) + l32) * kTickQS + 4 * hk + (q & 3) + 8 * (q >> 2)] = acc1[q];
+      }
+      lds_barrier();
+      // the pass holds columns [cA, cB): models mA .. (cB - 1) / r; those whose last column it
+      // holds (mA .. cB / r - 1, at most kTickWideFin) finish here
+      // (mA advances pass by pass: no scalar division)
+      const int cA = 32 * t0, cB = min(C, 32 * (t0 + nt));
+      while ((mA + 1) * r <= cA) ++mA;
+      int nfin = 0;
+      while ((mA + nfin + 1) * r <= cB) ++nfin;
+      const int nmod = nfin + ((mA + nfin) * r < cB ? 1 : 0);
+      for (int e = tid; e < kFP * nmod; e += kBlock) {
+        const int mm = e / kFP, pp = e - mm * kFP, m = mA + mm;
+        const int i0 = max(m * r, cA), i1 = min((m + 1) * r, cB);
+        const bool fin = i1 == (m + 1) * r;
+        double sc = -2.0;
+        if (gate[pp]) {
+          float q2 = i0 > m * r ? carry[par * kFP + pp] : 0.0f;
+          const float* q = qv + (i0 - cA) * kTickQS + pp;
+#pragma unroll 4  // reads issued four at a time (a dependent LDS round trip per element otherwise)
+          for (int i = 0; i < i1 - i0; ++i) q2 = __builtin_fmaf(q[i * kTickQS], q[i * kTickQS], q2);
+          if (fin) {
+            sc = sqrt((double)q2) / sqrt((double)ffv[pp]);
+            const long long en = ent[pp];
+            const ModeGeom& md = a.md[(int)(en >> 40)];
+            fscores[md.offset + (int64_t)m * md.P + (en & ((1ll << 40) - 1))] = sc;
+          } else {
+            carry[(par ^ 1) * kFP + pp] = q2;
+          }
+        }
+        if (fin) bsc[e] = sc;  // (the finishing models are the first nfin of the pass)
+      }
+      if (fpart && nfin > 0) {  // uniform
+        lds_barrier();
+        for (int mm = tid; mm < nfin; mm += kBlock) {  // (score desc, scan order asc)
+          double best = -2.0;
+          long long bo = -1;
+          for (int pp = 0; pp < kFP; ++pp) {
+            if (!gate[pp]) continue;
+            const double sc = bsc[mm * kFP + pp];
+            const long long en = ent[pp];
+            const long long o = a.order_base[(int)(en >> 40)] + (en & ((1ll << 40) - 1));
+            if (sc > best || (sc == best && o < bo)) {
+              best = sc;
+              bo = o;
+            }
+          }
+          ScorePartial* q = fpart + (int64_t)ch * a.M + mA + mm;
+          if (flists) {  // handed to another workgroup inside this launch: sc1 stores
+            __hip_atomic_store(&q->score, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&q->order, bo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          } else {
+            *q = ScorePartial{best, bo};
+          }
+        }
+      }
+    }
+    lds_barrier();  // LDS is reused by the next chunk
+  }
+  if (fpart && flists) {
+    // rank 1, fused replay: the last workgroup to finish reduces (score_list_body's hand-off)
+    int& s_last = *reinterpret_cast<int*>(reinterpret_cast<char*>(ssm) + score_list_lds_bytes(D, a.mpg) - 16);
+    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    lds_barrier();
+    if (tid == 0) {
+      const uint32_t total = (uint32_t)min(nch, gdx);
+      s_last = atomicAdd(&fdone[a.epoch & 1], 1u) == total - 1;
+    }
+    lds_barrier();
+    if (s_last) argmax_finalize(a, fpart, flists, fout, nch);
+  }
+}
+
 }  // namespace c3h

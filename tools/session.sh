@@ -31,6 +31,9 @@
 #   real_views       the reference's 126 committed Kinect views (tools/real_views_bench.py) -> real_views.json
 #   tileprof         the dot4 tile body's phases on a points-in frame (tools/tile_prof.py; with
 #                    VARIANT=<a diagnostics build> the C3H_PROF phase lines) -> tile_prof.*
+#   wide             63 models of r = 70 on the batch path (tools/wide_models_bench.py), this tree
+#                    and lib/variants/parent.so (the parent commit's library) in alternation,
+#                    three rounds                          -> wide.jsonl
 # Variants: VARIANT=name selects lib/variants/name.so for the python steps (C3HLAC_LIB).
 set -o pipefail
 TAG=$1
@@ -83,6 +86,14 @@ for step in "$@"; do
     config5) timeout -k 10 300 python -u tools/config5.py --fp16 > $O/config5.log 2>&1 || exit 21 ;;
     real_views) timeout -k 10 300 python -u tools/real_views_bench.py tests/golden/kinect_views_126.npz > $O/real_views.json 2> $O/real_views.err || exit 22 ;;
     tileprof) C3H_PROF=$O/tile_prof_phases.txt timeout -k 10 200 python -u tools/tile_prof.py 20 981 10 > $O/tile_prof.json 2> $O/tile_prof.err || exit 23 ;;
+    wide) rm -f $O/wide.jsonl
+      for rep in 1 2 3; do
+        for v in parent tree; do
+          if [ $v = tree ]; then unset C3HLAC_LIB; else export C3HLAC_LIB=$R/mapping-private_amd/lib/variants/parent.so; fi
+          timeout -k 10 300 python -u tools/wide_models_bench.py >> $O/wide.jsonl 2>> $O/wide.err || exit 29
+        done
+      done
+      unset C3HLAC_LIB ;;
     *) echo "unknown step $step" >&2; exit 2 ;;
   esac
 done
