@@ -355,7 +355,9 @@ int c3h_stream_flush(c3h_ctx* ctx);
  * more than 4,096 such voxels (65,536 of their points) or 256 moved ones, a centroid cell
  * past the last subdivision, one subdivision where the canvas has several (computeC3HLAC's
  * hist_num == 1 rule), no valid point -- are recomputed on the single-frame path after the
- * batches (status 1).  info (host, nframes records, may be
+ * batches (status 1).  Without subdivisions (p->subdiv == 0, a canvas of at most 16 voxels per
+ * axis) the reference runs no search: the batch is voxelised and its histogram computed, and
+ * the frames' lists are the fresh setRank state (status 0).  info (host, nframes records, may be
  * NULL): the frame's VoxelGrid geometry, getSubdivNum, point and voxel counts and status
  * (0 batched, 1 single-frame path, < 0 the C3H_ERR_* that frame failed with; its lists are
  * the fresh setRank state).  One host synchronisation per call (the frames' records).

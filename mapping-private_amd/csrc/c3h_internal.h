@@ -720,6 +720,8 @@ struct c3h_ctx {
     c3h::ReplayFrames rp{};
     bool overlap = false;         // c3h_set_remove_overlap: removeOverlap on d_out follows the replay
     c3h::RemoveOverlapFrames ro{};
+    bool nosearch = false;        // points-in without subdivisions (S = 0): SearchObj::setData returns
+                                  // early, so the batch leaves after its tile role and fixup
   };
   struct PipeKey {
     int32_t div_b[3], min_b[3];

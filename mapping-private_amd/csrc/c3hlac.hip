@@ -389,6 +389,14 @@ __global__ __launch_bounds__(64) void offcell_delta_kernel(OffcellArgs o) {
 // stamped and appended to the row list the compress role reads.  One workgroup per (frame,
 // job), jobs deduplicated.
 __device__ __forceinline__ int fix_centre_sub(const PointFixup& a, const int c[3], int* tile) {
+  // one subdivision (computeC3HLAC's hist_num == 1 rule, c3_hlac.cpp:350): no centre test,
+  // every voxel counts in histogram 0 wherever its centroid cell lies -- below cell 0 too
+  // (round 14: such a voxel was dropped).  The direct mode has one tile there (a split
+  // subdivision takes the atomic mode, which has no fixup)
+  if (a.s_h == 1) {
+    *tile = 0;
+    return 0;
+  }
   for (int ax = 0; ax < 3; ++ax)
     if (c[ax] < 0 || c[ax] >= a.C[ax]) return -1;
   const int ix = a.axmap[c[0]], iy = a.axmap[a.C[0] + c[1]], iz = a.axmap[a.C[0] + a.C[1] + c[2]];

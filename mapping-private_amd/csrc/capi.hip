@@ -2300,7 +2300,7 @@ int pipe_tick(c3h_ctx* ctx, const c3h_ctx::PipeBatch* fresh) {
   }
   std::vector<c3h_ctx::PipeBatch> next;
   for (auto& b : ctx->pipe)
-    if (b.age < 3) {
+    if (b.age < (b.nosearch ? 1 : 3)) {
       next.push_back(b);
       next.back().age++;
     }
@@ -2350,6 +2350,14 @@ int pipe_prepare(c3h_ctx* ctx, const uint32_t* const* grids, c3h_det* const* out
   if (rc < 0) {
     if (c != ctx) ctx->err = c->err;
     return rc;
+  }
+  // points-in frames without subdivisions (S = 0, one histogram): the reference runs no search
+  // (search_frames returned 0: setData returns early), the batch is its C3 stage alone
+  if (rc == 0 && lim && k.p.subdiv == 0 && c->cap_c3_valid && c3h::tick_ok(c->cap_c3)) {
+    c->nframes_feat = 1;
+    *fresh = c3h_ctx::PipeBatch{c->cap_c3, c3h::SparseSearch{}, c3h::SparseCompress{}, nb, 0};
+    fresh->nosearch = true;
+    return 1;
   }
   // rank 1: the score role's fused argmax; ranks 2 .. 64: the score role writes the scores
   // only and the batched replay follows it
@@ -2928,8 +2936,13 @@ int c3h_run_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n
       // tick less per call after the last voxeliser).  An unstamped batch's first tick
       // streams its canvases: it waits.
       if (!fresh.stamped) HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->pb_vox_ev, 0));
+      if (fresh.nosearch)  // no search: the frames' lists are the fresh setRank state
+        HIPCHK(hipMemsetAsync(d_out + (size_t)f0 * per_frame, 0, (size_t)nb * per_frame * sizeof(c3h_det), ctx->stream));
       rc = pipe_commit(ctx, fresh, k, rc);
-      if (rc > 0) nm = rc;
+      if (rc > 0) {
+        int modes[6];  // as the single-frame path: the modes the search schedules
+        nm = fresh.nosearch ? mode_schedule(range[0], range[1], range[2], rotate, modes) : rc;
+      }
       if (rc >= 0) HIPCHK(hipEventRecord(ctx->pb_tick_ev[ch & 3], ctx->stream));
       if (fresh.stamped) HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->pb_vox_ev, 0));
     }
@@ -2964,7 +2977,7 @@ int c3h_run_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n
       for (int a = 0; a < 3; ++a) {
         o.min_b[a] = r.min_b[a];
         o.div_b[a] = r.max_b[a] - r.min_b[a] + 1;
-        o.subdiv_b[a] = r.sb[a];
+        o.subdiv_b[a] = p->subdiv > 0 ? r.sb[a] : 0;  // getSubdivNum without subdivisions: 0
         one = one && r.sb[a] == 1;
       }
       o.n_valid = r.n_valid;

@@ -1293,6 +1293,7 @@ __global__ __launch_bounds__(kBT) void voxb_bucket_kernel(VoxBatchArgs a, int ni
   // a batch without a flagged voxel in any frame (all synthetic points-in batches): one
   // load per frame, every block out at once
   __shared__ int s_any;
+  static_assert(kMaxBatch <= 64, "the early exit ballots one frame per lane of a single wave");
   if (tid < 64) {
     const bool fl = tid < a.nf && a.xcnt[4 * tid] != 0u;
     const unsigned long long m = __ballot(fl);
@@ -1445,7 +1446,8 @@ __global__ __launch_bounds__(kBlock) void voxb_exact_kernel(VoxBatchArgs a) {
     // whose centroid rounds up past it): the fixup's canvas maps have no entry there (its
     // centre subdivision would be dropped), while the reference may still count the voxel
     // in the last subdivision -- the frame takes the single-frame path.  (Below the canvas,
-    // bc = -1, the reference's tmp < 0 is no centre either: the fixup agrees.)
+    // bc = -1, the reference's tmp < 0 is no centre either; with one subdivision it has no
+    // such test and the voxel counts with neighbour base -1: the fixup does both.)
     if (bc[0] >= Cx || bc[1] >= Cy || bc[2] >= a.C[2]) {
       atomicOr(&rec.err, 8u);
       continue;
