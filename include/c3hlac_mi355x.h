@@ -376,6 +376,49 @@ int c3h_run_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n
                          int on_device, float leaf, float z_limit, const int32_t canvas[3],
                          const c3h_extract_params* p, const int32_t range[3], int32_t exist_threshold,
                          int32_t rotate, c3h_det* d_out, c3h_frame_info* info);
+/* Feature-rows batch driver: SearchObj(Multi)::setData + search() from fresh lists
+ * (color_voxel_recognition/src/search.cpp:539-658) for nframes frames whose features the caller
+ * computed elsewhere, as setVOSCH / setConVOSCH / setGRSD of color_voxel_recognition_2 hand
+ * them to setData (search_new.h:34-126) -- detect_object_vosch_multi.cpp's per-frame search
+ * over a whole batch.  Frame i = d_feat[i], a device pointer aligned to 4 bytes holding
+ * subdiv_b[3i] * subdiv_b[3i+1] * subdiv_b[3i+2] rows of dim floats, row h = x + y * xn +
+ * z * xn * yn in the frame's own counts, exactly as c3h_set_features takes them (subdiv_b:
+ * host, nframes x 3).  d_exist: NULL, or nframes device pointers to the rows'
+ * exist_voxel_num; NULL derives it by exist_rule (C3H_EXIST_*) with the arithmetic and the
+ * dim minimums of c3h_set_features.  dim must equal the F of c3h_search_setup.  canvas_b is
+ * the subdivision canvas of the batch: every frame's counts must be <= it per axis, else
+ * C3H_ERR_ARG before anything is enqueued.  Frames sit at the canvas origin and a box
+ * position passes only inside the frame's own subdivisions, so frame i's M x rank records
+ * (d_out + i * M * rank, device) are those of its own setData + search() from the setRank
+ * state; a frame none of whose boxes fit, or with a zero count on an axis, yields that state.
+ * One launch per batch (c3h_set_batch) puts the rows into the form the software-pipelined
+ * tick of c3h_run_frames takes after its C3 stage (exist values, the list of rows with data,
+ * the rows), and the batch joins the tick at its compress + gate role; c3h_set_rank,
+ * c3h_set_batch, c3h_set_score_engine, c3h_set_pipeline and c3h_set_remove_overlap apply as
+ * to c3h_run_frames.  Configurations the pipeline does not cover (c3h_set_pipeline(0),
+ * rank > 64, Dpad > 128 or D > 160, r > 64 with c3h_set_score_engine(1), r > 256) run frame by
+ * frame as c3h_set_features(on_device) + c3h_search_async would, in the frame's own layout.
+ * c3h_run_feature_frames drains: afterwards the context holds the last frame's search state
+ * in the canvas layout (c3h_get_feature_info reports canvas_b; c3h_get_scores and
+ * c3h_get_lists work; positions outside the frame score -1).  Only rows with data were kept,
+ * so c3h_get_features, c3h_get_compressed and a further c3h_search on that state return
+ * C3H_ERR_STATE until c3h_set_features or c3h_extract replaces it.  Returns the number of
+ * searched modes or an error; nothing synchronises the host on the pipelined route. */
+int c3h_run_feature_frames(c3h_ctx* ctx, const float* const* d_feat, const int32_t* const* d_exist,
+                           int32_t nframes, const int32_t* subdiv_b /* nframes x 3, host */,
+                           const int32_t canvas_b[3], int32_t dim, int32_t exist_rule,
+                           const int32_t range[3], int32_t exist_threshold, int32_t rotate,
+                           c3h_det* d_out);
+/* The streaming form, with c3h_stream_frames' completion rule: a batch's records are complete
+ * once three more batches were pushed, or after c3h_stream_flush; d_feat[i], d_exist[i] and
+ * d_out stay valid until then (the pointer arrays and subdiv_b only during the call).  A push
+ * with another key -- canvas, dim, rule, range, threshold, rotate, rank, batch, remove_overlap
+ * or search setup; a c3h_stream_frames push is another key too -- drains the open stream. */
+int c3h_stream_feature_frames(c3h_ctx* ctx, const float* const* d_feat, const int32_t* const* d_exist,
+                              int32_t nframes, const int32_t* subdiv_b /* nframes x 3, host */,
+                              const int32_t canvas_b[3], int32_t dim, int32_t exist_rule,
+                              const int32_t range[3], int32_t exist_threshold, int32_t rotate,
+                              c3h_det* d_out);
 /* Frames per pipeline batch / launch in c3h_run_frames and c3h_stream_frames
  * (1..64, default 32; the fast search path only). */
 int c3h_set_batch(c3h_ctx* ctx, int32_t frames);

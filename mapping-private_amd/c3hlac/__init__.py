@@ -391,6 +391,57 @@ class Context:
             out[f] = raw[f]
         return nm, out
 
+    def run_feature_frames(self, feats, subdivs, canvas, rule=0, exist=None, ranges=(1, 1, 1), exist_threshold=0,
+                           rotate=True, d_out=None, stream=False):
+        """c3h_run_feature_frames (stream=True: c3h_stream_feature_frames; call stream_flush()
+        before reading the last batches): SearchObj::setData + search() from fresh lists for a
+        batch of caller-computed feature rows (VOSCH, ConVOSCH, GRSD, ...).  feats = list of
+        contiguous float32 torch tensors (rows, dim) on this context's device, frame i with
+        subdivs[i] = (xn, yn, zn) of its own rows; canvas = the batch's subdivision canvas
+        (every frame's counts <= it); exist = None (derived by rule: 0 setC3HLAC, 1 setVOSCH /
+        setConVOSCH, 2 setGRSD) or a list of int32 device tensors; d_out = device pointer (int) or
+        tensor of len(feats) * M * rank records.  Returns the number of searched modes."""
+        import torch
+        n = len(feats)
+        if len(subdivs) != n or (exist is not None and len(exist) != n):
+            raise ValueError("run_feature_frames: feats, subdivs and exist must have one entry per frame")
+        sb = np.ascontiguousarray(np.asarray(subdivs, dtype=np.int32).reshape(n, 3))
+        dim = int(feats[0].shape[1]) if n else int(getattr(self, "variant", 0) or 1)
+        ptrs = np.zeros(n, np.uint64)
+        eptrs = None if exist is None else np.zeros(n, np.uint64)
+
+        def on_device(t, what, i, dtype):
+            if not hasattr(t, "data_ptr") or t.dtype != dtype or not t.is_contiguous():
+                raise ValueError("run_feature_frames: %s %d must be a contiguous %s tensor" % (what, i, dtype))
+            if t.device.type != "cuda" or (t.device.index or 0) != self.device:
+                raise ValueError("run_feature_frames: %s %d is on %s, the context on cuda:%d"
+                                 % (what, i, t.device, self.device))
+
+        for i, fr in enumerate(feats):
+            on_device(fr, "frame", i, torch.float32)
+            rows = int(sb[i, 0]) * int(sb[i, 1]) * int(sb[i, 2])
+            if fr.ndim != 2 or fr.shape[1] != dim or fr.shape[0] != rows:
+                raise ValueError("run_feature_frames: frame %d must be (%d, %d), got %s" % (i, rows, dim, tuple(fr.shape)))
+            ptrs[i] = fr.data_ptr()
+            if exist is not None:
+                on_device(exist[i], "exist", i, torch.int32)
+                if exist[i].numel() != rows:
+                    raise ValueError("run_feature_frames: exist %d must hold %d values" % (i, rows))
+                eptrs[i] = exist[i].data_ptr()
+        if d_out is not None and hasattr(d_out, "data_ptr"):
+            need = n * max(self.M, 1) * self.rank * DET_DTYPE.itemsize
+            have = d_out.numel() * d_out.element_size()
+            if have < need or not d_out.is_contiguous() or d_out.device.type != "cuda" or \
+                    (d_out.device.index or 0) != self.device:
+                raise ValueError("run_feature_frames: d_out must be a contiguous tensor of >= %d bytes on cuda:%d"
+                                 % (need, self.device))
+        fn = self.lib.c3h_stream_feature_frames if stream else self.lib.c3h_run_feature_frames
+        nm = self._chk(fn(self.h, ptr(ptrs), ptr(eptrs), n, ptr(sb), i32x3(canvas), dim, int(rule), i32x3(ranges),
+                          int(exist_threshold), int(bool(rotate)), ptr(d_out)), "run_feature_frames")
+        if not stream:  # the context holds the last frame's search state (canvas layout)
+            self._refresh()
+        return nm
+
     def _refresh(self):
         """Re-read the grid / feature state the library holds (after run_frames)."""
         gi = _capi.GridInfo()

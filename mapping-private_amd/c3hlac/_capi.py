@@ -93,6 +93,10 @@ _SIGS = {
     "c3h_stream_frames": (C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_float,
                                     C.POINTER(ExtractParams), C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P]),
     "c3h_stream_flush": (C.c_int, [_P]),
+    "c3h_run_feature_frames": (C.c_int, [_P, _P, _P, C.c_int32, _P, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
+                                         C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P]),
+    "c3h_stream_feature_frames": (C.c_int, [_P, _P, _P, C.c_int32, _P, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
+                                            C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P]),
     "c3h_run_point_frames": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_int32),
                                        C.POINTER(ExtractParams), C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P,
                                        _P]),

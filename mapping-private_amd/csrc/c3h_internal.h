@@ -520,6 +520,28 @@ hipError_t launch_remove_overlap_frames(const RemoveOverlapFrames& a, hipStream_
 
 hipError_t launch_clean_lists(c3h_det* lists, int n, hipStream_t s);
 
+// the front of a batch of caller-computed feature rows (feat_front.hip; c3h_run_feature_frames):
+// frame f's sb[f] subdivisions of `dim` floats, placed at the origin of the canvas cb, become the
+// buffer set's exist values, has-data words, row list and feature rows (frame f at base + f * stride)
+struct FeatFront {
+  const float* feat[kMaxBatch];        // the caller's rows, row h = x + y * xn + z * xn * yn in sb[f]
+  const int32_t* exist_in[kMaxBatch];  // the caller's exist_voxel_num (nullptr: by `rule`)
+  int32_t sb[kMaxBatch][3];
+  int nf, dim, rule;
+  int R;                               // rows per workgroup: fr_block_rows(dim) (feat_rows.h)
+  uint32_t magic;                      // fr_div_magic(dim)
+  int cb[3];
+  float* out;                          // [nf][canvas rows][dim]: written for rows with data only
+  int32_t* exist;                      // [nf][canvas rows]
+  int32_t* has;                        // [nf][canvas rows] 1 = the row holds an element != 0
+  int32_t* rows;                       // [nf][canvas rows] the canvas rows with data, cnt[f] of them
+  uint32_t* cnt;                       // [nf], zeroed in stream order before the launch
+  int32_t* lim;                        // [nf][4] the frame's counts (SparseSearch::lim)
+  int64_t s_out, s_h;
+};
+bool feat_front_ok(int dim);  // a row fits the kernel's LDS stage
+hipError_t launch_feat_front(const FeatFront& a, hipStream_t s);
+
 // one pipeline tick of c3h_run_frames (pipeline.hip): every role nullable
 struct TickParts {
   const C3Launch* occ = nullptr;        // batch t: occupancy stream
@@ -625,6 +647,13 @@ struct c3h_ctx {
   int tf_frames = 0;
   int nframes_feat = 1;             // frames of the last extract (frame 0 = the API view)
   c3h::DevBuf<int32_t> rows;        // non-empty subdivisions of the last extract (direct mode)
+  // feature-row batches (c3h_run_feature_frames) on this buffer set: has-data words, row
+  // counters and gate limits the front kernel writes
+  c3h::DevBuf<int32_t> ff_has, ff_lim;
+  c3h::DevBuf<uint32_t> ff_cnt;
+  // the feature buffer holds a feature-row batch: only rows with data were written (the search
+  // reads those alone), so c3h_get_features / c3h_get_compressed have nothing whole to return
+  bool feat_listed = false;
   bool rows_valid = false;          // rows/epoch describe the current features
   bool g_sparse = false;            // G holds only the listed rows (others stale)
   bool feat_sparse = false;         // feature rows of empty subdivisions are stale (exist == 0)
@@ -722,12 +751,17 @@ struct c3h_ctx {
     c3h::RemoveOverlapFrames ro{};
     bool nosearch = false;        // points-in without subdivisions (S = 0): SearchObj::setData returns
                                   // early, so the batch leaves after its tile role and fixup
+    // feature-row batch (c3h_run_feature_frames): it enters at the compress + gate slot (no
+    // occupancy or tile role); qs is its score role's search, whose `exist` is the has-data array
+    bool rows_in = false;
+    c3h::SparseSearch qs{};
   };
   struct PipeKey {
     int32_t div_b[3], min_b[3];
     float leaf;
     c3h_extract_params p;
     int32_t range[3], thr, rotate, batch, rank, remove_overlap;
+    int32_t rows_in, dim, rule;   // feature-row stream (1), its row length, exist rule (-1: the caller's exist)
     uint64_t setup_version;
   };
   // points-in batches (c3h_run_point_frames).  Per buffer set: the canvas grids of its frame

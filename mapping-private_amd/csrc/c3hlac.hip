@@ -43,6 +43,7 @@
 #include "c3h_internal.h"
 
 #include "c3hlac_dev.h"
+#include "feat_rows.h"
 #include "c3hlac_mfma.h"
 
 namespace c3h {
@@ -920,18 +921,7 @@ hipError_t launch_c3hlac(const C3Launch& l, hipStream_t s) {
 __global__ void exist_rule_kernel(const float* __restrict__ feat, int64_t H, int dim, int rule,
                                   int32_t* __restrict__ exist) {
   for (int64_t h = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; h < H; h += (int64_t)gridDim.x * blockDim.x) {
-    const float* f = feat + h * dim;
-    int32_t e;
-    if (rule == 2) {
-      e = 0;
-      for (int i = 0; i < 20; ++i) e = (int32_t)((float)e + f[i]);
-      e /= 26;
-    } else {
-      const int i0 = rule == 1 ? 20 : 0;
-      const float t = (f[i0] + f[i0 + 1]) * 2.0f;
-      e = (int32_t)((double)t + 0.001);
-    }
-    exist[h] = e;
+    exist[h] = fr_exist_rule(feat + h * dim, rule);  // feat_rows.h: shared with the feature-rows front
   }
 }
 

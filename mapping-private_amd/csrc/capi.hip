@@ -14,6 +14,7 @@
 #include <thread>
 
 #include "c3h_internal.h"
+#include "feat_rows.h"
 #include "occ_sched.h"
 
 using c3h::DevBuf;
@@ -380,6 +381,10 @@ int search_frames(c3h_ctx* ctx, int nf, const int32_t range[3], int32_t thr, int
   if (ctx->feat_dim != ctx->F)
     return fail(ctx, C3H_ERR_ARG, "c3h_search: feature dimension differs from the scene axis");
   if (nf != ctx->nframes_feat) return fail(ctx, C3H_ERR_STATE, "search: frame count differs from the extract");
+  // a feature-frames batch wrote only its rows with data, for its own search
+  if (ctx->feat_listed && !ctx->capture)
+    return fail(ctx, C3H_ERR_STATE, "c3h_search: the rows of a feature-frames batch are not searchable again "
+                                    "(call c3h_set_features or c3h_extract)");
   const int xn = ctx->subdiv_b[0], yn = ctx->subdiv_b[1], zn = ctx->subdiv_b[2];
   const int64_t H = (int64_t)xn * yn * zn;
   if (ctx->lists.M != std::max(ctx->M, 1) || ctx->lists.rank != ctx->rank) init_lists(ctx);
@@ -814,6 +819,9 @@ void c3h_destroy(c3h_ctx* ctx) {
   release(ctx->pb_vlist);
   release(ctx->pb_stage);
   release(ctx->pb_info);
+  release(ctx->ff_has);
+  release(ctx->ff_lim);
+  release(ctx->ff_cnt);
   for (int s = 0; s < C3H_NTIMERS; ++s)
     for (auto& e : ctx->timer.pending[s]) ctx->timer.pool.push_back({e.a, e.b});
   for (auto& e : ctx->timer.pool) {
@@ -862,6 +870,7 @@ int c3h_voxelize(c3h_ctx* ctx, const float* xyzrgb, int64_t n, int on_device, fl
   HIPCHK(hipSetDevice(ctx->device));
   ctx->have_grid = false;
   ctx->have_feat = false;
+  ctx->feat_listed = false;
   ctx->g_valid = false;
   ctx->table_valid = false;
   ctx->vcent_valid = false;
@@ -1283,6 +1292,7 @@ int c3h_set_grid(c3h_ctx* ctx, const uint32_t* words, const int32_t div_b[3],
   ctx->have_grid = true;
   ctx->table_valid = false;
   ctx->have_feat = false;
+  ctx->feat_listed = false;
   ctx->g_valid = false;
   return C3H_OK;
 }
@@ -1308,6 +1318,7 @@ int extract_frames(c3h_ctx* ctx, const uint32_t* const* grids, int nf, const c3h
   if (nf < 1 || nf > c3h::kMaxBatch) return fail(ctx, C3H_ERR_ARG, "extract: bad frame count");
   HIPCHK(hipSetDevice(ctx->device));
   ctx->have_feat = false;
+  ctx->feat_listed = false;
   ctx->g_valid = false;
   ctx->rows_valid = false;
   ctx->exist_gates_rows = true;
@@ -1756,6 +1767,7 @@ int c3h_extract_grsd(c3h_ctx* ctx, const c3h_grsd_params* p, int32_t subdiv_out[
   if (!ctx->have_grid || !ctx->table_valid) return fail(ctx, C3H_ERR_STATE, "extract_grsd: no c3h_voxelize grid");
   HIPCHK(hipSetDevice(ctx->device));
   ctx->have_feat = false;
+  ctx->feat_listed = false;
   ctx->g_valid = false;
   ctx->rows_valid = false;
   ctx->exist_gates_rows = false;
@@ -1847,6 +1859,7 @@ int c3h_set_features(c3h_ctx* ctx, const float* feat, const int32_t subdiv_b[3],
   if (H > 0 && !feat) return C3H_ERR_ARG;
   ctx->feat16_pending = false;  // the caller's rows replace the extract's
   ctx->have_feat = false;
+  ctx->feat_listed = false;
   ctx->g_valid = false;
   ctx->rows_valid = false;
   ctx->exist_gates_rows = false;
@@ -1903,6 +1916,8 @@ int c3h_get_features(c3h_ctx* ctx, float* out, int on_device) {
   if (!ctx || !out) return C3H_ERR_ARG;
   QUIESCE(ctx);
   if (!ctx->have_feat) return fail(ctx, C3H_ERR_STATE, "no features");
+  if (ctx->feat_listed)
+    return fail(ctx, C3H_ERR_STATE, "c3h_get_features: a feature-frames batch keeps only its rows with data");
   HIPCHK(hipSetDevice(ctx->device));
   const size_t n = (size_t)ctx->hist_num * ctx->feat_dim;
   {
@@ -2265,7 +2280,14 @@ struct PipeScope {
 int pipe_tick(c3h_ctx* ctx, const c3h_ctx::PipeBatch* fresh) {
   c3h::TickParts tp;
   tp.prof = &ctx->prof;
-  if (fresh && !fresh->stamped) tp.occ = &fresh->l;
+  // a feature-row batch has no occupancy and no tile role (its front kernel wrote what they
+  // produce): it joins at the compress + gate slot of this very tick
+  const bool rows_in = fresh && fresh->rows_in;
+  if (rows_in) {
+    ctx->pipe.push_back(*fresh);
+    ctx->pipe.back().age = 2;
+  }
+  if (fresh && !fresh->stamped && !rows_in) tp.occ = &fresh->l;
   for (auto& b : ctx->pipe) {
     if (b.age == 1) {
       tp.tile = &b.l;
@@ -2275,7 +2297,7 @@ int pipe_tick(c3h_ctx* ctx, const c3h_ctx::PipeBatch* fresh) {
       tp.gate = &b.q;
       tp.comp = &b.sc;
     }
-    if (b.age == 3) tp.score = &b.q;
+    if (b.age == 3) tp.score = b.rows_in ? &b.qs : &b.q;
   }
   {
     Timed tm(ctx, 5, fresh ? fresh->nf : 0);
@@ -2304,7 +2326,7 @@ int pipe_tick(c3h_ctx* ctx, const c3h_ctx::PipeBatch* fresh) {
       next.push_back(b);
       next.back().age++;
     }
-  if (fresh) {
+  if (fresh && !rows_in) {
     next.push_back(*fresh);
     next.back().age = 1;
     next.back().mapped = tp.occ != nullptr;
@@ -2589,6 +2611,272 @@ int c3h_stream_flush(c3h_ctx* ctx) {
   if (!ctx) return C3H_ERR_ARG;
   HIPCHK(hipSetDevice(ctx->device));
   return pipe_flush(ctx);
+}
+
+}  // extern "C"
+
+namespace {
+
+// ---- feature-rows batches (c3h_run_feature_frames) -------------------------------------
+// A batch of caller-computed rows enters the pipeline at the compress + gate slot: its front
+// kernel (feat_front.hip), one launch ahead of the batch's first tick, writes the buffer set's
+// exist values, has-data words, row list and feature rows on the canvas layout, which is all
+// the tick's later roles read of an extract.
+
+// the buffer set's state and buffers for nb frames of `dim` floats on a canvas of H rows: an
+// extract of nb frames whose non-empty rows are listed
+int feature_set_state(c3h_ctx* ctx, int nb, int64_t H, int dim, const int32_t canvas[3]) {
+  ctx->have_feat = false;
+  ctx->feat16_pending = false;
+  ctx->g_valid = false;
+  ctx->g_sparse = false;
+  ctx->feat_sparse = false;
+  ctx->exist_gates_rows = false;
+  ENSURE(ctx->feat, (size_t)nb * H * dim);
+  ENSURE(ctx->exist, (size_t)nb * H);
+  ENSURE(ctx->rows, (size_t)nb * H);
+  ENSURE(ctx->ff_has, (size_t)nb * H);
+  ENSURE(ctx->ff_cnt, (size_t)c3h::kMaxBatch);
+  ENSURE(ctx->ff_lim, (size_t)c3h::kMaxBatch * 4);
+  ctx->hist_num = H;
+  ctx->feat_dim = dim;
+  for (int a = 0; a < 3; ++a) ctx->subdiv_b[a] = canvas[a];
+  ctx->nframes_feat = nb;
+  ctx->rows_valid = true;
+  ctx->feat_listed = true;
+  ctx->have_feat = true;
+  return C3H_OK;
+}
+
+// Captures nb frames of rows as the next batch on its buffer set and enqueues its front
+// kernel.  Returns as pipe_prepare: > 0 modes searched, 0 when the configuration does not fit
+// the tick (nothing was enqueued), < 0 on error.
+int feature_prepare(c3h_ctx* ctx, const float* const* feats, const int32_t* const* exists,
+                    const int32_t* const* sbs, c3h_det* const* outs, int nb, const c3h_ctx::PipeKey& k,
+                    c3h_ctx::PipeBatch* fresh) {
+  c3h_ctx* c = pipe_set(ctx, ctx->pipe_seq);
+  const int64_t H = (int64_t)k.div_b[0] * k.div_b[1] * k.div_b[2];
+  int rc = feature_set_state(c, nb, H, k.dim, k.div_b);
+  if (rc == C3H_OK) {
+    c->capture = true;
+    c->cap_c3_valid = c->cap_search_valid = false;
+    rc = search_frames(c, nb, k.range, k.thr, k.rotate, outs, 2);
+    c->capture = false;
+  }
+  if (rc < 0) {
+    c->have_feat = false;
+    if (c != ctx) ctx->err = c->err;
+    return rc;
+  }
+  const bool ranked = c->cap_argmax || (c->cap_replay && c->rank >= 2 && !c->cap_q.lists && !c->cap_q.partials);
+  if (!(rc > 0 && c->cap_search_valid && c->cap_sparse_g && ranked)) {  // one geometry per stream
+    c->have_feat = false;
+    if (!ctx->pipe.empty()) return fail(ctx, C3H_ERR_STATE, "pipeline: internal: geometry changed");
+    return 0;
+  }
+  c->nframes_feat = 1;  // slot 0 is the context's view from here on
+  c3h::FeatFront ff{};
+  for (int j = 0; j < nb; ++j) {
+    ff.feat[j] = feats[j];
+    ff.exist_in[j] = exists ? exists[j] : nullptr;
+    for (int a = 0; a < 3; ++a) ff.sb[j][a] = sbs[j][a];
+  }
+  ff.nf = nb;
+  ff.dim = k.dim;
+  ff.rule = k.rule < 0 ? 0 : k.rule;
+  ff.R = c3h::fr_block_rows(k.dim);
+  ff.magic = c3h::fr_div_magic(k.dim);
+  for (int a = 0; a < 3; ++a) ff.cb[a] = k.div_b[a];
+  ff.out = c->feat.p;
+  ff.exist = c->exist.p;
+  ff.has = c->ff_has.p;
+  ff.rows = c->rows.p;
+  ff.cnt = c->ff_cnt.p;
+  ff.lim = c->ff_lim.p;
+  ff.s_out = H * k.dim;
+  ff.s_h = H;
+  // (the set's previous batch left the pipeline two batches ago: stream order covers its reads)
+  HIPCHK(hipMemsetAsync(c->ff_cnt.p, 0, (size_t)c3h::kMaxBatch * sizeof(uint32_t), ctx->stream));
+  {
+    Timed t(ctx, 1, nb);
+    HIPCHK(c3h::launch_feat_front(ff, ctx->stream));
+  }
+  *fresh = c3h_ctx::PipeBatch{c3h::C3Launch{}, c->cap_q, c->cap_sc, nb, 0};
+  fresh->rows_in = true;
+  // the gate role: the true exist values, positions bounded by each frame's own counts
+  fresh->q.lim = c->ff_lim.p;
+  fresh->q.score_engine = ctx->score_engine;
+  // the compress role: the front kernel's list (its counters in place of the extract's)
+  fresh->sc.nrows = c->ff_cnt.p;
+  fresh->sc.s_nrows = 1;
+  // the score role skips rows by the has-data words: exist 0 does not mean an empty row here
+  fresh->qs = fresh->q;
+  fresh->qs.exist = c->ff_has.p;
+  fresh->qs.skip_empty = 1;
+  fresh->set = c;
+  fresh->layout = c->cap_layout;
+  fresh->replay = !c->cap_argmax;
+  fresh->rp = c->cap_rp;
+  fresh->overlap = overlap_wanted(ctx);
+  if (fresh->overlap) fresh->ro = overlap_args(ctx, k.range, outs, nb);
+  return rc;
+}
+
+c3h_ctx::PipeKey feature_key(c3h_ctx* ctx, const int32_t canvas[3], int dim, int rule, const int32_t range[3],
+                             int32_t thr, int32_t rotate, int B) {
+  c3h_ctx::PipeKey k;
+  memset(&k, 0, sizeof(k));  // compared bytewise
+  memcpy(k.div_b, canvas, sizeof(k.div_b));
+  memcpy(k.range, range, sizeof(k.range));
+  k.thr = thr;
+  k.rotate = rotate ? 1 : 0;
+  k.batch = B;
+  k.rank = ctx->rank;
+  k.remove_overlap = ctx->remove_overlap;
+  k.rows_in = 1;
+  k.dim = dim;
+  k.rule = rule;  // -1: the caller's exist arrays
+  k.setup_version = ctx->setup_version;
+  return k;
+}
+
+// nframes through the pipeline in batches of B (as run_frames_pipelined).  Returns > 0 modes
+// searched, 0 when the configuration does not fit the tick (nothing was enqueued), < 0 on error.
+int feature_frames_pipelined(c3h_ctx* ctx, const float* const* d_feat, const int32_t* const* d_exist,
+                             int32_t nframes, const int32_t* subdiv_b, const int32_t canvas[3], int dim,
+                             int rule, const int32_t range[3], int32_t thr, int32_t rotate, c3h_det* d_out,
+                             int B, bool drain) {
+  const size_t per_frame = (size_t)std::max(ctx->M, 1) * ctx->rank;
+  const int nchunks = (nframes + B - 1) / B;
+  int rc = ensure_lanes(ctx, kPipeDepth - 1);
+  if (rc != C3H_OK) return rc;
+  const c3h_ctx::PipeKey k = feature_key(ctx, canvas, dim, d_exist ? -1 : rule, range, thr, rotate, B);
+  if (!ctx->pipe.empty() && memcmp(&k, &ctx->pipe_key, sizeof(k)) != 0) {
+    rc = pipe_flush(ctx);  // a different stream: drain the open one first
+    if (rc != C3H_OK) return rc;
+  }
+  PipeScope scope(ctx);
+  if (drain && ctx->pipe.empty())  // the last batch lands on set 0
+    ctx->pipe_seq = (uint64_t)((kPipeDepth - (nchunks - 1) % kPipeDepth) % kPipeDepth);
+  int nm = 0;
+  for (int ch = 0; ch < nchunks; ++ch) {
+    const float* feats[c3h::kMaxBatch];
+    const int32_t* exists[c3h::kMaxBatch];
+    const int32_t* sbs[c3h::kMaxBatch];
+    c3h_det* outs[c3h::kMaxBatch];
+    const int f0 = ch * B, nb = std::min(B, nframes - f0);
+    for (int j = 0; j < nb; ++j) {  // a draining call's last batch puts its last frame in slot 0
+      const int fi = (drain && ch == nchunks - 1) ? (j == 0 ? f0 + nb - 1 : f0 + j - 1) : f0 + j;
+      feats[j] = d_feat[fi];
+      exists[j] = d_exist ? d_exist[fi] : nullptr;
+      sbs[j] = subdiv_b + 3 * fi;
+      outs[j] = d_out + (size_t)fi * per_frame;
+    }
+    c3h_ctx::PipeBatch fresh{};
+    rc = feature_prepare(ctx, feats, d_exist ? exists : nullptr, sbs, outs, nb, k, &fresh);
+    if (rc > 0) rc = pipe_commit(ctx, fresh, k, rc);
+    if (rc <= 0) {
+      if (rc == 0 && ch == 0) return 0;
+      ctx->pipe.clear();
+      return rc == 0 ? fail(ctx, C3H_ERR_STATE, "pipeline: internal: batch does not fit") : rc;
+    }
+    nm = rc;
+  }
+  if (drain) {
+    while (!ctx->pipe.empty()) {
+      rc = pipe_tick(ctx, nullptr);
+      if (rc != C3H_OK) {
+        ctx->pipe.clear();
+        return rc;
+      }
+    }
+  }
+  return nm;
+}
+
+int feature_frames(c3h_ctx* ctx, const float* const* d_feat, const int32_t* const* d_exist, int32_t nframes,
+                   const int32_t* subdiv_b, const int32_t canvas_b[3], int32_t dim, int32_t exist_rule,
+                   const int32_t range[3], int32_t thr, int32_t rotate, c3h_det* d_out, bool stream) {
+  const char* who = stream ? "c3h_stream_feature_frames" : "c3h_run_feature_frames";
+  if (!ctx || !d_feat || nframes < 0 || (nframes > 0 && !subdiv_b) || !canvas_b || !range || !d_out || dim <= 0)
+    return C3H_ERR_ARG;
+  if (!ctx->have_setup) return fail(ctx, C3H_ERR_STATE, std::string(who) + ": no axes (call c3h_search_setup)");
+  if (!d_exist && (exist_rule < 0 || exist_rule > 2)) return fail(ctx, C3H_ERR_ARG, std::string(who) + ": exist rule");
+  if (!d_exist && dim < c3h::fr_exist_min_dim(exist_rule))
+    return fail(ctx, C3H_ERR_ARG, std::string(who) + ": the exist rule needs more columns (VOSCH 22, GRSD 20, C3-HLAC 2)");
+  if (dim != ctx->F) return fail(ctx, C3H_ERR_ARG, std::string(who) + ": feature dimension differs from the scene axis");
+  if (range[0] < 1 || range[1] < 1 || range[2] < 1) return fail(ctx, C3H_ERR_ARG, std::string(who) + ": ranges must be >= 1");
+  if (int rc = overlap_rank_check(ctx, who)) return rc;
+  int64_t H = 1;
+  for (int a = 0; a < 3; ++a) {
+    if (canvas_b[a] < 0) return fail(ctx, C3H_ERR_ARG, std::string(who) + ": canvas_b");
+    H *= canvas_b[a];
+  }
+  if (H > INT32_MAX) return fail(ctx, C3H_ERR_RANGE, std::string(who) + ": canvas beyond int32 row indices");
+  for (int i = 0; i < nframes; ++i) {
+    int64_t h = 1;
+    for (int a = 0; a < 3; ++a) {
+      const int32_t n = subdiv_b[3 * i + a];
+      if (n < 0 || n > canvas_b[a]) return fail(ctx, C3H_ERR_ARG, std::string(who) + ": a frame's subdiv_b exceeds canvas_b");
+      h *= n;
+    }
+    if (h > 0 && (!d_feat[i] || ((uintptr_t)d_feat[i] & 3) || (d_exist && (!d_exist[i] || ((uintptr_t)d_exist[i] & 3)))))
+      return fail(ctx, C3H_ERR_ARG, std::string(who) + ": frame pointers must be device pointers aligned to 4 bytes");
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!stream) {
+    int rc = pipe_flush(ctx);  // an open stream completes first
+    if (rc != C3H_OK) return rc;
+  }
+  int modes[6];
+  const int nm_sched = mode_schedule(range[0], range[1], range[2], rotate, modes);
+  if (nframes == 0) return stream ? ctx->pipe_nm : 0;
+  const size_t per_frame = (size_t)std::max(ctx->M, 1) * ctx->rank;
+  const int B = std::max(1, std::min(ctx->nbatch, c3h::kMaxBatch));
+  if (H > 0 && pipelinable(ctx) && c3h::feat_front_ok(dim)) {
+    const int rc = feature_frames_pipelined(ctx, d_feat, d_exist, nframes, subdiv_b, canvas_b, dim, exist_rule, range,
+                                            thr, rotate, d_out, B, !stream);
+    if (rc != 0) return rc;
+  }
+  // Routes the tick does not take (c3h_set_pipeline(0), rank > 64, models or axes it has no
+  // role for): frame by frame as a caller would, c3h_set_features + a search from the setRank
+  // state into the frame's slot, in the frame's own layout
+  {
+    int rc = pipe_flush(ctx);
+    if (rc != C3H_OK) return rc;
+  }
+  for (int i = 0; i < nframes; ++i) {
+    c3h_det* out = d_out + (size_t)i * per_frame;
+    int rc = c3h_set_features(ctx, d_feat[i], subdiv_b + 3 * i, dim, d_exist ? d_exist[i] : nullptr, exist_rule, 1);
+    if (rc == C3H_OK) rc = c3h_set_rank(ctx, ctx->rank);
+    if (rc == C3H_OK) rc = c3h_search_async(ctx, range, thr, rotate, out);
+    if (rc >= 0 && overlap_wanted(ctx)) {
+      const hipError_t e = c3h::launch_remove_overlap_frames(overlap_args(ctx, range, &out, 1), ctx->stream);
+      if (e != hipSuccess) rc = hip_fail(ctx, "launch_remove_overlap_frames", e);
+    }
+    if (rc < 0) return rc;
+  }
+  return nm_sched;
+}
+
+}  // namespace
+
+extern "C" {
+
+int c3h_run_feature_frames(c3h_ctx* ctx, const float* const* d_feat, const int32_t* const* d_exist,
+                           int32_t nframes, const int32_t* subdiv_b, const int32_t canvas_b[3], int32_t dim,
+                           int32_t exist_rule, const int32_t range[3], int32_t exist_threshold, int32_t rotate,
+                           c3h_det* d_out) {
+  return feature_frames(ctx, d_feat, d_exist, nframes, subdiv_b, canvas_b, dim, exist_rule, range, exist_threshold,
+                        rotate, d_out, false);
+}
+
+int c3h_stream_feature_frames(c3h_ctx* ctx, const float* const* d_feat, const int32_t* const* d_exist,
+                              int32_t nframes, const int32_t* subdiv_b, const int32_t canvas_b[3], int32_t dim,
+                              int32_t exist_rule, const int32_t range[3], int32_t exist_threshold, int32_t rotate,
+                              c3h_det* d_out) {
+  return feature_frames(ctx, d_feat, d_exist, nframes, subdiv_b, canvas_b, dim, exist_rule, range, exist_threshold,
+                        rotate, d_out, true);
 }
 
 }  // extern "C"
@@ -3015,6 +3303,8 @@ int c3h_get_compressed(c3h_ctx* ctx, float* out, int on_device) {
   if (!ctx || !out) return C3H_ERR_ARG;
   QUIESCE(ctx);
   if (!ctx->g_valid) return fail(ctx, C3H_ERR_STATE, "no compressed features (run a search)");
+  if (ctx->feat_listed)
+    return fail(ctx, C3H_ERR_STATE, "c3h_get_compressed: a feature-frames batch compresses only its rows with data");
   HIPCHK(hipSetDevice(ctx->device));
   if (ctx->D_user != ctx->D) {  // appended zero axes: the caller's D columns of each row
     const int W = ctx->D, Wu = ctx->D_user;
