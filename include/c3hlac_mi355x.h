@@ -376,6 +376,37 @@ int c3h_run_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n
                          int on_device, float leaf, float z_limit, const int32_t canvas[3],
                          const c3h_extract_params* p, const int32_t range[3], int32_t exist_threshold,
                          int32_t rotate, c3h_det* d_out, c3h_frame_info* info);
+/* The same for nframes sensor_msgs/PointCloud2 messages -- the callback of detect_object.cpp from
+ * its first statement, pcl::fromROSMsg(*msg, cloud), on: the batched voxeliser reads the messages'
+ * records in place (no conversion launch, no x y z rgb copy).  One layout per call (a sensor's
+ * messages share it; a caller with several layouts groups its messages): point_step, the byte
+ * offsets of the FLOAT32 fields x, y, z and rgb | rgba (rgb < 0: absent, read as 0) and
+ * is_bigendian, as c3h_voxelize_pointcloud2 takes them.  data[i] = message i's data[]: height[i]
+ * rows of row_step[i] bytes, the last row only width[i] * point_step bytes long; height, width
+ * and row_step are host arrays, data[i] is a device pointer with on_device = 1, else host memory
+ * whose bytes the library stages once per batch.  Every point of a message is a point of its
+ * frame in message order (row-major, NaN points included: limitPoint drops them), at most
+ * 16,777,215 per message.  Everything else means what it means for c3h_run_point_frames, and
+ * frame i's records, c3h_frame_info and status are byte for byte those of c3h_run_point_frames on
+ * the arrays c3h_pointcloud2_to_xyzrgb makes of the same messages, on every route (frames that
+ * leave the batch are converted by that converter, one message at a time).  Little-endian
+ * messages with 16-byte aligned data, point_step and row_step multiples of 16 and field offsets
+ * multiples of 4 (the Kinect / PCL PointXYZRGB record: step 32, rgb at 16) are read with 16-byte
+ * loads, 4-byte aligned ones with one load per field, anything else byte by byte: the same
+ * results, at different rates.  Errors before anything is enqueued, with c3h_voxelize_pointcloud2's
+ * messages: C3H_ERR_ARG (a field outside point_step, row_step < width * point_step),
+ * C3H_ERR_RANGE (too many points). */
+typedef struct {
+  uint32_t point_step;
+  int32_t offsets[4];    /* byte offsets of FLOAT32 x, y, z, rgb|rgba; rgb < 0: absent, read as 0 */
+  int32_t is_bigendian;
+} c3h_pc2_layout;
+int c3h_run_pointcloud2_frames(c3h_ctx* ctx, const void* const* data, const uint32_t* height,
+                               const uint32_t* width, const uint32_t* row_step, int32_t nframes,
+                               const c3h_pc2_layout* layout, int on_device, float leaf, float z_limit,
+                               const int32_t canvas[3], const c3h_extract_params* p,
+                               const int32_t range[3], int32_t exist_threshold, int32_t rotate,
+                               c3h_det* d_out, c3h_frame_info* info);
 /* Feature-rows batch driver: SearchObj(Multi)::setData + search() from fresh lists
  * (color_voxel_recognition/src/search.cpp:539-658) for nframes frames whose features the caller
  * computed elsewhere, as setVOSCH / setConVOSCH / setGRSD of color_voxel_recognition_2 hand

@@ -30,6 +30,19 @@ class PointFrames:
         return len(self.ns)
 
 
+class PointCloud2Frames:
+    """sensor_msgs/PointCloud2 messages validated for c3h_run_pointcloud2_frames
+    (Context.prepare_pointcloud2_frames): one layout, per-message geometry and data pointers,
+    and the device the messages were checked against."""
+
+    def __init__(self, ptrs, height, width, row_step, layout, on_device, keep, device):
+        self.ptrs, self.height, self.width, self.row_step = ptrs, height, width, row_step
+        self.layout, self.on_device, self._keep, self.device = layout, on_device, keep, device
+
+    def __len__(self):
+        return len(self.ptrs)
+
+
 S_MODE = {"S_MODE_%d" % (i + 1): i for i in range(6)}
 # setColor of the estimator (c3h_extract_params.color_mode, include/c3hlac_mi355x.h):
 # C3HLAC with sin/cos in float or in double (the default), or ColorCHLAC's (v, 255 - v)
@@ -367,29 +380,116 @@ class Context:
         if not isinstance(frames, PointFrames):
             frames = self.prepare_point_frames(frames)
         ptrs, ns, on_dev = frames.ptrs, frames.ns, frames.on_device
+        self._check_d_out("run_point_frames", d_out, len(frames))
+        p = self._extract_params(variant, thr, subdiv, offset, color_mode)
+        info = (_capi.FrameInfo * max(len(frames), 1))()
+        nm = self._chk(self.lib.c3h_run_point_frames(self.h, ptr(ptrs), ptr(ns), len(frames), int(on_dev),
+                                                     float(leaf), float(z_limit), i32x3(canvas), C.byref(p),
+                                                     i32x3(ranges), int(exist_threshold), int(bool(rotate)),
+                                                     ptr(d_out), info), "run_point_frames")
+        return nm, self._frame_info(info, len(frames))
+
+    def _check_d_out(self, what, d_out, nframes):
         if d_out is not None and hasattr(d_out, "data_ptr"):
-            need = len(frames) * max(self.M, 1) * self.rank * DET_DTYPE.itemsize
+            need = nframes * max(self.M, 1) * self.rank * DET_DTYPE.itemsize
             have = d_out.numel() * d_out.element_size()
             if have < need or not d_out.is_contiguous() or d_out.device.type != "cuda" or \
                     (d_out.device.index or 0) != self.device:
-                raise ValueError("run_point_frames: d_out must be a contiguous tensor of >= %d bytes on cuda:%d"
-                                 % (need, self.device))
+                raise ValueError("%s: d_out must be a contiguous tensor of >= %d bytes on cuda:%d"
+                                 % (what, need, self.device))
+
+    @staticmethod
+    def _extract_params(variant, thr, subdiv, offset, color_mode):
         p = _capi.ExtractParams()
         p.variant = int(variant)
         p.thr = (C.c_int32 * 3)(*[int(t) for t in thr])
         p.subdiv = int(subdiv)
         p.offset = (C.c_int32 * 3)(*[int(o) for o in offset])
         p.color_mode = int(color_mode)
-        info = (_capi.FrameInfo * max(len(frames), 1))()
-        nm = self._chk(self.lib.c3h_run_point_frames(self.h, ptr(ptrs), ptr(ns), len(frames), int(on_dev),
-                                                     float(leaf), float(z_limit), i32x3(canvas), C.byref(p),
-                                                     i32x3(ranges), int(exist_threshold), int(bool(rotate)),
-                                                     ptr(d_out), info), "run_point_frames")
-        raw = np.frombuffer(info, _FRAME_INFO_C, count=len(frames))
-        out = np.zeros(len(frames), FRAME_INFO_DTYPE)
+        return p
+
+    @staticmethod
+    def _frame_info(info, nframes):
+        raw = np.frombuffer(info, _FRAME_INFO_C, count=nframes)
+        out = np.zeros(nframes, FRAME_INFO_DTYPE)
         for f in FRAME_INFO_DTYPE.names:
             out[f] = raw[f]
-        return nm, out
+        return out
+
+    def prepare_pointcloud2_frames(self, msgs):
+        """Validates a list of sensor_msgs/PointCloud2 messages for run_pointcloud2_frames once.
+        Each message is the dict voxelize_pointcloud2 takes ({height, width, point_step, row_step,
+        is_bigendian, fields: {name: offset}, data}); data are all host bytes / bytearrays / uint8
+        numpy arrays, or all contiguous uint8 torch tensors on this context's device.  One call
+        takes one layout -- point_step, the offsets of x, y, z and rgb | rgba (a missing rgb is a
+        layout too) and is_bigendian -- so messages with different layouts raise ValueError: group
+        them by sensor.  Returns a PointCloud2Frames (the arrays the C-ABI takes, references that
+        keep the messages alive, and the device it was checked against)."""
+        def layout_of(m):
+            f = m["fields"]
+            return (int(m["point_step"]), int(f["x"]), int(f["y"]), int(f["z"]),
+                    int(f.get("rgb", f.get("rgba", -1))), int(bool(m.get("is_bigendian", 0))))
+
+        n = len(msgs)
+        on_dev = hasattr(msgs[0]["data"], "data_ptr") if n else False
+        layout = layout_of(msgs[0]) if n else (16, 0, 4, 8, 12, 0)
+        keep = []
+        ptrs = np.zeros(n, np.uint64)
+        height, width, row_step = (np.zeros(n, np.uint32) for _ in range(3))
+        for i, m in enumerate(msgs):
+            if layout_of(m) != layout:
+                raise ValueError("run_pointcloud2_frames: message %d has another layout %r than message 0 %r "
+                                 "(point_step, x, y, z, rgb, is_bigendian): one call takes one layout"
+                                 % (i, layout_of(m), layout))
+            data = m["data"]
+            if hasattr(data, "data_ptr") != on_dev:
+                raise ValueError("run_pointcloud2_frames: message %d: all host data or all device tensors" % i)
+            if on_dev:
+                import torch
+                if data.dtype != torch.uint8 or not data.is_contiguous():
+                    raise ValueError("run_pointcloud2_frames: message %d data must be a contiguous uint8 tensor" % i)
+                if data.device.type != "cuda" or (data.device.index or 0) != self.device:
+                    raise ValueError("run_pointcloud2_frames: message %d is on %s, the context on cuda:%d"
+                                     % (i, data.device, self.device))
+                have = data.numel()
+                ptrs[i] = data.data_ptr()
+            else:
+                if isinstance(data, (bytes, bytearray, memoryview)):
+                    data = np.frombuffer(data, np.uint8)
+                if not isinstance(data, np.ndarray) or data.dtype != np.uint8:
+                    raise ValueError("run_pointcloud2_frames: message %d data must be bytes or a uint8 array" % i)
+                data = np.ascontiguousarray(data)
+                have = data.size
+                ptrs[i] = data.ctypes.data
+            keep.append(data)
+            height[i], width[i], row_step[i] = int(m["height"]), int(m["width"]), int(m["row_step"])
+            h, w = int(height[i]), int(width[i])
+            need = ((h - 1) * int(row_step[i]) if h > 1 else 0) + w * layout[0] if h * w else 0
+            if have < need:
+                raise ValueError("run_pointcloud2_frames: message %d holds %d bytes, its geometry needs %d"
+                                 % (i, have, need))
+        lay = _capi.Pc2Layout(layout[0], (C.c_int32 * 4)(*layout[1:5]), layout[5])
+        return PointCloud2Frames(ptrs, height, width, row_step, lay, on_dev, keep, self.device)
+
+    def run_pointcloud2_frames(self, msgs, leaf, canvas, variant, thr, subdiv, ranges, exist_threshold, rotate=True,
+                               d_out=None, z_limit=float("inf"), offset=(0, 0, 0), color_mode=COLOR_C3_DOUBLE):
+        """c3h_run_pointcloud2_frames: run_point_frames for a list of sensor_msgs/PointCloud2
+        messages (see prepare_pointcloud2_frames) or a PointCloud2Frames; the batched voxeliser
+        reads the messages in place.  Same results, frame info and statuses as run_point_frames on
+        the x y z rgb arrays c3h_pointcloud2_to_xyzrgb makes of the messages."""
+        if not isinstance(msgs, PointCloud2Frames):
+            msgs = self.prepare_pointcloud2_frames(msgs)
+        if msgs.device != self.device:
+            raise ValueError("run_pointcloud2_frames: the messages were prepared for cuda:%d, the context is on cuda:%d"
+                             % (msgs.device, self.device))
+        self._check_d_out("run_pointcloud2_frames", d_out, len(msgs))
+        p = self._extract_params(variant, thr, subdiv, offset, color_mode)
+        info = (_capi.FrameInfo * max(len(msgs), 1))()
+        nm = self._chk(self.lib.c3h_run_pointcloud2_frames(
+            self.h, ptr(msgs.ptrs), ptr(msgs.height), ptr(msgs.width), ptr(msgs.row_step), len(msgs),
+            C.byref(msgs.layout), int(msgs.on_device), float(leaf), float(z_limit), i32x3(canvas), C.byref(p),
+            i32x3(ranges), int(exist_threshold), int(bool(rotate)), ptr(d_out), info), "run_pointcloud2_frames")
+        return nm, self._frame_info(info, len(msgs))
 
     def run_feature_frames(self, feats, subdivs, canvas, rule=0, exist=None, ranges=(1, 1, 1), exist_threshold=0,
                            rotate=True, d_out=None, stream=False):
@@ -504,6 +604,26 @@ class Context:
         cnt = np.zeros(_capi.NTIMERS, np.int32)
         self._chk(self.lib.c3h_kernel_times(self.h, ptr(ms), ptr(cnt), int(bool(reset))), "kernel_times")
         return {n: (float(ms[i]), int(cnt[i])) for i, n in enumerate(TIMER_NAMES)}
+
+
+def pointcloud2_to_xyzrgb(msg, out=None, stream=None):
+    """c3h_pointcloud2_to_xyzrgb: the conversion of one sensor_msgs/PointCloud2 message (the dict
+    voxelize_pointcloud2 takes, data a uint8 device tensor) into an (n, 4) float32 device tensor,
+    device to device on a HIP stream handle (None: torch's current stream)."""
+    import torch
+    f = msg["fields"]
+    off = (C.c_int32 * 4)(f["x"], f["y"], f["z"], f.get("rgb", f.get("rgba", -1)))
+    data = msg["data"]
+    n = int(msg["height"]) * int(msg["width"])
+    if out is None:
+        out = torch.empty((n, 4), dtype=torch.float32, device=data.device)
+    if stream is None:
+        stream = torch.cuda.current_stream(data.device).cuda_stream
+    rc = _capi.load().c3h_pointcloud2_to_xyzrgb(ptr(data), msg["height"], msg["width"], msg["point_step"],
+                                                msg["row_step"], off, int(bool(msg.get("is_bigendian", 0))), ptr(out),
+                                                C.c_void_p(stream))
+    check(rc, None, "pointcloud2_to_xyzrgb")
+    return out
 
 
 def auto_threshold(hist):

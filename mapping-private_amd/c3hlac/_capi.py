@@ -50,6 +50,10 @@ class FrameInfo(C.Structure):
                 ("n_occ", C.c_int64)]
 
 
+class Pc2Layout(C.Structure):
+    _fields_ = [("point_step", C.c_uint32), ("offsets", C.c_int32 * 4), ("is_bigendian", C.c_int32)]
+
+
 DET_DTYPE = np.dtype([("score", "<f8"), ("x", "<i4"), ("y", "<i4"), ("z", "<i4"), ("mode", "<i4")])
 assert DET_DTYPE.itemsize == C.sizeof(Det)
 
@@ -100,6 +104,9 @@ _SIGS = {
     "c3h_run_point_frames": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_int32),
                                        C.POINTER(ExtractParams), C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P,
                                        _P]),
+    "c3h_run_pointcloud2_frames": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.POINTER(Pc2Layout), C.c_int, C.c_float,
+                                             C.c_float, C.POINTER(C.c_int32), C.POINTER(ExtractParams),
+                                             C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P, _P]),
     "c3h_set_lanes": (C.c_int, [_P, C.c_int32]),
     "c3h_set_batch": (C.c_int, [_P, C.c_int32]),
     "c3h_set_pipeline": (C.c_int, [_P, C.c_int32]),

@@ -11,6 +11,7 @@
 
 #include "../../include/c3hlac_mi355x.h"
 #include "occ_sched.h"
+#include "pc2_layout.h"
 
 namespace c3h {
 
@@ -243,7 +244,17 @@ struct VoxBatchArgs {
   uint32_t* bucket;                   // [nf][kVbBucketCap] point indices
   VoxMoved* moved;                    // [nf][kVbMovedCap]
   uint32_t* xcnt;                     // [nf][4]: flags, bucket words, moved, - (zeroed by voxb_reduce)
+  // where the points are read from (appended: the fields above keep their kernel-argument
+  // offsets).  src 0: pts[f] = n[f] packed x y z rgb float4 records.  src 1: pts[f] = data[0]
+  // of a sensor_msgs/PointCloud2 message of n[f] = height * width points, read in place by
+  // the call's plan (pc2_layout.h) with the frame's width, row step and row reciprocal
+  int src;
+  Pc2Plan pc2;
+  uint32_t pc2_width[kMaxBatch], pc2_row_step[kMaxBatch], pc2_magic[kMaxBatch];
+  uint8_t pc2_shift[kMaxBatch];
 };
+// by value in the kernel arguments (4 KB with voxb_bucket's item count behind it): 3,192 B at 64 frames
+static_assert(sizeof(VoxBatchArgs) + 16 <= 4096, "VoxBatchArgs: the kernel-argument limit");
 int vb_chunk();  // points per accumulate block
 // The off-cell correction of a points-in batch, run after the tick that ran the batch's
 // tile role and before the one that compresses it: every subdivision holding a voxel the
@@ -783,6 +794,7 @@ struct c3h_ctx {
   int64_t pb_acc_vox = 0;
   int pb_acc_slots = 0;
   c3h::DevBuf<float> pb_stage;
+  c3h::DevBuf<uint8_t> pb_raw;      // host PointCloud2 messages of a batch (c3h_run_pointcloud2_frames)
   c3h::DevBuf<c3h::VoxFrameRec> pb_info;
   // the batched voxeliser runs on its own stream, one batch ahead of the tick that consumes
   // it (events: a batch's voxels are done / the tick that last read a buffer set is done)

@@ -818,6 +818,7 @@ void c3h_destroy(c3h_ctx* ctx) {
   release(ctx->pb_fcnt);
   release(ctx->pb_vlist);
   release(ctx->pb_stage);
+  release(ctx->pb_raw);
   release(ctx->pb_info);
   release(ctx->ff_has);
   release(ctx->ff_lim);
@@ -2915,33 +2916,68 @@ int point_frame_single(c3h_ctx* ctx, const float* pts, int64_t n, int on_device,
   return rc < 0 ? rc : C3H_OK;
 }
 
-}  // namespace
+// Where the frames of a points-in call come from: packed x y z rgb float arrays
+// (c3h_run_point_frames) or sensor_msgs/PointCloud2 messages the batched voxeliser reads in
+// place (c3h_run_pointcloud2_frames: layout != nullptr).  base[i] is frame i's pts[i] or
+// data[i], n[i] its points.
+struct PointSrc {
+  std::string who;
+  const void* const* base = nullptr;
+  const int64_t* n = nullptr;
+  int32_t nframes = 0;
+  int on_device = 0;
+  const c3h_pc2_layout* layout = nullptr;
+  const uint32_t *height = nullptr, *width = nullptr, *row_step = nullptr;
+  c3h::Pc2Plan plan{};
+  // the bytes of frame i (what a host frame's staging copy moves)
+  size_t bytes(int i) const {
+    return layout ? (size_t)c3h::pc2_msg_bytes(height[i], width[i], layout->point_step, row_step[i]) : (size_t)n[i] * 16;
+  }
+  // the batch's staging buffer: frames follow each other at 16-byte aligned offsets
+  static size_t staged(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+};
 
-extern "C" {
+// Frame i on the single-frame path.  A message is converted by the single-frame path's own
+// converter into the context's point buffer first (c3h_voxelize_pointcloud2's steps).
+int point_src_single(c3h_ctx* ctx, const PointSrc& s, int i, float leaf, float z_limit, const c3h_extract_params* p,
+                     const int32_t range[3], int32_t thr, int32_t rotate, c3h_det* d_out_f, c3h_frame_info* fi) {
+  if (!s.layout)
+    return point_frame_single(ctx, static_cast<const float*>(s.base[i]), s.n[i], s.on_device, leaf, z_limit, p, range,
+                              thr, rotate, d_out_f, fi);
+  const void* msg = s.base[i];
+  const size_t bytes = s.bytes(i);
+  if (bytes > 0 && !s.on_device) {
+    ENSURE(ctx->raw, (bytes + 3) / 4);
+    HIPCHK(hipMemcpyAsync(ctx->raw.p, msg, bytes, hipMemcpyHostToDevice, ctx->stream));
+    msg = ctx->raw.p;
+  }
+  ENSURE(ctx->pts, (size_t)std::max<int64_t>(s.n[i], 1) * 4);
+  const uint32_t ps = s.layout->point_step;
+  HIPCHK(c3h::launch_pc2_convert(msg, s.height[i], s.width[i], ps, s.height[i] > 1 ? s.row_step[i] : s.width[i] * ps,
+                                 s.layout->offsets, s.layout->is_bigendian ? 1 : 0, ctx->pts.p, ctx->stream));
+  return point_frame_single(ctx, ctx->pts.p, s.n[i], 1, leaf, z_limit, p, range, thr, rotate, d_out_f, fi);
+}
 
 // Points-in batches: the scatter stamps the tick's tiles (a canvas that does not match the
 // grid: the tick streams the canvases), and flagged voxels are summed exactly and off-cell
-// voxels fixed up in the batch.
-
-int c3h_run_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t nframes, int on_device,
-                         float leaf, float z_limit, const int32_t canvas[3], const c3h_extract_params* p,
-                         const int32_t range[3], int32_t exist_threshold, int32_t rotate, c3h_det* d_out,
-                         c3h_frame_info* info) {
-  if (!ctx || !pts || !n || nframes < 0 || !canvas || !p || !range || !d_out || !(leaf > 0)) return C3H_ERR_ARG;
-  if (!ctx->have_setup) return fail(ctx, C3H_ERR_STATE, "c3h_run_point_frames: no axes (call c3h_search_setup)");
-  for (int i = 0; i < nframes; ++i)
-    if (n[i] < 0 || (n[i] > 0 && !pts[i]) || n[i] >= ((int64_t)1 << 24))
-      return fail(ctx, C3H_ERR_ARG, "c3h_run_point_frames: frame point counts must be in [0, 16,777,215]");
-  if (p->variant != 981 && p->variant != 117) return fail(ctx, C3H_ERR_ARG, "c3h_run_point_frames: variant");
+// voxels fixed up in the batch.  The body of both points-in entry points.
+int run_point_source(c3h_ctx* ctx, const PointSrc& src, float leaf, float z_limit, const int32_t canvas[3],
+                     const c3h_extract_params* p, const int32_t range[3], int32_t exist_threshold, int32_t rotate,
+                     c3h_det* d_out, c3h_frame_info* info) {
+  const int32_t nframes = src.nframes;
+  const int on_device = src.on_device;
+  const int64_t* n = src.n;
+  const std::string& who = src.who;
+  if (p->variant != 981 && p->variant != 117) return fail(ctx, C3H_ERR_ARG, who + ": variant");
   if (p->color_mode < C3H_COLOR_C3_FLOAT || p->color_mode > C3H_COLOR_CHLAC)
-    return fail(ctx, C3H_ERR_ARG, "c3h_run_point_frames: color_mode");
-  if (int rc = overlap_rank_check(ctx, "c3h_run_point_frames")) return rc;
+    return fail(ctx, C3H_ERR_ARG, who + ": color_mode");
+  if (int rc = overlap_rank_check(ctx, who.c_str())) return rc;
   int64_t cvox = 1;
   for (int a = 0; a < 3; ++a) {
-    if (canvas[a] < 1) return fail(ctx, C3H_ERR_ARG, "c3h_run_point_frames: canvas dims must be >= 1");
+    if (canvas[a] < 1) return fail(ctx, C3H_ERR_ARG, who + ": canvas dims must be >= 1");
     cvox *= canvas[a];
   }
-  if (cvox > 2147483647LL) return fail(ctx, C3H_ERR_RANGE, "c3h_run_point_frames: canvas beyond int32 voxel indices");
+  if (cvox > 2147483647LL) return fail(ctx, C3H_ERR_RANGE, who + ": canvas beyond int32 voxel indices");
   HIPCHK(hipSetDevice(ctx->device));
   {
     int rc = pipe_flush(ctx);  // an open frame stream completes first
@@ -2982,7 +3018,7 @@ int c3h_run_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n
       while ((1 << tb[a]) < canvas[a]) ++tb[a];
       tvox <<= tb[a];
     }
-    if (tvox > ((int64_t)1 << 31)) return fail(ctx, C3H_ERR_RANGE, "c3h_run_point_frames: canvas too large");
+    if (tvox > ((int64_t)1 << 31)) return fail(ctx, C3H_ERR_RANGE, who + ": canvas too large");
     if (ctx->pb_acc_vox != tvox || ctx->pb_acc_slots < B) {
       ENSURE(ctx->pb_acc, (size_t)B * tvox);
       ENSURE(ctx->pb_accM, (size_t)B * tvox);
@@ -2997,19 +3033,24 @@ int c3h_run_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n
     // shared buffers sized for the largest batch up front: the voxeliser stream may still be
     // reading them while the next batch is prepared
     {
-      int64_t max_blk = 1, max_pts = 1;
+      int64_t max_blk = 1;
+      size_t max_bytes = 16;
       for (int ch = 0; ch < nchunks; ++ch) {
-        int64_t b = 0, q = 0;
+        int64_t b = 0;
+        size_t q = 0;
         for (int j = ch * B; j < std::min(nframes, (ch + 1) * B); ++j) {
           b += std::max<int64_t>(1, (n[j] + chunk - 1) / chunk);
-          q += n[j];
+          q += PointSrc::staged(src.bytes(j));
         }
         max_blk = std::max(max_blk, b);
-        max_pts = std::max(max_pts, q);
+        max_bytes = std::max(max_bytes, q);
       }
-      if (max_blk > INT_MAX / chunk) return fail(ctx, C3H_ERR_RANGE, "c3h_run_point_frames: batch too large");
+      if (max_blk > INT_MAX / chunk) return fail(ctx, C3H_ERR_RANGE, who + ": batch too large");
       ENSURE(ctx->pb_vlist, (size_t)max_blk * chunk);
-      if (!on_device) ENSURE(ctx->pb_stage, (size_t)max_pts * 4);
+      if (!on_device) {  // the messages' raw bytes have a byte buffer of their own
+        if (src.layout) ENSURE(ctx->pb_raw, max_bytes);
+        else ENSURE(ctx->pb_stage, max_bytes / 4);
+      }
     }
     if (!ctx->pb_vstream) {
       // the voxeliser's stream is the points-in call's critical path (its accumulate runs
@@ -3082,15 +3123,27 @@ int c3h_run_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n
       for (int j = 0; j <= c3h::kMaxBatch; ++j)
         va.prev_blk0[j] = j < (int)c->pb_prev_blk0.size() ? c->pb_prev_blk0[j] : va.prev_total;
       if (on_device) {
-        for (int j = 0; j < nb; ++j) va.pts[j] = reinterpret_cast<const float4*>(pts[f0 + j]);
+        for (int j = 0; j < nb; ++j) va.pts[j] = static_cast<const float4*>(src.base[f0 + j]);
       } else {  // host frames: one staging copy per batch, ordered on the voxeliser stream
-        int64_t o = 0;
+        uint8_t* stage = src.layout ? ctx->pb_raw.p : reinterpret_cast<uint8_t*>(ctx->pb_stage.p);
+        size_t o = 0;
         for (int j = 0; j < nb; ++j) {
-          va.pts[j] = reinterpret_cast<const float4*>(ctx->pb_stage.p + 4 * o);
-          if (n[f0 + j] > 0)
-            HIPCHK(hipMemcpyAsync(ctx->pb_stage.p + 4 * o, pts[f0 + j], (size_t)n[f0 + j] * 16,
-                                  hipMemcpyHostToDevice, vs));
-          o += n[f0 + j];
+          va.pts[j] = reinterpret_cast<const float4*>(stage + o);
+          const size_t bytes = src.bytes(f0 + j);
+          if (bytes > 0) HIPCHK(hipMemcpyAsync(stage + o, src.base[f0 + j], bytes, hipMemcpyHostToDevice, vs));
+          o += PointSrc::staged(bytes);
+        }
+      }
+      if (src.layout) {  // the voxeliser reads the messages in place
+        va.src = 1;
+        va.pc2 = src.plan;
+        for (int j = 0; j < nb; ++j) {
+          const c3h::Pc2Frame fr =
+              c3h::pc2_frame(src.height[f0 + j], src.width[f0 + j], src.layout->point_step, src.row_step[f0 + j]);
+          va.pc2_width[j] = fr.width;
+          va.pc2_row_step[j] = fr.row_step;
+          va.pc2_magic[j] = fr.magic;
+          va.pc2_shift[j] = (uint8_t)fr.shift;
         }
       }
       va.inv = 1.0f / leaf;
@@ -3114,7 +3167,7 @@ int c3h_run_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n
       for (int j = 0; j < c3h::kMaxBatch; ++j)
         va.grid[j] = j < c->pb_slots ? c->pb_grid.p + (size_t)j * cvox : nullptr;
       if (va.prev_nf > c->pb_slots || va.nf > c->pb_slots)
-        return fail(ctx, C3H_ERR_STATE, "c3h_run_point_frames: internal: frame slots");
+        return fail(ctx, C3H_ERR_STATE, who + ": internal: frame slots");
       va.info = ctx->pb_info.p + f0;
       va.lim = c->pb_lim.p;
       const uint32_t* grids[c3h::kMaxBatch];
@@ -3148,7 +3201,7 @@ int c3h_run_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n
       c3h_ctx::PipeBatch fresh{};
       const int h2d0 = c->cap_h2d;
       rc = pipe_prepare(ctx, grids, outs, nb, k, c->pb_lim.p, &fresh);
-      if (rc == 0) rc = fail(ctx, C3H_ERR_STATE, "c3h_run_point_frames: the canvas does not fit the pipeline");
+      if (rc == 0) rc = fail(ctx, C3H_ERR_STATE, who + ": the canvas does not fit the pipeline");
       if (rc < 0) break;
       const c3h::C3Launch& cl = fresh.l;
       va.stamp = (cl.gx == canvas[0] && cl.gy == canvas[1] && cl.gz == canvas[2] &&
@@ -3279,8 +3332,8 @@ int c3h_run_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n
   }
   for (int i = 0; i < nframes; ++i) {
     if (!redo[i]) continue;
-    int rc = point_frame_single(ctx, pts[i], n[i], on_device, leaf, z_limit, p, range, exist_threshold, rotate,
-                                d_out + (size_t)i * per_frame, &fi[i]);
+    int rc = point_src_single(ctx, src, i, leaf, z_limit, p, range, exist_threshold, rotate,
+                              d_out + (size_t)i * per_frame, &fi[i]);
     if (rc == C3H_ERR_HIP || rc == C3H_ERR_NOMEM) return rc;  // device trouble ends the call
   }
   if (!batched) {  // the modes the search schedules (search.cpp:384-417)
@@ -3290,6 +3343,66 @@ int c3h_run_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (info) memcpy(info, fi.data(), fi.size() * sizeof(c3h_frame_info));
   return nm;
+}
+
+}  // namespace
+
+extern "C" {
+
+int c3h_run_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t nframes, int on_device,
+                         float leaf, float z_limit, const int32_t canvas[3], const c3h_extract_params* p,
+                         const int32_t range[3], int32_t exist_threshold, int32_t rotate, c3h_det* d_out,
+                         c3h_frame_info* info) {
+  if (!ctx || !pts || !n || nframes < 0 || !canvas || !p || !range || !d_out || !(leaf > 0)) return C3H_ERR_ARG;
+  if (!ctx->have_setup) return fail(ctx, C3H_ERR_STATE, "c3h_run_point_frames: no axes (call c3h_search_setup)");
+  for (int i = 0; i < nframes; ++i)
+    if (n[i] < 0 || (n[i] > 0 && !pts[i]) || n[i] >= ((int64_t)1 << 24))
+      return fail(ctx, C3H_ERR_ARG, "c3h_run_point_frames: frame point counts must be in [0, 16,777,215]");
+  PointSrc src;
+  src.who = "c3h_run_point_frames";
+  src.base = reinterpret_cast<const void* const*>(pts);
+  src.n = n;
+  src.nframes = nframes;
+  src.on_device = on_device;
+  return run_point_source(ctx, src, leaf, z_limit, canvas, p, range, exist_threshold, rotate, d_out, info);
+}
+
+int c3h_run_pointcloud2_frames(c3h_ctx* ctx, const void* const* data, const uint32_t* height, const uint32_t* width,
+                               const uint32_t* row_step, int32_t nframes, const c3h_pc2_layout* layout, int on_device,
+                               float leaf, float z_limit, const int32_t canvas[3], const c3h_extract_params* p,
+                               const int32_t range[3], int32_t exist_threshold, int32_t rotate, c3h_det* d_out,
+                               c3h_frame_info* info) {
+  if (!ctx || nframes < 0 || (nframes > 0 && (!data || !height || !width || !row_step)) || !layout || !canvas || !p ||
+      !range || !d_out || !(leaf > 0))
+    return C3H_ERR_ARG;
+  if (!ctx->have_setup) return fail(ctx, C3H_ERR_STATE, "c3h_run_pointcloud2_frames: no axes (call c3h_search_setup)");
+  std::vector<int64_t> n((size_t)nframes);
+  uint64_t base_or = 0;
+  uint32_t row_step_or = 0;
+  for (int i = 0; i < nframes; ++i) {
+    int rc = pc2_check(ctx, height[i], width[i], layout->point_step, row_step[i], layout->offsets);
+    if (rc != C3H_OK) return rc;
+    n[i] = (int64_t)height[i] * width[i];
+    if (n[i] > 0 && !data[i]) return fail(ctx, C3H_ERR_ARG, "pointcloud2: no data");
+    if (n[i] >= (int64_t)1 << 24)
+      return fail(ctx, C3H_ERR_RANGE, "c3h_run_pointcloud2_frames: at most 16,777,215 points per message");
+    if (n[i] == 0) continue;
+    // host messages are staged at 16-byte aligned addresses
+    if (on_device) base_or |= (uint64_t)(uintptr_t)data[i];
+    if (!c3h::pc2_flat(height[i], width[i], layout->point_step, row_step[i])) row_step_or |= row_step[i];
+  }
+  PointSrc src;
+  src.who = "c3h_run_pointcloud2_frames";
+  src.base = data;
+  src.n = n.data();
+  src.nframes = nframes;
+  src.on_device = on_device;
+  src.layout = layout;
+  src.height = height;
+  src.width = width;
+  src.row_step = row_step;
+  src.plan = c3h::pc2_plan(layout->point_step, layout->offsets, layout->is_bigendian, base_or, row_step_or);
+  return run_point_source(ctx, src, leaf, z_limit, canvas, p, range, exist_threshold, rotate, d_out, info);
 }
 
 int c3h_set_pipeline(c3h_ctx* ctx, int32_t enable) {

@@ -45,6 +45,7 @@
 // their C3-HLAC contribution, c3hlac.hip offcell_delta_kernel).
 #include <algorithm>
 #include <climits>
+#include <type_traits>
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -926,7 +927,82 @@ __device__ __forceinline__ int vb_frame(const int* blk0, int nf, int b) {
   return lo;
 }
 
+// ---- where a frame's points come from: the fetch policy of voxb_accum / voxb_bucket /
+// voxb_exact.  load_nt + point: a round's loads issued together (streamed, non-temporal), the
+// records turned into points where they are used; get: one point by index (the exact pass).
+// PtsXyzrgb: packed x y z rgb float4 records (c3h_run_point_frames).
+struct PtsXyzrgb {
+  static constexpr int kRound = kBRound;
+  using Raw = float4;
+  const float4* __restrict__ pts;
+  __device__ __forceinline__ PtsXyzrgb(const VoxBatchArgs& a, int f) : pts(a.pts[f]) {}
+  __device__ __forceinline__ Raw load_nt(int64_t i) const {
+    const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(pts) + i);
+    return make_float4(v.x, v.y, v.z, v.w);
+  }
+  static __device__ __forceinline__ Raw none() { return make_float4(NAN, NAN, NAN, 0.0f); }
+  __device__ __forceinline__ const float4& point(const Raw& v) const { return v; }
+  template <class I>
+  __device__ __forceinline__ const float4& get(I i) const {
+    return pts[i];
+  }
+};
 
+// PtsPc2: the records of a sensor_msgs/PointCloud2 message read in place
+// (c3h_run_pointcloud2_frames; forms, offsets and extraction: pc2_layout.h)
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+template <bool kNT>
+struct Pc2Mem {
+  const uint8_t* __restrict__ p;
+  __device__ __forceinline__ void ld16(uint64_t o, uint32_t* out) const {
+    const u32x4* q = reinterpret_cast<const u32x4*>(p + o);
+    const u32x4 v = kNT ? __builtin_nontemporal_load(q) : *q;
+    out[0] = v.x;
+    out[1] = v.y;
+    out[2] = v.z;
+    out[3] = v.w;
+  }
+  __device__ __forceinline__ uint32_t ld4(uint64_t o) const {
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(p + o);
+    return kNT ? __builtin_nontemporal_load(q) : *q;
+  }
+  __device__ __forceinline__ uint32_t ld1(uint64_t o) const { return kNT ? __builtin_nontemporal_load(p + o) : p[o]; }
+};
+#ifndef C3H_VB_PC2_ROUND
+#define C3H_VB_PC2_ROUND 4  // points per round of a two-piece VEC16 record (8 loads in flight, as PtsXyzrgb)
+#endif
+template <int kForm, int kNP>
+struct PtsPc2 {
+  static constexpr int kRound = (kForm == kPc2Vec16 && kNP == 2) ? (kBRound < C3H_VB_PC2_ROUND ? kBRound : C3H_VB_PC2_ROUND)
+                                                                  : kBRound;
+  using Raw = Pc2Raw<kForm, kNP>;
+  const uint8_t* __restrict__ data;
+  const Pc2Plan L;
+  Pc2Frame fr;
+  __device__ __forceinline__ PtsPc2(const VoxBatchArgs& a, int f)
+      : data(reinterpret_cast<const uint8_t*>(a.pts[f])), L(a.pc2),
+        fr{a.pc2_width[f], a.pc2_row_step[f], a.pc2_magic[f], a.pc2_shift[f]} {}
+  __device__ __forceinline__ Raw load_nt(int64_t i) const {
+    return pc2_load<kForm, kNP>(Pc2Mem<true>{data}, pc2_offset((uint32_t)i, fr, L.point_step), L);
+  }
+  static __device__ __forceinline__ Raw none() {
+    Raw r;
+#pragma unroll
+    for (int k = 0; k < (int)(sizeof(r.w) / 4); ++k) r.w[k] = 0x7fc00000u;  // every field a NaN: no valid point
+    return r;
+  }
+  __device__ __forceinline__ float4 point(const Raw& r) const {
+    uint32_t w[4];
+    pc2_extract<kForm, kNP>(r, L, w);
+    return make_float4(__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2]), __uint_as_float(w[3]));
+  }
+  template <class I>
+  __device__ __forceinline__ float4 get(I i) const {
+    return point(pc2_load<kForm, kNP>(Pc2Mem<false>{data}, pc2_offset((uint32_t)i, fr, L.point_step), L));
+  }
+};
+
+template <class Pts>
 __global__ __launch_bounds__(kBT) void voxb_accum_kernel(VoxBatchArgs a) {
   __shared__ uint32_t s_key[kBSlots];
   __shared__ unsigned long long s_A[kBSlots];  // count << 40 | sum r
@@ -947,7 +1023,7 @@ __global__ __launch_bounds__(kBT) void voxb_accum_kernel(VoxBatchArgs a) {
   if (b >= a.total) return;  // clearing only
   const int f = vb_frame(a.blk0, a.nf, b);
   const int64_t base = (int64_t)(b - a.blk0[f]) * kBChunk;
-  const float4* __restrict__ pts = a.pts[f];
+  const Pts src(a, f);
   const int64_t n = a.n[f];
   const uint32_t mx_ = (1u << a.tb[0]) - 1, my_ = (1u << a.tb[1]) - 1, mz_ = (1u << a.tb[2]) - 1;
   const int sy = a.tb[0], sz = a.tb[0] + a.tb[1];
@@ -974,24 +1050,26 @@ __global__ __launch_bounds__(kBT) void voxb_accum_kernel(VoxBatchArgs a) {
     if (m < kMarginFlush) __hip_atomic_fetch_min(Mg + t, m, __ATOMIC_RELAXED, C3H_VB_ATOM_SCOPE);
   };
   const uint64_t le = (lane == 63) ? ~0ull : ((2ull << lane) - 1);  // lanes <= this one
-  for (int r0 = 0; r0 < kBPer; r0 += kBRound) {
-  float4 p[kBRound];
+  constexpr int kRound = Pts::kRound;
+  static_assert(kBPer % kRound == 0, "rounds");
+  for (int r0 = 0; r0 < kBPer; r0 += kRound) {
+  typename Pts::Raw raw[kRound];
 #pragma unroll
-  for (int j = 0; j < kBRound; ++j) {  // a round of loads in flight together
+  for (int j = 0; j < kRound; ++j) {  // a round of loads in flight together
     const int64_t i = base + (int64_t)(r0 + j) * kBT + tid;
     if (i < n) {
-      const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(pts) + i);
-      p[j] = make_float4(v.x, v.y, v.z, v.w);
+      raw[j] = src.load_nt(i);
     } else {
-      p[j] = make_float4(NAN, NAN, NAN, 0.0f);
+      raw[j] = Pts::none();
     }
   }
 #pragma unroll
-  for (int j = 0; j < kBRound; ++j) {
+  for (int j = 0; j < kRound; ++j) {
+    const float4& pj = src.point(raw[j]);
     int c[3];
     float margin;
-    bool valid = point_valid(p[j], a.z_limit);
-    if (valid && !point_cell(a.inv, p[j], c, &margin)) {
+    bool valid = point_valid(pj, a.z_limit);
+    if (valid && !point_cell(a.inv, pj, c, &margin)) {
       err = true;
       valid = false;
     }
@@ -1004,7 +1082,7 @@ __global__ __launch_bounds__(kBT) void voxb_accum_kernel(VoxBatchArgs a) {
         mx[ax] = max(mx[ax], c[ax]);
       }
       t = ((uint32_t)c[0] & mx_) | (((uint32_t)c[1] & my_) << sy) | (((uint32_t)c[2] & mz_) << sz);
-      const uint32_t rgb = __float_as_uint(p[j].w);
+      const uint32_t rgb = __float_as_uint(pj.w);
       w0 = ((rgb >> 16) & 0xffu) | (((rgb >> 8) & 0xffu) << 12) | (1u << 24);  // r | g << 12 | count << 24
       w1 = rgb & 0xffu;                                                         // b
       const uint32_t mbits = __float_as_uint(margin);
@@ -1286,6 +1364,7 @@ static_assert((kVbFlagSlots & (kVbFlagSlots - 1)) == 0, "flag hash");
 // read per item instead of a dispatched 48 KB-LDS block each (round 6: 15.6k empty blocks
 // per 64-frame batch took ~20 us of the voxeliser's critical path)
 constexpr int kBucketGrid = 768;
+template <class Pts>
 __global__ __launch_bounds__(kBT) void voxb_bucket_kernel(VoxBatchArgs a, int nitems) {
   __shared__ uint32_t s_key[kVbFlagSlots];
   __shared__ uint16_t s_rec[kVbFlagSlots];
@@ -1324,7 +1403,7 @@ __global__ __launch_bounds__(kBT) void voxb_bucket_kernel(VoxBatchArgs a, int ni
       f_tab = f;
     }
     const int64_t base = (int64_t)(b - a.blk0[f]) * kBChunk;
-    const float4* __restrict__ pts = a.pts[f];
+    const Pts src(a, f);
     const int64_t n = a.n[f];
     const uint32_t mx_ = (1u << a.tb[0]) - 1, my_ = (1u << a.tb[1]) - 1, mz_ = (1u << a.tb[2]) - 1;
     const int sy = a.tb[0], sz = a.tb[0] + a.tb[1];
@@ -1334,7 +1413,7 @@ __global__ __launch_bounds__(kBT) void voxb_bucket_kernel(VoxBatchArgs a, int ni
 #pragma unroll
     for (int q = 0; q < kPer; ++q) {
       const int64_t i = base + (int64_t)(qy * kPer + q) * kBT + tid;
-      p[q] = i < n ? pts[i] : make_float4(NAN, NAN, NAN, 0.0f);
+      p[q] = i < n ? src.get(i) : make_float4(NAN, NAN, NAN, 0.0f);
     }
 #pragma unroll
     for (int q = 0; q < kPer; ++q) {
@@ -1370,6 +1449,7 @@ __global__ __launch_bounds__(kBT) void voxb_bucket_kernel(VoxBatchArgs a, int ni
 constexpr int kExactSplit = 16;
 constexpr int kExactLds = 64;  // bucket entries per thread sorted in LDS (64 KB; the real Kinect
                                // views' near-face voxels hold <= 66 points, 99 % <= 51)
+template <class Pts>
 __global__ __launch_bounds__(kBlock) void voxb_exact_kernel(VoxBatchArgs a) {
   __shared__ uint32_t s_bk[kBlock * kExactLds];
   const int f = blockIdx.x, tid = threadIdx.x;
@@ -1379,9 +1459,15 @@ __global__ __launch_bounds__(kBlock) void voxb_exact_kernel(VoxBatchArgs a) {
   const int nrec = (int)min(nflag, (uint32_t)kVbFlagCap);
   const VoxFlag* fl = a.flags + (size_t)f * kVbFlagCap;
   uint32_t* bks = a.bucket + (size_t)f * kVbBucketCap;
-  const float4* __restrict__ pts = a.pts[f];
+  const Pts src(a, f);
   const int Cx = a.C[0], Cy = a.C[1];
-  uint32_t* mine = s_bk + tid;  // this thread's slice, strided by kBlock (bank-conflict free)
+  // this thread's slice, strided by kBlock (bank-conflict free).  PtsXyzrgb keeps the generic
+  // pointer its code was built with; behind PtsPc2's loads the compiler fails to select
+  // instructions for the generic pointer chosen between the slice and the global bucket
+  // (src_shared_base as a VOPC operand), so there the slice is typed as LDS
+  typedef __attribute__((address_space(3))) uint32_t lds_u32;
+  using Slice = typename std::conditional<std::is_same<Pts, PtsXyzrgb>::value, uint32_t, lds_u32>::type;
+  Slice* mine = (Slice*)s_bk + tid;
   for (int r = blockIdx.y * kBlock + tid; r < nrec; r += kBlock * gridDim.y) {
     const VoxFlag e = fl[r];
     const int m = (int)e.count;
@@ -1420,7 +1506,7 @@ __global__ __launch_bounds__(kBlock) void voxb_exact_kernel(VoxBatchArgs a) {
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
         const int u = u0 + q;
-        p[q] = u < m ? pts[small ? mine[u * kBlock] : bk[u]] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        p[q] = u < m ? src.get(small ? mine[u * kBlock] : bk[u]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
       }
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
@@ -1482,9 +1568,25 @@ hipError_t launch_vox_batch(const VoxBatchArgs& a, hipStream_t s) {
   return e != hipSuccess ? e : launch_vox_batch_post(a, s);
 }
 
+namespace {
+// the kernels of the batch's point source: f(policy tag)
+template <class P>
+struct PtsTag {
+  using type = P;
+};
+template <class F>
+void with_pts(const VoxBatchArgs& a, F&& f) {
+  if (a.src == 0) return f(PtsTag<PtsXyzrgb>{});
+  if (a.pc2.form == kPc2Vec16) return a.pc2.npiece == 2 ? f(PtsTag<PtsPc2<kPc2Vec16, 2>>{}) : f(PtsTag<PtsPc2<kPc2Vec16, 1>>{});
+  if (a.pc2.form == kPc2Dword) return f(PtsTag<PtsPc2<kPc2Dword, 1>>{});
+  return f(PtsTag<PtsPc2<kPc2Bytes, 1>>{});
+}
+}  // namespace
+
 hipError_t launch_vox_batch_accum(const VoxBatchArgs& a, hipStream_t s) {
   const int g = std::max(a.total, a.prev_total);
-  if (g > 0) voxb_accum_kernel<<<(unsigned)g, kBT, 0, s>>>(a);
+  if (g > 0)
+    with_pts(a, [&](auto tag) { voxb_accum_kernel<typename decltype(tag)::type><<<(unsigned)g, kBT, 0, s>>>(a); });
   return hipGetLastError();
 }
 
@@ -1494,8 +1596,11 @@ hipError_t launch_vox_batch_post(const VoxBatchArgs& a, hipStream_t s) {
     voxb_scatter_kernel<<<(unsigned)a.total, kBlock, a.stamp ? 4 * (size_t)((a.ntiles + 31) / 32) : 0, s>>>(a);
     if (a.flags) {
       const int items = a.total * kBucketSplit;
-      voxb_bucket_kernel<<<(unsigned)std::min(items, kBucketGrid), kBT, 0, s>>>(a, items);
-      voxb_exact_kernel<<<dim3((unsigned)a.nf, kExactSplit), kBlock, 0, s>>>(a);
+      with_pts(a, [&](auto tag) {
+        using Pts = typename decltype(tag)::type;
+        voxb_bucket_kernel<Pts><<<(unsigned)std::min(items, kBucketGrid), kBT, 0, s>>>(a, items);
+        voxb_exact_kernel<Pts><<<dim3((unsigned)a.nf, kExactSplit), kBlock, 0, s>>>(a);
+      });
     }
   }
   return hipGetLastError();
