@@ -7,6 +7,8 @@
 #include <cstdlib>
 #include <string>
 #include <mutex>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/c3hlac_mi355x.h"
@@ -30,11 +32,42 @@ constexpr float kNorm117_1 = 1 / 845325.0;
 constexpr float kNorm117_1Bin = 1 / 13.0;
 
 // ---- device buffers --------------------------------------------------------------
+// A buffer owns its allocation and frees it when it goes: a context's buffers with the
+// context (c3h_destroy: the device set, nothing in flight).  None may have static storage:
+// it would be freed after the runtime has shut down.
 template <class T>
 struct DevBuf {
   T* p = nullptr;
   size_t n = 0;  // capacity in elements
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), n(std::exchange(o.n, 0)) {}
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    std::swap(p, o.p);
+    std::swap(n, o.n);
+    return *this;
+  }
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+  // Capacity for `want` elements (0 counts as 1).  A buffer that has to grow is freed, then
+  // allocated: the contents are not kept.  On failure it is left empty and *in_free tells
+  // which of the two calls failed.
+  hipError_t reserve(size_t want, bool* in_free = nullptr) {
+    if (want == 0) want = 1;
+    if (n >= want) return hipSuccess;
+    hipError_t e = p ? hipFree(p) : hipSuccess;
+    p = nullptr;
+    n = 0;
+    if (in_free) *in_free = e != hipSuccess;
+    if (e == hipSuccess) e = hipMalloc(&p, want * sizeof(T));
+    if (e != hipSuccess) p = nullptr;
+    else n = want;
+    return e;
+  }
 };
+static_assert(!std::is_copy_constructible<DevBuf<float>>::value, "DevBuf: one owner per allocation");
 
 struct SearchLists {  // SearchObjMulti max_*_multi state, host side
   int rank = 0, M = 0;

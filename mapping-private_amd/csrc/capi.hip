@@ -5,109 +5,21 @@
 // (c3_hlac/src/c3_hlac.cpp:204-231), the search mode schedule (search.cpp:384-427),
 // setSceneAxis whitening (search.cpp:701-712), setRank/cleanMax list state
 // (search.cpp:130-143, 683-732) and removeOverlap (search.cpp:972-992).
+// This unit: the context, the single-frame path and the readbacks; the lanes, the pipeline
+// and the batch entry points are capi_batch.hip.
 #include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <thread>
 
-#include "c3h_internal.h"
-#include "feat_rows.h"
+#include "capi_host.h"
 #include "occ_sched.h"
 
-using c3h::DevBuf;
+using namespace c3h;
 
 namespace {
-
-int fail(c3h_ctx* ctx, int code, const std::string& msg) {
-  if (ctx) ctx->err = msg;
-  return code;
-}
-int hip_fail(c3h_ctx* ctx, const char* what, hipError_t e) {
-  return fail(ctx, C3H_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-#define HIPCHK(expr)                                     \
-  do {                                                   \
-    hipError_t e_ = (expr);                              \
-    if (e_ != hipSuccess) return hip_fail(ctx, #expr, e_); \
-  } while (0)
-
-template <class T>
-int ensure(c3h_ctx* ctx, DevBuf<T>& b, size_t n) {
-  if (n == 0) n = 1;
-  if (b.n >= n) return C3H_OK;
-  if (b.p) {
-    hipError_t e = hipFree(b.p);
-    b.p = nullptr;
-    b.n = 0;
-    if (e != hipSuccess) return hip_fail(ctx, "hipFree", e);
-  }
-  hipError_t e = hipMalloc(&b.p, n * sizeof(T));
-  if (e != hipSuccess) {
-    b.p = nullptr;
-    return fail(ctx, C3H_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-  }
-  b.n = n;
-  return C3H_OK;
-}
-
-template <class T>
-void release(DevBuf<T>& b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.n = 0;
-}
-
-int pipe_quiesce(c3h_ctx* ctx);  // defined with the pipeline below
-int pipe_flush(c3h_ctx* ctx);
-
-// entry points that touch a context's buffers first drain its open frame stream
-#define QUIESCE(ctx)                            \
-  do {                                          \
-    int rq_ = pipe_quiesce(ctx);                \
-    if (rq_ != C3H_OK) return rq_;              \
-  } while (0)
-
-#define ENSURE(buf, n)                          \
-  do {                                          \
-    int rc_ = ensure(ctx, buf, (size_t)(n));    \
-    if (rc_ != C3H_OK) return rc_;              \
-  } while (0)
-
-// ---- timing ------------------------------------------------------------------------
-struct Timed {
-  c3h_ctx* ctx;
-  c3h::Timer* T;
-  int slot, weight;
-  std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
-  hipStream_t st;
-  Timed(c3h_ctx* c, int s, int w = 1, hipStream_t on = nullptr)
-      : ctx(c), T(c->parent ? &c->parent->timer : &c->timer), slot(s), weight(w), st(on ? on : c->stream) {
-    if (!(T->mask >> (s + 1) & 1) || c->capture) return;
-    std::lock_guard<std::mutex> g(T->mu);
-    if (T->pool.empty()) {
-      hipEvent_t a, b;
-      if (hipEventCreate(&a) != hipSuccess) return;
-      if (hipEventCreate(&b) != hipSuccess) {
-        (void)hipEventDestroy(a);
-        return;
-      }
-      T->pool.push_back({a, b});
-    }
-    ev = T->pool.back();
-    T->pool.pop_back();
-    (void)hipEventRecord(ev.first, st);  // on the stream the kernels run on
-  }
-  ~Timed() {
-    if (!ev.first) return;
-    (void)hipEventRecord(ev.second, st);
-    std::lock_guard<std::mutex> g(T->mu);
-    T->pending[slot].push_back(c3h::TimedPair{ev.first, ev.second, weight});
-  }
-};
 
 // setColor as a 256-entry table of packed (r | r_ << 8) channel pairs, one table per
 // C3H_COLOR_* mode (color_chlac.hpp:148-179)
@@ -142,8 +54,10 @@ void get_range(int mode, int r1, int r2, int r3, int* xr, int* yr, int* zr) {
   }
 }
 
+}  // namespace
+
 // search.cpp:384-427
-int mode_schedule(int r1, int r2, int r3, int rotate, int* modes) {
+int c3h::mode_schedule(int r1, int r2, int r3, int rotate, int* modes) {
   if (!rotate) {
     modes[0] = C3H_S_MODE_1;
     return 1;
@@ -167,6 +81,8 @@ int mode_schedule(int r1, int r2, int r3, int rotate, int* modes) {
   for (int i = 0; i < 6; ++i) modes[i] = i;
   return 6;
 }
+
+namespace {
 
 // checkOverlap of SearchObjMulti (search.cpp:862-891) on host lists
 int check_overlap(const c3h_det* L, int rank, int r1, int r2, int r3, int x, int y, int z,
@@ -357,11 +273,6 @@ int sync_host_lists(c3h_ctx* ctx) {
   return C3H_OK;
 }
 
-// setData + searchPart for every scheduled mode; leaves the lists valid on the device
-// setData + search for the nf frames of the last extract_frames (frame f's results at
-// f * stride; d_out + f * M * rank).  clean: 0 = continue from the lists, 1 = cleanMax
-// first, 2 = reset the lists as setRank does (batched frames start fresh).
-// gate: -1 fill only for positions not already gated out (0: every gated-out position)
 // The f32 feature rows of the last extract when it wrote them as f16 (fp16 search precision
 // on a large dense grid): converted on the device if the MFMA body set the flag.
 int feat_rows_f32(c3h_ctx* ctx) {
@@ -372,8 +283,15 @@ int feat_rows_f32(c3h_ctx* ctx) {
   return C3H_OK;
 }
 
-int search_frames(c3h_ctx* ctx, int nf, const int32_t range[3], int32_t thr, int32_t rotate,
-                  c3h_det* const* d_outs, int clean) {
+}  // namespace
+
+// setData + searchPart for every scheduled mode; leaves the lists valid on the device
+// setData + search for the nf frames of the last extract_frames (frame f's results at
+// f * stride; d_out + f * M * rank).  clean: 0 = continue from the lists, 1 = cleanMax
+// first, 2 = reset the lists as setRank does (batched frames start fresh).
+// gate: -1 fill only for positions not already gated out (0: every gated-out position)
+int c3h::search_frames(c3h_ctx* ctx, int nf, const int32_t range[3], int32_t thr, int32_t rotate,
+                       c3h_det* const* d_outs, int clean) {
   if (!ctx->have_feat) return fail(ctx, C3H_ERR_STATE, "c3h_search: no features (call c3h_extract)");
   if (!ctx->have_setup) return fail(ctx, C3H_ERR_STATE, "c3h_search: no axes (call c3h_search_setup)");
   if (!range || range[0] < 1 || range[1] < 1 || range[2] < 1)
@@ -660,6 +578,8 @@ int search_frames(c3h_ctx* ctx, int nf, const int32_t range[3], int32_t thr, int
   return nm;
 }
 
+namespace {
+
 int run_search(c3h_ctx* ctx, const int32_t range[3], int32_t thr, int32_t rotate, c3h_det* d_out) {
   return search_frames(ctx, 1, range, thr, rotate, &d_out, 0);
 }
@@ -732,7 +652,7 @@ int c3h_create(int hip_device, c3h_ctx** out) {
 void c3h_destroy(c3h_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
-  (void)pipe_flush(ctx);
+  (void)c3h::pipe_flush(ctx);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   for (c3h_ctx* l : ctx->lanes) c3h_destroy(l);
   for (hipEvent_t e : ctx->lane_ev) (void)hipEventDestroy(e);
@@ -745,84 +665,6 @@ void c3h_destroy(c3h_ctx* ctx) {
   if (ctx->pb_vox_ev) (void)hipEventDestroy(ctx->pb_vox_ev);
   for (hipEvent_t e : ctx->pb_tick_ev)
     if (e) (void)hipEventDestroy(e);
-  release(ctx->grid);
-  release(ctx->pts);
-  release(ctx->raw);
-  release(ctx->dsbuf);
-  release(ctx->normals);
-  release(ctx->nkeys);
-  release(ctx->nkeys2);
-  release(ctx->nidx);
-  release(ctx->nidx2);
-  release(ctx->ncstart);
-  release(ctx->ncend);
-  release(ctx->ntmp);
-  release(ctx->dsamp);
-  release(ctx->rsd_radii);
-  release(ctx->rsd_types);
-  release(ctx->grsd_trans);
-  release(ctx->grsd_feat);
-  release(ctx->vosch_feat);
-  release(ctx->vacc);
-  release(ctx->vmg);
-  release(ctx->vtpos);
-  release(ctx->vlcnt);
-  release(ctx->vlists);
-  release(ctx->vcnt);
-  release(ctx->vpart);
-  release(ctx->vcounts);
-  release(ctx->voffs);
-  release(ctx->vcur);
-  release(ctx->vbucket);
-  release(ctx->vcent);
-  release(ctx->voffcell);
-  release(ctx->scratch);
-  release(ctx->tmp_u32);
-  release(ctx->tmp_i32);
-  release(ctx->feat);
-  release(ctx->exist);
-  release(ctx->acc64);
-  release(ctx->segs);
-  release(ctx->axmap);
-  release(ctx->tileflags);
-  release(ctx->segmap);
-  release(ctx->rows);
-  release(ctx->work);
-  release(ctx->glist);
-  release(ctx->gbox);
-  release(ctx->gcnt);
-  release(ctx->lut);
-  release(ctx->axis_pt);
-  release(ctx->axis_pt16);
-  release(ctx->axis_q);
-  release(ctx->fmax);
-  release(ctx->G);
-  release(ctx->scores);
-  release(ctx->qt);
-  release(ctx->partials);
-  release(ctx->d_lists);
-  release(ctx->prof);
-  release(ctx->chist);
-  release(ctx->qt16);
-  release(ctx->pb_grid);
-  release(ctx->pb_wlist);
-  release(ctx->pb_part);
-  release(ctx->pb_lim);
-  release(ctx->dense_flag);
-  release(ctx->pb_flags);
-  release(ctx->pb_bucket);
-  release(ctx->pb_xcnt);
-  release(ctx->pb_moved);
-  release(ctx->pb_acc);
-  release(ctx->pb_accM);
-  release(ctx->pb_fcnt);
-  release(ctx->pb_vlist);
-  release(ctx->pb_stage);
-  release(ctx->pb_raw);
-  release(ctx->pb_info);
-  release(ctx->ff_has);
-  release(ctx->ff_lim);
-  release(ctx->ff_cnt);
   for (int s = 0; s < C3H_NTIMERS; ++s)
     for (auto& e : ctx->timer.pending[s]) ctx->timer.pool.push_back({e.a, e.b});
   for (auto& e : ctx->timer.pool) {
@@ -833,7 +675,7 @@ void c3h_destroy(c3h_ctx* ctx) {
   if (ctx->h_recs) (void)hipHostFree(ctx->h_recs);
   if (ctx->h_dl) (void)hipHostFree(ctx->h_dl);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-  delete ctx;
+  delete ctx;  // frees every device buffer: the device is set and nothing is in flight
 }
 
 int c3h_set_stream(c3h_ctx* ctx, void* hip_stream) {
@@ -1305,13 +1147,15 @@ int c3h_set_grid(c3h_ctx* ctx, const uint32_t* words, const int32_t div_b[3],
 // The extract after a c3h_voxelize stamps its tiles from the voxeliser's list (round 6);
 // any other extract streams the grid.
 
-static bool extract_params_ok(const c3h_extract_params* p) {
+}  // extern "C"
+
+bool c3h::extract_params_ok(const c3h_extract_params* p) {
   return (p->variant == 981 || p->variant == 117) && p->color_mode >= C3H_COLOR_C3_FLOAT &&
          p->color_mode <= C3H_COLOR_CHLAC;
 }
 
-int extract_frames(c3h_ctx* ctx, const uint32_t* const* grids, int nf, const c3h_extract_params* p,
-                   int32_t subdiv_out[3], int64_t* hist_num_out) {
+int c3h::extract_frames(c3h_ctx* ctx, const uint32_t* const* grids, int nf, const c3h_extract_params* p,
+                        int32_t subdiv_out[3], int64_t* hist_num_out) {
   if (!ctx || !p) return C3H_ERR_ARG;
   if (!extract_params_ok(p))
     return fail(ctx, C3H_ERR_ARG, "c3h_extract: variant must be 981 or 117, color_mode a C3H_COLOR_* value");
@@ -1576,6 +1420,8 @@ int extract_frames(c3h_ctx* ctx, const uint32_t* const* grids, int nf, const c3h
   return C3H_OK;
 }
 
+extern "C" {
+
 int c3h_extract(c3h_ctx* ctx, const c3h_extract_params* p, int32_t subdiv_out[3],
                 int64_t* hist_num_out) {
   if (!ctx) return C3H_ERR_ARG;
@@ -1584,18 +1430,8 @@ int c3h_extract(c3h_ctx* ctx, const c3h_extract_params* p, int32_t subdiv_out[3]
   return extract_frames(ctx, &g, 1, p, subdiv_out, hist_num_out);
 }
 
-// sensor_msgs/PointCloud2 ingestion (pcl::fromROSMsg, detect_object.cpp:142)
-static int pc2_check(c3h_ctx* ctx, uint32_t height, uint32_t width, uint32_t point_step, uint32_t row_step,
-                     const int32_t off[4]) {
-  if (!off) return fail(ctx, C3H_ERR_ARG, "pointcloud2: no field offsets");
-  for (int k = 0; k < 4; ++k)
-    if ((k < 3 && off[k] < 0) || off[k] + 4 > (int64_t)point_step)
-      return fail(ctx, C3H_ERR_ARG, "pointcloud2: field x/y/z missing or outside point_step");
-  if (height > 1 && (uint64_t)row_step < (uint64_t)width * point_step)
-    return fail(ctx, C3H_ERR_ARG, "pointcloud2: row_step < width * point_step");
-  return C3H_OK;
-}
-
+// sensor_msgs/PointCloud2 ingestion (pcl::fromROSMsg, detect_object.cpp:142; the argument
+// check is capi_host.h's pc2_check)
 int c3h_pointcloud2_to_xyzrgb(const void* d_data, uint32_t height, uint32_t width, uint32_t point_step,
                               uint32_t row_step, const int32_t offsets[4], int32_t is_bigendian, float* d_out,
                               void* hip_stream) {
@@ -1897,7 +1733,6 @@ static int masked_readback(c3h_ctx* ctx, const float* src, int W, float* out, in
   hipError_t e = c3h::launch_masked_rows(src, ctx->exist.p, ctx->hist_num, W, dst, ctx->stream);
   if (e == hipSuccess && !on_device) e = hipMemcpyAsync(out, dst, n * 4, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (!on_device) release(tmp);
   if (e != hipSuccess) return fail(ctx, C3H_ERR_HIP, std::string("readback: ") + hipGetErrorString(e));
   return C3H_OK;
 }
@@ -1966,10 +1801,12 @@ int c3h_set_remove_overlap(c3h_ctx* ctx, int32_t enable) {
   return C3H_OK;
 }
 
+}  // extern "C"
+
 // the bases on the device (D a multiple of 4 when D <= 160; see c3h_search_setup)
-static int search_setup_dev(c3h_ctx* ctx, const float* axis_p, const float* var, int32_t D, int32_t F,
-                            const float* axis_q, int32_t M, int32_t r, const float* feature_max,
-                            int32_t feature_max_len, int32_t D_user) {
+int c3h::search_setup_dev(c3h_ctx* ctx, const float* axis_p, const float* var, int32_t D, int32_t F,
+                          const float* axis_q, int32_t M, int32_t r, const float* feature_max,
+                          int32_t feature_max_len, int32_t D_user) {
   HIPCHK(hipSetDevice(ctx->device));
   // the bases are replaced with synchronous copies: queued kernels of this context may
   // still read them
@@ -2047,6 +1884,8 @@ static int search_setup_dev(c3h_ctx* ctx, const float* axis_p, const float* var,
   if (ctx->lists.M != M) init_lists(ctx);
   return C3H_OK;
 }
+
+extern "C" {
 
 int c3h_search_setup(c3h_ctx* ctx, const float* axis_p, const float* var, int32_t D, int32_t F,
                      const float* axis_q, int32_t M, int32_t r, const float* feature_max,
@@ -2170,1241 +2009,6 @@ int c3h_set_batch(c3h_ctx* ctx, int32_t frames) {
   return C3H_OK;
 }
 
-}  // extern "C"
-
-namespace {
-
-// child contexts lanes[0 .. n-1] exist and carry the context's search setup and rank
-int ensure_lanes(c3h_ctx* ctx, int n) {
-  while ((int)ctx->lanes.size() < n) {
-    c3h_ctx* c = nullptr;
-    int rc = c3h_create(ctx->device, &c);
-    if (rc != C3H_OK) return fail(ctx, rc, "c3h_run_frames: lane context");
-    c->parent = ctx;
-    ctx->lanes.push_back(c);
-    hipEvent_t e;
-    HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    ctx->lane_ev.push_back(e);
-  }
-  bool synced = false;
-  for (int l = 0; l < n; ++l) {
-    c3h_ctx* c = ctx->lanes[l];
-    if (c->setup_version != ctx->setup_version || !c->have_setup) {
-      if (!synced) {  // pipelined batches of this lane may still be queued on the parent's stream
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        synced = true;
-      }
-      int rc = search_setup_dev(c, ctx->h_axis_p.empty() ? nullptr : ctx->h_axis_p.data(),
-                                ctx->h_var.empty() ? nullptr : ctx->h_var.data(), ctx->D, ctx->F,
-                                ctx->h_axis_q.data(), ctx->M, ctx->r,
-                                ctx->h_fmax.empty() ? nullptr : ctx->h_fmax.data(), (int)ctx->h_fmax.size(),
-                                ctx->D_user);
-      if (rc != C3H_OK) return fail(ctx, rc, std::string("c3h_run_frames: lane setup: ") + c->err);
-      c->setup_version = ctx->setup_version;
-    }
-    if (c->rank != ctx->rank) {
-      int rc = c3h_set_rank(c, ctx->rank);
-      if (rc != C3H_OK) return rc;
-    }
-  }
-  return C3H_OK;
-}
-
-// c3h_set_remove_overlap: the launch that passes the records of nb searched frames (outs)
-// through removeOverlap; it goes behind those searches on their stream
-c3h::RemoveOverlapFrames overlap_args(const c3h_ctx* ctx, const int32_t range[3], c3h_det* const* outs, int nb) {
-  c3h::RemoveOverlapFrames ro{};
-  ro.M = std::max(ctx->M, 1);
-  ro.nf = nb;
-  ro.rank = ctx->rank;
-  ro.r1 = range[0];
-  ro.r2 = range[1];
-  ro.r3 = range[2];
-  for (int f = 0; f < nb; ++f) ro.outs[f] = outs[f];
-  return ro;
-}
-
-bool overlap_wanted(const c3h_ctx* ctx) { return ctx->remove_overlap && ctx->rank >= 2; }
-
-// the batch entry points' limit: the per-slot form holds a list on the lanes of one wave
-int overlap_rank_check(c3h_ctx* ctx, const char* who) {
-  if (ctx->remove_overlap && ctx->rank > 64)
-    return fail(ctx, C3H_ERR_ARG, std::string(who) + ": c3h_set_remove_overlap needs rank <= 64");
-  return C3H_OK;
-}
-
-// frames of chunk ch (B per chunk); the last chunk puts its last frame in slot 0, so the
-// context that runs it ends up holding the last frame's state
-int chunk_frames(const uint32_t* const* d_grids, c3h_det* d_out, size_t per_frame, int nframes, int B,
-                 int nchunks, int ch, const uint32_t** grids, c3h_det** outs) {
-  const int f0 = ch * B, nb = std::min(B, nframes - f0);
-  for (int j = 0; j < nb; ++j) {  // nchunks < 0: natural order throughout
-    const int fi = (ch == nchunks - 1) ? (j == 0 ? f0 + nb - 1 : f0 + j - 1) : f0 + j;
-    grids[j] = d_grids[fi];
-    outs[j] = d_out + (size_t)fi * per_frame;
-  }
-  return nb;
-}
-
-// Software-pipelined batches (pipeline.hip).  Batch number s is prepared on buffer set
-// s % 4 (set 0 = this context) and runs as the occupancy role of one tick, the tile role
-// of the next, compress+gate of the one after and scoring + rank-1 argmax of the fourth.
-// All buffer sets work on this context's stream, so ticks order themselves; the host
-// only enqueues.  The pipeline persists across c3h_stream_frames calls (a continuous
-// frame source keeps it full); c3h_run_frames and c3h_stream_flush drain it.
-constexpr int kPipeDepth = 4;
-
-c3h_ctx* pipe_set(c3h_ctx* ctx, uint64_t seq) {
-  const int set = (int)(seq % kPipeDepth);
-  return set == 0 ? ctx : ctx->lanes[set - 1];
-}
-
-// lane contexts enqueue on the parent's stream while a pipeline call runs
-struct PipeScope {
-  c3h_ctx* ctx;
-  hipStream_t saved[kPipeDepth - 1];
-  explicit PipeScope(c3h_ctx* c) : ctx(c) {
-    ctx->pipe_busy = true;
-    for (int l = 0; l < kPipeDepth - 1 && l < (int)ctx->lanes.size(); ++l) {
-      saved[l] = ctx->lanes[l]->stream;
-      ctx->lanes[l]->stream = ctx->stream;
-    }
-  }
-  ~PipeScope() {
-    for (int l = 0; l < kPipeDepth - 1 && l < (int)ctx->lanes.size(); ++l) ctx->lanes[l]->stream = saved[l];
-    ctx->pipe_busy = false;
-  }
-};
-
-// one tick: the occupancy role of `fresh` (nullable) and the next role of every batch in
-// flight; afterwards every batch is one stage older and finished batches leave
-int pipe_tick(c3h_ctx* ctx, const c3h_ctx::PipeBatch* fresh) {
-  c3h::TickParts tp;
-  tp.prof = &ctx->prof;
-  // a feature-row batch has no occupancy and no tile role (its front kernel wrote what they
-  // produce): it joins at the compress + gate slot of this very tick
-  const bool rows_in = fresh && fresh->rows_in;
-  if (rows_in) {
-    ctx->pipe.push_back(*fresh);
-    ctx->pipe.back().age = 2;
-  }
-  if (fresh && !fresh->stamped && !rows_in) tp.occ = &fresh->l;
-  for (auto& b : ctx->pipe) {
-    if (b.age == 1) {
-      tp.tile = &b.l;
-      tp.tile_mapped = b.mapped;
-    }
-    if (b.age == 2) {
-      tp.gate = &b.q;
-      tp.comp = &b.sc;
-    }
-    if (b.age == 3) tp.score = b.rows_in ? &b.qs : &b.q;
-  }
-  {
-    Timed tm(ctx, 5, fresh ? fresh->nf : 0);
-    hipError_t e = c3h::launch_tick(tp, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, "launch_tick", e);
-  }
-  for (auto& b : ctx->pipe) {
-    if (b.age == 3 && b.replay) {  // its score role ran in this tick: the lists of its frames
-      Timed tm(ctx, 4, b.nf);
-      hipError_t e = c3h::launch_replay_frames(b.rp, ctx->stream);
-      if (e != hipSuccess) return hip_fail(ctx, "launch_replay_frames", e);
-    }
-    if (b.age == 3 && b.overlap) {  // removeOverlap on its frames' records, behind the replay
-      hipError_t e = c3h::launch_remove_overlap_frames(b.ro, ctx->stream);
-      if (e != hipSuccess) return hip_fail(ctx, "launch_remove_overlap_frames", e);
-    }
-    if (b.age == 2 && b.set) b.set->scores_layout = b.layout;  // this tick enqueued its gate
-    if (b.age == 1 && b.fix) {  // its tile role ran in this tick: the off-cell fixup before its compress
-      hipError_t e = c3h::launch_point_fixup(b.fx, ctx->stream);
-      if (e != hipSuccess) return hip_fail(ctx, "launch_point_fixup", e);
-    }
-  }
-  std::vector<c3h_ctx::PipeBatch> next;
-  for (auto& b : ctx->pipe)
-    if (b.age < (b.nosearch ? 1 : 3)) {
-      next.push_back(b);
-      next.back().age++;
-    }
-  if (fresh && !rows_in) {
-    next.push_back(*fresh);
-    next.back().age = 1;
-    next.back().mapped = tp.occ != nullptr;
-  }
-  ctx->pipe.swap(next);
-  return C3H_OK;
-}
-
-int pipe_flush(c3h_ctx* ctx) {
-  if (ctx->pipe.empty()) return C3H_OK;
-  PipeScope scope(ctx);
-  while (!ctx->pipe.empty()) {
-    int rc = pipe_tick(ctx, nullptr);
-    if (rc != C3H_OK) {
-      ctx->pipe.clear();
-      return rc;
-    }
-  }
-  return C3H_OK;
-}
-
-// public entry points that touch this context's buffers drain an open stream first
-int pipe_quiesce(c3h_ctx* ctx) {
-  if (ctx->pipe_busy || ctx->pipe.empty()) return C3H_OK;
-  return pipe_flush(ctx);
-}
-
-// Captures nb frames as the next batch on its buffer set (no launch: its tile stamps may
-// come from elsewhere first).  Returns > 0 (modes searched), 0 when the configuration does
-// not fit the tick (only possible for the first batch of a stream: the caller then runs
-// the lanes), < 0 on error.
-int pipe_prepare(c3h_ctx* ctx, const uint32_t* const* grids, c3h_det* const* outs, int nb,
-                 const c3h_ctx::PipeKey& k, const int32_t* lim, c3h_ctx::PipeBatch* fresh) {
-  c3h_ctx* c = pipe_set(ctx, ctx->pipe_seq);
-  c->capture = true;
-  c->cap_c3_valid = c->cap_search_valid = false;
-  int rc = c3h_set_grid(c, grids[0], k.div_b, k.min_b, k.leaf, 1);
-  if (rc == C3H_OK) rc = extract_frames(c, grids, nb, &k.p, nullptr, nullptr);
-  if (rc == C3H_OK) rc = search_frames(c, nb, k.range, k.thr, k.rotate, outs, 2);
-  c->capture = false;
-  c->cap_q.lim = lim;  // canvas frames: each frame's own subdivisions bound its positions
-  c->cap_q.score_engine = ctx->score_engine;  // the tick's score role (launch_tick)
-  if (rc < 0) {
-    if (c != ctx) ctx->err = c->err;
-    return rc;
-  }
-  // points-in frames without subdivisions (S = 0, one histogram): the reference runs no search
-  // (search_frames returned 0: setData returns early), the batch is its C3 stage alone
-  if (rc == 0 && lim && k.p.subdiv == 0 && c->cap_c3_valid && c3h::tick_ok(c->cap_c3)) {
-    c->nframes_feat = 1;
-    *fresh = c3h_ctx::PipeBatch{c->cap_c3, c3h::SparseSearch{}, c3h::SparseCompress{}, nb, 0};
-    fresh->nosearch = true;
-    return 1;
-  }
-  // rank 1: the score role's fused argmax; ranks 2 .. 64: the score role writes the scores
-  // only and the batched replay follows it
-  const bool ranked = c->cap_argmax || (c->cap_replay && c->rank >= 2 && !c->cap_q.lists && !c->cap_q.partials);
-  const bool fits = c->cap_c3_valid && c->cap_search_valid && c->cap_sparse_g && ranked &&
-                    c3h::tick_ok(c->cap_c3);
-  if (!fits) {  // one geometry per stream: decided on its first batch
-    if (!ctx->pipe.empty()) return fail(ctx, C3H_ERR_STATE, "pipeline: internal: geometry changed");
-    return 0;
-  }
-  c->nframes_feat = 1;  // slot 0 is the context's view from here on
-  *fresh = c3h_ctx::PipeBatch{c->cap_c3, c->cap_q, c->cap_sc, nb, 0};
-  fresh->set = c;
-  fresh->layout = c->cap_layout;
-  fresh->replay = !c->cap_argmax;
-  fresh->rp = c->cap_rp;
-  fresh->overlap = overlap_wanted(ctx);
-  if (fresh->overlap) fresh->ro = overlap_args(ctx, k.range, outs, nb);
-  return rc;
-}
-
-// Launches a prepared batch's first tick; rc: pipe_prepare's result (> 0)
-int pipe_commit(c3h_ctx* ctx, const c3h_ctx::PipeBatch& fresh, const c3h_ctx::PipeKey& k, int rc) {
-  if (ctx->pipe.empty()) {
-    // a stream starts: the occupancy role's tail-stealing pool (words 0-1 of each buffer
-    // set's tile flags) resets itself at the end of every launch; zero it here as well, so
-    // a launch that ended early (an aborted stream) cannot leave it counting
-    for (int sidx = 0; sidx < kPipeDepth; ++sidx) {
-      c3h_ctx* c = sidx == 0 ? ctx : (sidx - 1 < (int)ctx->lanes.size() ? ctx->lanes[sidx - 1] : nullptr);
-      if (c && c->tileflags.p && c->tileflags.n >= 2)
-        HIPCHK(hipMemsetAsync(c->tileflags.p, 0, 2 * sizeof(uint32_t), ctx->stream));
-    }
-  }
-  int trc = pipe_tick(ctx, &fresh);
-  if (trc != C3H_OK) return trc;
-  ctx->pipe_seq++;
-  ctx->pipe_key = k;
-  ctx->pipe_nm = rc;
-  return rc;
-}
-
-// Prepares nb frames as the next batch on its buffer set and launches its first tick.
-// Returns as pipe_prepare.
-int pipe_push(c3h_ctx* ctx, const uint32_t* const* grids, c3h_det* const* outs, int nb,
-              const c3h_ctx::PipeKey& k, const int32_t* lim = nullptr) {
-  c3h_ctx::PipeBatch fresh{};
-  const int rc = pipe_prepare(ctx, grids, outs, nb, k, lim, &fresh);
-  if (rc <= 0) return rc;
-  return pipe_commit(ctx, fresh, k, rc);
-}
-
-c3h_ctx::PipeKey pipe_key(c3h_ctx* ctx, const int32_t div_b[3], const int32_t min_b[3], float leaf,
-                          const c3h_extract_params* p, const int32_t range[3], int32_t thr, int32_t rotate,
-                          int B) {
-  c3h_ctx::PipeKey k;
-  memset(&k, 0, sizeof(k));  // compared bytewise
-  memcpy(k.div_b, div_b, sizeof(k.div_b));
-  memcpy(k.min_b, min_b, sizeof(k.min_b));
-  k.leaf = leaf;
-  k.p = *p;
-  memcpy(k.range, range, sizeof(k.range));
-  k.thr = thr;
-  k.rotate = rotate ? 1 : 0;
-  k.batch = B;
-  k.rank = ctx->rank;
-  k.remove_overlap = ctx->remove_overlap;
-  k.setup_version = ctx->setup_version;
-  return k;
-}
-
-// models the tick's score role takes: r <= 64 (either engine), or wide ones on the matrix
-// cores (with c3h_set_score_engine(1) there is no VALU role for them: the lanes)
-bool tick_models_ok(const c3h_ctx* ctx) {
-  return c3h::score_fast_ok(ctx->D, ctx->r) ||
-         (ctx->score_engine != 1 && c3h::score_tick_wide_ok(ctx->D, ctx->M, ctx->r));
-}
-
-bool pipelinable(const c3h_ctx* ctx) {
-  return ctx->pipeline && ctx->rank >= 1 && ctx->rank <= 64 && tick_models_ok(ctx);
-}
-
-// Runs nframes through the pipeline in batches of B.  drain: run the fill/drain ticks so
-// every result is complete on return (c3h_run_frames); the last batch is then placed on
-// set 0 with its last frame in slot 0, so this context holds the last frame's state.
-// Returns as pipe_push.
-int run_frames_pipelined(c3h_ctx* ctx, const uint32_t* const* d_grids, int32_t nframes,
-                         const int32_t div_b[3], const int32_t min_b[3], float leaf,
-                         const c3h_extract_params* p, const int32_t range[3], int32_t exist_threshold,
-                         int32_t rotate, c3h_det* d_out, int B, bool drain) {
-  const size_t per_frame = (size_t)std::max(ctx->M, 1) * ctx->rank;
-  const int nchunks = (nframes + B - 1) / B;
-  int rc = ensure_lanes(ctx, kPipeDepth - 1);
-  if (rc != C3H_OK) return rc;
-  const c3h_ctx::PipeKey k = pipe_key(ctx, div_b, min_b, leaf, p, range, exist_threshold, rotate, B);
-  if (!ctx->pipe.empty() && memcmp(&k, &ctx->pipe_key, sizeof(k)) != 0) {
-    rc = pipe_flush(ctx);  // a different stream: drain the open one first
-    if (rc != C3H_OK) return rc;
-  }
-  PipeScope scope(ctx);
-  if (drain && ctx->pipe.empty())  // the last batch lands on set 0
-    ctx->pipe_seq = (uint64_t)((kPipeDepth - (nchunks - 1) % kPipeDepth) % kPipeDepth);
-  int nm = 0;
-  for (int ch = 0; ch < nchunks; ++ch) {
-    const uint32_t* grids[c3h::kMaxBatch];
-    c3h_det* outs[c3h::kMaxBatch];
-    const int nb = chunk_frames(d_grids, d_out, per_frame, nframes, B, drain ? nchunks : -1, ch, grids, outs);
-    rc = pipe_push(ctx, grids, outs, nb, k);
-    if (rc <= 0) {
-      if (rc == 0 && ch == 0) return 0;
-      ctx->pipe.clear();
-      return rc == 0 ? fail(ctx, C3H_ERR_STATE, "pipeline: internal: batch does not fit") : rc;
-    }
-    nm = rc;
-  }
-  if (drain) {
-    while (!ctx->pipe.empty()) {
-      rc = pipe_tick(ctx, nullptr);
-      if (rc != C3H_OK) {
-        ctx->pipe.clear();
-        return rc;
-      }
-    }
-  }
-  return nm;
-}
-
-}  // namespace
-
-extern "C" {
-
-int c3h_run_frames(c3h_ctx* ctx, const uint32_t* const* d_grids, int32_t nframes,
-                   const int32_t div_b[3], const int32_t min_b[3], float leaf,
-                   const c3h_extract_params* p, const int32_t range[3], int32_t exist_threshold,
-                   int32_t rotate, c3h_det* d_out) {
-  if (!ctx || !d_grids || nframes < 0 || !div_b || !min_b || !p || !range || !d_out)
-    return C3H_ERR_ARG;
-  if (!ctx->have_setup) return fail(ctx, C3H_ERR_STATE, "c3h_run_frames: no axes (call c3h_search_setup)");
-  if (!extract_params_ok(p)) return fail(ctx, C3H_ERR_ARG, "c3h_run_frames: variant / color_mode");
-  if (int rc = overlap_rank_check(ctx, "c3h_run_frames")) return rc;
-  HIPCHK(hipSetDevice(ctx->device));
-  {
-    int rc = pipe_flush(ctx);  // an open stream completes first
-    if (rc != C3H_OK) return rc;
-  }
-  if (nframes == 0) return 0;
-  const size_t per_frame = (size_t)std::max(ctx->M, 1) * ctx->rank;
-  // frames go in chunks of B (one set of launches per chunk, frame = launch y / z index)
-  const int Bset = std::max(1, std::min(ctx->nbatch, c3h::kMaxBatch));
-  if (pipelinable(ctx)) {
-    const int rc = run_frames_pipelined(ctx, d_grids, nframes, div_b, min_b, leaf, p, range, exist_threshold,
-                                        rotate, d_out, Bset, true);
-    if (rc != 0) return rc;
-  }
-  // the lanes' multi-frame launch is the VALU list kernel's: wide models (r > 64) go one frame
-  // per chunk there, whatever batch the pipeline was offered
-  const int B = c3h::score_fast_ok(ctx->D, ctx->r) ? Bset : 1;
-  const int nchunks = (nframes + B - 1) / B;
-  // lanes: chunks are spread over K child contexts on their own streams and host threads
-  const int K = std::max(1, std::min(ctx->nlanes, nchunks));
-  {
-    int rc = ensure_lanes(ctx, K - 1);
-    if (rc != C3H_OK) return rc;
-  }
-  if (!ctx->fork_ev) HIPCHK(hipEventCreateWithFlags(&ctx->fork_ev, hipEventDisableTiming));
-  HIPCHK(hipEventRecord(ctx->fork_ev, ctx->stream));  // inputs were produced on ctx's stream
-  for (int l = 0; l < K - 1; ++l) HIPCHK(hipStreamWaitEvent(ctx->lanes[l]->stream, ctx->fork_ev, 0));
-  std::vector<int> lane_rc(K, 0);
-  auto run_lane = [&](int lane) {
-    c3h_ctx* c = lane == 0 ? ctx : ctx->lanes[lane - 1];
-    if (lane) (void)hipSetDevice(c->device);
-    int nm_lane = 0;
-    for (int ch = 0; ch < nchunks; ++ch) {
-      if ((nchunks - 1 - ch) % K != lane) continue;
-      const uint32_t* grids[c3h::kMaxBatch];
-      c3h_det* outs[c3h::kMaxBatch];
-      const int nb = chunk_frames(d_grids, d_out, per_frame, nframes, B, nchunks, ch, grids, outs);
-      int rc = c3h_set_grid(c, grids[0], div_b, min_b, leaf, 1);
-      if (rc == C3H_OK) rc = extract_frames(c, grids, nb, p, nullptr, nullptr);
-      if (rc == C3H_OK) rc = search_frames(c, nb, range, exist_threshold, rotate, outs, 2);
-      if (rc >= 0 && overlap_wanted(ctx)) {
-        const hipError_t e = c3h::launch_remove_overlap_frames(overlap_args(ctx, range, outs, nb), c->stream);
-        if (e != hipSuccess) rc = hip_fail(c, "launch_remove_overlap_frames", e);
-      }
-      if (rc < 0) {
-        lane_rc[lane] = rc;
-        return;
-      }
-      nm_lane = rc;
-      c->nframes_feat = 1;  // slot 0 is the context's view from here on
-    }
-    lane_rc[lane] = nm_lane;
-  };
-  std::vector<std::thread> workers;
-  for (int l = 1; l < K; ++l) workers.emplace_back(run_lane, l);
-  run_lane(0);
-  for (auto& w : workers) w.join();
-  for (int l = 1; l < K; ++l)
-    if (lane_rc[l] < 0) return fail(ctx, lane_rc[l], std::string("c3h_run_frames lane: ") + ctx->lanes[l - 1]->err);
-  if (lane_rc[0] < 0) return lane_rc[0];
-  for (int l = 0; l < K - 1; ++l) {  // join
-    HIPCHK(hipEventRecord(ctx->lane_ev[l], ctx->lanes[l]->stream));
-    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->lane_ev[l], 0));
-  }
-  return lane_rc[0];
-}
-
-int c3h_stream_frames(c3h_ctx* ctx, const uint32_t* const* d_grids, int32_t nframes,
-                      const int32_t div_b[3], const int32_t min_b[3], float leaf,
-                      const c3h_extract_params* p, const int32_t range[3], int32_t exist_threshold,
-                      int32_t rotate, c3h_det* d_out) {
-  if (!ctx || !d_grids || nframes < 0 || !div_b || !min_b || !p || !range || !d_out)
-    return C3H_ERR_ARG;
-  if (!ctx->have_setup) return fail(ctx, C3H_ERR_STATE, "c3h_stream_frames: no axes (call c3h_search_setup)");
-  if (!extract_params_ok(p)) return fail(ctx, C3H_ERR_ARG, "c3h_stream_frames: variant / color_mode");
-  if (int rc = overlap_rank_check(ctx, "c3h_stream_frames")) return rc;
-  if (nframes == 0) return ctx->pipe_nm;
-  HIPCHK(hipSetDevice(ctx->device));
-  const int B = std::max(1, std::min(ctx->nbatch, c3h::kMaxBatch));
-  if (pipelinable(ctx)) {
-    const int rc = run_frames_pipelined(ctx, d_grids, nframes, div_b, min_b, leaf, p, range, exist_threshold,
-                                        rotate, d_out, B, false);
-    if (rc != 0) return rc;
-  }
-  // not pipelinable: the frames complete as in c3h_run_frames
-  return c3h_run_frames(ctx, d_grids, nframes, div_b, min_b, leaf, p, range, exist_threshold, rotate, d_out);
-}
-
-int c3h_stream_flush(c3h_ctx* ctx) {
-  if (!ctx) return C3H_ERR_ARG;
-  HIPCHK(hipSetDevice(ctx->device));
-  return pipe_flush(ctx);
-}
-
-}  // extern "C"
-
-namespace {
-
-// ---- feature-rows batches (c3h_run_feature_frames) -------------------------------------
-// A batch of caller-computed rows enters the pipeline at the compress + gate slot: its front
-// kernel (feat_front.hip), one launch ahead of the batch's first tick, writes the buffer set's
-// exist values, has-data words, row list and feature rows on the canvas layout, which is all
-// the tick's later roles read of an extract.
-
-// the buffer set's state and buffers for nb frames of `dim` floats on a canvas of H rows: an
-// extract of nb frames whose non-empty rows are listed
-int feature_set_state(c3h_ctx* ctx, int nb, int64_t H, int dim, const int32_t canvas[3]) {
-  ctx->have_feat = false;
-  ctx->feat16_pending = false;
-  ctx->g_valid = false;
-  ctx->g_sparse = false;
-  ctx->feat_sparse = false;
-  ctx->exist_gates_rows = false;
-  ENSURE(ctx->feat, (size_t)nb * H * dim);
-  ENSURE(ctx->exist, (size_t)nb * H);
-  ENSURE(ctx->rows, (size_t)nb * H);
-  ENSURE(ctx->ff_has, (size_t)nb * H);
-  ENSURE(ctx->ff_cnt, (size_t)c3h::kMaxBatch);
-  ENSURE(ctx->ff_lim, (size_t)c3h::kMaxBatch * 4);
-  ctx->hist_num = H;
-  ctx->feat_dim = dim;
-  for (int a = 0; a < 3; ++a) ctx->subdiv_b[a] = canvas[a];
-  ctx->nframes_feat = nb;
-  ctx->rows_valid = true;
-  ctx->feat_listed = true;
-  ctx->have_feat = true;
-  return C3H_OK;
-}
-
-// Captures nb frames of rows as the next batch on its buffer set and enqueues its front
-// kernel.  Returns as pipe_prepare: > 0 modes searched, 0 when the configuration does not fit
-// the tick (nothing was enqueued), < 0 on error.
-int feature_prepare(c3h_ctx* ctx, const float* const* feats, const int32_t* const* exists,
-                    const int32_t* const* sbs, c3h_det* const* outs, int nb, const c3h_ctx::PipeKey& k,
-                    c3h_ctx::PipeBatch* fresh) {
-  c3h_ctx* c = pipe_set(ctx, ctx->pipe_seq);
-  const int64_t H = (int64_t)k.div_b[0] * k.div_b[1] * k.div_b[2];
-  int rc = feature_set_state(c, nb, H, k.dim, k.div_b);
-  if (rc == C3H_OK) {
-    c->capture = true;
-    c->cap_c3_valid = c->cap_search_valid = false;
-    rc = search_frames(c, nb, k.range, k.thr, k.rotate, outs, 2);
-    c->capture = false;
-  }
-  if (rc < 0) {
-    c->have_feat = false;
-    if (c != ctx) ctx->err = c->err;
-    return rc;
-  }
-  const bool ranked = c->cap_argmax || (c->cap_replay && c->rank >= 2 && !c->cap_q.lists && !c->cap_q.partials);
-  if (!(rc > 0 && c->cap_search_valid && c->cap_sparse_g && ranked)) {  // one geometry per stream
-    c->have_feat = false;
-    if (!ctx->pipe.empty()) return fail(ctx, C3H_ERR_STATE, "pipeline: internal: geometry changed");
-    return 0;
-  }
-  c->nframes_feat = 1;  // slot 0 is the context's view from here on
-  c3h::FeatFront ff{};
-  for (int j = 0; j < nb; ++j) {
-    ff.feat[j] = feats[j];
-    ff.exist_in[j] = exists ? exists[j] : nullptr;
-    for (int a = 0; a < 3; ++a) ff.sb[j][a] = sbs[j][a];
-  }
-  ff.nf = nb;
-  ff.dim = k.dim;
-  ff.rule = k.rule < 0 ? 0 : k.rule;
-  ff.R = c3h::fr_block_rows(k.dim);
-  ff.magic = c3h::fr_div_magic(k.dim);
-  for (int a = 0; a < 3; ++a) ff.cb[a] = k.div_b[a];
-  ff.out = c->feat.p;
-  ff.exist = c->exist.p;
-  ff.has = c->ff_has.p;
-  ff.rows = c->rows.p;
-  ff.cnt = c->ff_cnt.p;
-  ff.lim = c->ff_lim.p;
-  ff.s_out = H * k.dim;
-  ff.s_h = H;
-  // (the set's previous batch left the pipeline two batches ago: stream order covers its reads)
-  HIPCHK(hipMemsetAsync(c->ff_cnt.p, 0, (size_t)c3h::kMaxBatch * sizeof(uint32_t), ctx->stream));
-  {
-    Timed t(ctx, 1, nb);
-    HIPCHK(c3h::launch_feat_front(ff, ctx->stream));
-  }
-  *fresh = c3h_ctx::PipeBatch{c3h::C3Launch{}, c->cap_q, c->cap_sc, nb, 0};
-  fresh->rows_in = true;
-  // the gate role: the true exist values, positions bounded by each frame's own counts
-  fresh->q.lim = c->ff_lim.p;
-  fresh->q.score_engine = ctx->score_engine;
-  // the compress role: the front kernel's list (its counters in place of the extract's)
-  fresh->sc.nrows = c->ff_cnt.p;
-  fresh->sc.s_nrows = 1;
-  // the score role skips rows by the has-data words: exist 0 does not mean an empty row here
-  fresh->qs = fresh->q;
-  fresh->qs.exist = c->ff_has.p;
-  fresh->qs.skip_empty = 1;
-  fresh->set = c;
-  fresh->layout = c->cap_layout;
-  fresh->replay = !c->cap_argmax;
-  fresh->rp = c->cap_rp;
-  fresh->overlap = overlap_wanted(ctx);
-  if (fresh->overlap) fresh->ro = overlap_args(ctx, k.range, outs, nb);
-  return rc;
-}
-
-c3h_ctx::PipeKey feature_key(c3h_ctx* ctx, const int32_t canvas[3], int dim, int rule, const int32_t range[3],
-                             int32_t thr, int32_t rotate, int B) {
-  c3h_ctx::PipeKey k;
-  memset(&k, 0, sizeof(k));  // compared bytewise
-  memcpy(k.div_b, canvas, sizeof(k.div_b));
-  memcpy(k.range, range, sizeof(k.range));
-  k.thr = thr;
-  k.rotate = rotate ? 1 : 0;
-  k.batch = B;
-  k.rank = ctx->rank;
-  k.remove_overlap = ctx->remove_overlap;
-  k.rows_in = 1;
-  k.dim = dim;
-  k.rule = rule;  // -1: the caller's exist arrays
-  k.setup_version = ctx->setup_version;
-  return k;
-}
-
-// nframes through the pipeline in batches of B (as run_frames_pipelined).  Returns > 0 modes
-// searched, 0 when the configuration does not fit the tick (nothing was enqueued), < 0 on error.
-int feature_frames_pipelined(c3h_ctx* ctx, const float* const* d_feat, const int32_t* const* d_exist,
-                             int32_t nframes, const int32_t* subdiv_b, const int32_t canvas[3], int dim,
-                             int rule, const int32_t range[3], int32_t thr, int32_t rotate, c3h_det* d_out,
-                             int B, bool drain) {
-  const size_t per_frame = (size_t)std::max(ctx->M, 1) * ctx->rank;
-  const int nchunks = (nframes + B - 1) / B;
-  int rc = ensure_lanes(ctx, kPipeDepth - 1);
-  if (rc != C3H_OK) return rc;
-  const c3h_ctx::PipeKey k = feature_key(ctx, canvas, dim, d_exist ? -1 : rule, range, thr, rotate, B);
-  if (!ctx->pipe.empty() && memcmp(&k, &ctx->pipe_key, sizeof(k)) != 0) {
-    rc = pipe_flush(ctx);  // a different stream: drain the open one first
-    if (rc != C3H_OK) return rc;
-  }
-  PipeScope scope(ctx);
-  if (drain && ctx->pipe.empty())  // the last batch lands on set 0
-    ctx->pipe_seq = (uint64_t)((kPipeDepth - (nchunks - 1) % kPipeDepth) % kPipeDepth);
-  int nm = 0;
-  for (int ch = 0; ch < nchunks; ++ch) {
-    const float* feats[c3h::kMaxBatch];
-    const int32_t* exists[c3h::kMaxBatch];
-    const int32_t* sbs[c3h::kMaxBatch];
-    c3h_det* outs[c3h::kMaxBatch];
-    const int f0 = ch * B, nb = std::min(B, nframes - f0);
-    for (int j = 0; j < nb; ++j) {  // a draining call's last batch puts its last frame in slot 0
-      const int fi = (drain && ch == nchunks - 1) ? (j == 0 ? f0 + nb - 1 : f0 + j - 1) : f0 + j;
-      feats[j] = d_feat[fi];
-      exists[j] = d_exist ? d_exist[fi] : nullptr;
-      sbs[j] = subdiv_b + 3 * fi;
-      outs[j] = d_out + (size_t)fi * per_frame;
-    }
-    c3h_ctx::PipeBatch fresh{};
-    rc = feature_prepare(ctx, feats, d_exist ? exists : nullptr, sbs, outs, nb, k, &fresh);
-    if (rc > 0) rc = pipe_commit(ctx, fresh, k, rc);
-    if (rc <= 0) {
-      if (rc == 0 && ch == 0) return 0;
-      ctx->pipe.clear();
-      return rc == 0 ? fail(ctx, C3H_ERR_STATE, "pipeline: internal: batch does not fit") : rc;
-    }
-    nm = rc;
-  }
-  if (drain) {
-    while (!ctx->pipe.empty()) {
-      rc = pipe_tick(ctx, nullptr);
-      if (rc != C3H_OK) {
-        ctx->pipe.clear();
-        return rc;
-      }
-    }
-  }
-  return nm;
-}
-
-int feature_frames(c3h_ctx* ctx, const float* const* d_feat, const int32_t* const* d_exist, int32_t nframes,
-                   const int32_t* subdiv_b, const int32_t canvas_b[3], int32_t dim, int32_t exist_rule,
-                   const int32_t range[3], int32_t thr, int32_t rotate, c3h_det* d_out, bool stream) {
-  const char* who = stream ? "c3h_stream_feature_frames" : "c3h_run_feature_frames";
-  if (!ctx || !d_feat || nframes < 0 || (nframes > 0 && !subdiv_b) || !canvas_b || !range || !d_out || dim <= 0)
-    return C3H_ERR_ARG;
-  if (!ctx->have_setup) return fail(ctx, C3H_ERR_STATE, std::string(who) + ": no axes (call c3h_search_setup)");
-  if (!d_exist && (exist_rule < 0 || exist_rule > 2)) return fail(ctx, C3H_ERR_ARG, std::string(who) + ": exist rule");
-  if (!d_exist && dim < c3h::fr_exist_min_dim(exist_rule))
-    return fail(ctx, C3H_ERR_ARG, std::string(who) + ": the exist rule needs more columns (VOSCH 22, GRSD 20, C3-HLAC 2)");
-  if (dim != ctx->F) return fail(ctx, C3H_ERR_ARG, std::string(who) + ": feature dimension differs from the scene axis");
-  if (range[0] < 1 || range[1] < 1 || range[2] < 1) return fail(ctx, C3H_ERR_ARG, std::string(who) + ": ranges must be >= 1");
-  if (int rc = overlap_rank_check(ctx, who)) return rc;
-  int64_t H = 1;
-  for (int a = 0; a < 3; ++a) {
-    if (canvas_b[a] < 0) return fail(ctx, C3H_ERR_ARG, std::string(who) + ": canvas_b");
-    H *= canvas_b[a];
-  }
-  if (H > INT32_MAX) return fail(ctx, C3H_ERR_RANGE, std::string(who) + ": canvas beyond int32 row indices");
-  for (int i = 0; i < nframes; ++i) {
-    int64_t h = 1;
-    for (int a = 0; a < 3; ++a) {
-      const int32_t n = subdiv_b[3 * i + a];
-      if (n < 0 || n > canvas_b[a]) return fail(ctx, C3H_ERR_ARG, std::string(who) + ": a frame's subdiv_b exceeds canvas_b");
-      h *= n;
-    }
-    if (h > 0 && (!d_feat[i] || ((uintptr_t)d_feat[i] & 3) || (d_exist && (!d_exist[i] || ((uintptr_t)d_exist[i] & 3)))))
-      return fail(ctx, C3H_ERR_ARG, std::string(who) + ": frame pointers must be device pointers aligned to 4 bytes");
-  }
-  HIPCHK(hipSetDevice(ctx->device));
-  if (!stream) {
-    int rc = pipe_flush(ctx);  // an open stream completes first
-    if (rc != C3H_OK) return rc;
-  }
-  int modes[6];
-  const int nm_sched = mode_schedule(range[0], range[1], range[2], rotate, modes);
-  if (nframes == 0) return stream ? ctx->pipe_nm : 0;
-  const size_t per_frame = (size_t)std::max(ctx->M, 1) * ctx->rank;
-  const int B = std::max(1, std::min(ctx->nbatch, c3h::kMaxBatch));
-  if (H > 0 && pipelinable(ctx) && c3h::feat_front_ok(dim)) {
-    const int rc = feature_frames_pipelined(ctx, d_feat, d_exist, nframes, subdiv_b, canvas_b, dim, exist_rule, range,
-                                            thr, rotate, d_out, B, !stream);
-    if (rc != 0) return rc;
-  }
-  // Routes the tick does not take (c3h_set_pipeline(0), rank > 64, models or axes it has no
-  // role for): frame by frame as a caller would, c3h_set_features + a search from the setRank
-  // state into the frame's slot, in the frame's own layout
-  {
-    int rc = pipe_flush(ctx);
-    if (rc != C3H_OK) return rc;
-  }
-  for (int i = 0; i < nframes; ++i) {
-    c3h_det* out = d_out + (size_t)i * per_frame;
-    int rc = c3h_set_features(ctx, d_feat[i], subdiv_b + 3 * i, dim, d_exist ? d_exist[i] : nullptr, exist_rule, 1);
-    if (rc == C3H_OK) rc = c3h_set_rank(ctx, ctx->rank);
-    if (rc == C3H_OK) rc = c3h_search_async(ctx, range, thr, rotate, out);
-    if (rc >= 0 && overlap_wanted(ctx)) {
-      const hipError_t e = c3h::launch_remove_overlap_frames(overlap_args(ctx, range, &out, 1), ctx->stream);
-      if (e != hipSuccess) rc = hip_fail(ctx, "launch_remove_overlap_frames", e);
-    }
-    if (rc < 0) return rc;
-  }
-  return nm_sched;
-}
-
-}  // namespace
-
-extern "C" {
-
-int c3h_run_feature_frames(c3h_ctx* ctx, const float* const* d_feat, const int32_t* const* d_exist,
-                           int32_t nframes, const int32_t* subdiv_b, const int32_t canvas_b[3], int32_t dim,
-                           int32_t exist_rule, const int32_t range[3], int32_t exist_threshold, int32_t rotate,
-                           c3h_det* d_out) {
-  return feature_frames(ctx, d_feat, d_exist, nframes, subdiv_b, canvas_b, dim, exist_rule, range, exist_threshold,
-                        rotate, d_out, false);
-}
-
-int c3h_stream_feature_frames(c3h_ctx* ctx, const float* const* d_feat, const int32_t* const* d_exist,
-                              int32_t nframes, const int32_t* subdiv_b, const int32_t canvas_b[3], int32_t dim,
-                              int32_t exist_rule, const int32_t range[3], int32_t exist_threshold, int32_t rotate,
-                              c3h_det* d_out) {
-  return feature_frames(ctx, d_feat, d_exist, nframes, subdiv_b, canvas_b, dim, exist_rule, range, exist_threshold,
-                        rotate, d_out, true);
-}
-
-}  // extern "C"
-
-namespace {
-
-// One frame on the single-frame path (c3h_voxelize + c3h_extract + search from the setRank
-// state) into d_out_f: the frames c3h_run_point_frames' canvas cannot reproduce exactly.
-int point_frame_single(c3h_ctx* ctx, const float* pts, int64_t n, int on_device, float leaf, float z_limit,
-                       const c3h_extract_params* p, const int32_t range[3], int32_t thr, int32_t rotate,
-                       c3h_det* d_out_f, c3h_frame_info* fi) {
-  const size_t per_frame = (size_t)std::max(ctx->M, 1) * ctx->rank;
-  HIPCHK(hipMemsetAsync(d_out_f, 0, per_frame * sizeof(c3h_det), ctx->stream));  // fresh lists
-  c3h_grid_info gi{};
-  int rc = c3h_voxelize(ctx, pts, n, on_device, leaf, z_limit, &gi);
-  int32_t sb[3] = {0, 0, 0};
-  if (rc == C3H_OK) rc = extract_frames(ctx, &ctx->grid_ptr, 1, p, sb, nullptr);
-  if (rc == C3H_OK) rc = search_frames(ctx, 1, range, thr, rotate, &d_out_f, 2);
-  if (rc >= 0 && overlap_wanted(ctx)) {
-    const hipError_t e = c3h::launch_remove_overlap_frames(overlap_args(ctx, range, &d_out_f, 1), ctx->stream);
-    if (e != hipSuccess) rc = hip_fail(ctx, "launch_remove_overlap_frames", e);
-  }
-  if (fi) {
-    memset(fi, 0, sizeof(*fi));
-    if (rc >= 0) {
-      for (int a = 0; a < 3; ++a) {
-        fi->div_b[a] = gi.div_b[a];
-        fi->min_b[a] = gi.min_b[a];
-        fi->subdiv_b[a] = sb[a];
-      }
-      fi->n_valid = gi.n_valid;
-      fi->n_occ = gi.n_occ;
-    }
-    fi->status = rc >= 0 ? 1 : rc;
-  }
-  return rc < 0 ? rc : C3H_OK;
-}
-
-// Where the frames of a points-in call come from: packed x y z rgb float arrays
-// (c3h_run_point_frames) or sensor_msgs/PointCloud2 messages the batched voxeliser reads in
-// place (c3h_run_pointcloud2_frames: layout != nullptr).  base[i] is frame i's pts[i] or
-// data[i], n[i] its points.
-struct PointSrc {
-  std::string who;
-  const void* const* base = nullptr;
-  const int64_t* n = nullptr;
-  int32_t nframes = 0;
-  int on_device = 0;
-  const c3h_pc2_layout* layout = nullptr;
-  const uint32_t *height = nullptr, *width = nullptr, *row_step = nullptr;
-  c3h::Pc2Plan plan{};
-  // the bytes of frame i (what a host frame's staging copy moves)
-  size_t bytes(int i) const {
-    return layout ? (size_t)c3h::pc2_msg_bytes(height[i], width[i], layout->point_step, row_step[i]) : (size_t)n[i] * 16;
-  }
-  // the batch's staging buffer: frames follow each other at 16-byte aligned offsets
-  static size_t staged(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-};
-
-// Frame i on the single-frame path.  A message is converted by the single-frame path's own
-// converter into the context's point buffer first (c3h_voxelize_pointcloud2's steps).
-int point_src_single(c3h_ctx* ctx, const PointSrc& s, int i, float leaf, float z_limit, const c3h_extract_params* p,
-                     const int32_t range[3], int32_t thr, int32_t rotate, c3h_det* d_out_f, c3h_frame_info* fi) {
-  if (!s.layout)
-    return point_frame_single(ctx, static_cast<const float*>(s.base[i]), s.n[i], s.on_device, leaf, z_limit, p, range,
-                              thr, rotate, d_out_f, fi);
-  const void* msg = s.base[i];
-  const size_t bytes = s.bytes(i);
-  if (bytes > 0 && !s.on_device) {
-    ENSURE(ctx->raw, (bytes + 3) / 4);
-    HIPCHK(hipMemcpyAsync(ctx->raw.p, msg, bytes, hipMemcpyHostToDevice, ctx->stream));
-    msg = ctx->raw.p;
-  }
-  ENSURE(ctx->pts, (size_t)std::max<int64_t>(s.n[i], 1) * 4);
-  const uint32_t ps = s.layout->point_step;
-  HIPCHK(c3h::launch_pc2_convert(msg, s.height[i], s.width[i], ps, s.height[i] > 1 ? s.row_step[i] : s.width[i] * ps,
-                                 s.layout->offsets, s.layout->is_bigendian ? 1 : 0, ctx->pts.p, ctx->stream));
-  return point_frame_single(ctx, ctx->pts.p, s.n[i], 1, leaf, z_limit, p, range, thr, rotate, d_out_f, fi);
-}
-
-// Points-in batches: the scatter stamps the tick's tiles (a canvas that does not match the
-// grid: the tick streams the canvases), and flagged voxels are summed exactly and off-cell
-// voxels fixed up in the batch.  The body of both points-in entry points.
-int run_point_source(c3h_ctx* ctx, const PointSrc& src, float leaf, float z_limit, const int32_t canvas[3],
-                     const c3h_extract_params* p, const int32_t range[3], int32_t exist_threshold, int32_t rotate,
-                     c3h_det* d_out, c3h_frame_info* info) {
-  const int32_t nframes = src.nframes;
-  const int on_device = src.on_device;
-  const int64_t* n = src.n;
-  const std::string& who = src.who;
-  if (p->variant != 981 && p->variant != 117) return fail(ctx, C3H_ERR_ARG, who + ": variant");
-  if (p->color_mode < C3H_COLOR_C3_FLOAT || p->color_mode > C3H_COLOR_CHLAC)
-    return fail(ctx, C3H_ERR_ARG, who + ": color_mode");
-  if (int rc = overlap_rank_check(ctx, who.c_str())) return rc;
-  int64_t cvox = 1;
-  for (int a = 0; a < 3; ++a) {
-    if (canvas[a] < 1) return fail(ctx, C3H_ERR_ARG, who + ": canvas dims must be >= 1");
-    cvox *= canvas[a];
-  }
-  if (cvox > 2147483647LL) return fail(ctx, C3H_ERR_RANGE, who + ": canvas beyond int32 voxel indices");
-  HIPCHK(hipSetDevice(ctx->device));
-  {
-    int rc = pipe_flush(ctx);  // an open frame stream completes first
-    if (rc != C3H_OK) return rc;
-  }
-  if (nframes == 0) return 0;
-  const size_t per_frame = (size_t)std::max(ctx->M, 1) * ctx->rank;
-  std::vector<c3h_frame_info> fi((size_t)nframes);
-  std::vector<char> redo((size_t)nframes, 1);
-  int nm = 0;
-  std::vector<char> exact_ran((size_t)nframes, 0);  // per frame: its batch ran the exact pass + fixup
-  // canvas subdivisions: a frame with one subdivision where the canvas has several takes the
-  // single-frame path (computeC3HLAC's hist_num == 1 rule puts every voxel in histogram 0)
-  bool canvas_multi = false;
-  if (p->subdiv > 0) {
-    const float inv_s = 1.0 / p->subdiv;
-    int64_t hn = 1;
-    for (int a = 0; a < 3; ++a) hn *= canvas[a] > p->offset[a] ? (int64_t)ceilf((canvas[a] - p->offset[a]) * inv_s) : 0;
-    canvas_multi = hn > 1;
-  }
-  const bool batched = pipelinable(ctx) && p->subdiv >= 0 && p->thr[0] >= 0 && p->thr[1] >= 0 && p->thr[2] >= 0;
-  if (batched) {
-    const int B = std::max(1, std::min(ctx->nbatch, c3h::kMaxBatch));
-    const int nchunks = (nframes + B - 1) / B;
-    const int chunk = c3h::vb_chunk();
-    int rc = ensure_lanes(ctx, kPipeDepth - 1);
-    if (rc != C3H_OK) return rc;
-    const int32_t zero[3] = {0, 0, 0};
-    const c3h_ctx::PipeKey k = pipe_key(ctx, canvas, zero, leaf, p, range, exist_threshold, rotate, B);
-    // shared: toroidal accumulators (one per frame slot; the scatter returns them to zero),
-    // voxel lists, the frames' records, host staging
-    // toroidal accumulator dims: powers of two >= the canvas (a frame whose extent fits the
-    // canvas never wraps onto itself; the index is then three masks and shifts)
-    int tb[3];
-    int64_t tvox = 1;
-    for (int a = 0; a < 3; ++a) {
-      tb[a] = 0;
-      while ((1 << tb[a]) < canvas[a]) ++tb[a];
-      tvox <<= tb[a];
-    }
-    if (tvox > ((int64_t)1 << 31)) return fail(ctx, C3H_ERR_RANGE, who + ": canvas too large");
-    if (ctx->pb_acc_vox != tvox || ctx->pb_acc_slots < B) {
-      ENSURE(ctx->pb_acc, (size_t)B * tvox);
-      ENSURE(ctx->pb_accM, (size_t)B * tvox);
-      ENSURE(ctx->pb_fcnt, (size_t)c3h::kMaxBatch);
-      HIPCHK(hipMemsetAsync(ctx->pb_acc.p, 0, (size_t)B * tvox * 16, ctx->stream));
-      HIPCHK(hipMemsetAsync(ctx->pb_accM.p, 0xff, (size_t)B * tvox * 4, ctx->stream));
-      HIPCHK(hipMemsetAsync(ctx->pb_fcnt.p, 0, (size_t)c3h::kMaxBatch * 4, ctx->stream));
-      ctx->pb_acc_vox = tvox;
-      ctx->pb_acc_slots = B;
-    }
-    ENSURE(ctx->pb_info, (size_t)nframes);
-    // shared buffers sized for the largest batch up front: the voxeliser stream may still be
-    // reading them while the next batch is prepared
-    {
-      int64_t max_blk = 1;
-      size_t max_bytes = 16;
-      for (int ch = 0; ch < nchunks; ++ch) {
-        int64_t b = 0;
-        size_t q = 0;
-        for (int j = ch * B; j < std::min(nframes, (ch + 1) * B); ++j) {
-          b += std::max<int64_t>(1, (n[j] + chunk - 1) / chunk);
-          q += PointSrc::staged(src.bytes(j));
-        }
-        max_blk = std::max(max_blk, b);
-        max_bytes = std::max(max_bytes, q);
-      }
-      if (max_blk > INT_MAX / chunk) return fail(ctx, C3H_ERR_RANGE, who + ": batch too large");
-      ENSURE(ctx->pb_vlist, (size_t)max_blk * chunk);
-      if (!on_device) {  // the messages' raw bytes have a byte buffer of their own
-        if (src.layout) ENSURE(ctx->pb_raw, max_bytes);
-        else ENSURE(ctx->pb_stage, max_bytes / 4);
-      }
-    }
-    if (!ctx->pb_vstream) {
-      // the voxeliser's stream is the points-in call's critical path (its accumulate runs
-      // beside the tick of the batches before, which has slack): high priority, so its
-      // workgroups are dispatched first as CUs free up
-      int lo = 0, hi = 0;
-      if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo)
-        HIPCHK(hipStreamCreateWithPriority(&ctx->pb_vstream, hipStreamNonBlocking, hi));
-      else
-        HIPCHK(hipStreamCreateWithFlags(&ctx->pb_vstream, hipStreamNonBlocking));
-    }
-    if (!ctx->pb_vox_ev) HIPCHK(hipEventCreateWithFlags(&ctx->pb_vox_ev, hipEventDisableTiming));
-    for (hipEvent_t& e : ctx->pb_tick_ev)
-      if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    // overlap pays where the tick is light: 512 x 128^3 frames 51k -> 74k frames/s.  While
-    // the tick streamed the canvases, 256^3 lost with it (33k -> 30k: the 67 MB grid stream
-    // and the voxeliser's atomics slowed each other down, profiles/r3/points_overlap/); with
-    // the scatter's stamps (no canvas stream) it gains there too: 41k -> 45k frames/s
-    // (profiles/r3/point_stamp/).  Canvases up to 2^25 voxels (256^3 and a little beyond)
-#ifndef C3H_POINT_OVERLAP_VOX
-#define C3H_POINT_OVERLAP_VOX (1 << 25)
-#endif
-    const bool overlap = cvox <= (int64_t)C3H_POINT_OVERLAP_VOX;
-    const hipStream_t vs = overlap ? ctx->pb_vstream : ctx->stream;
-    // every exit (errors included) leaves the voxeliser stream idle: the next call may
-    // reallocate the buffers its work reads
-    struct VsIdle {
-      hipStream_t s;
-      ~VsIdle() { (void)hipStreamSynchronize(s); }
-    } vs_idle{vs};
-    // the voxeliser stream starts after everything enqueued so far (the memsets above)
-    HIPCHK(hipEventRecord(ctx->pb_vox_ev, ctx->stream));
-    HIPCHK(hipStreamWaitEvent(vs, ctx->pb_vox_ev, 0));
-    PipeScope scope(ctx);
-    for (int ch = 0; ch < nchunks && rc >= 0; ++ch) {
-      const int f0 = ch * B, nb = std::min(B, nframes - f0);
-      c3h_ctx* c = pipe_set(ctx, ctx->pipe_seq);
-      c3h::VoxBatchArgs va{};
-      va.nf = nb;
-      va.blk0[0] = 0;
-      for (int j = 0; j < nb; ++j) {  // every frame at least one block: it publishes the record
-        va.n[j] = n[f0 + j];
-        va.blk0[j + 1] = va.blk0[j] + (int)std::max<int64_t>(1, (n[f0 + j] + chunk - 1) / chunk);
-      }
-      va.total = va.blk0[nb];
-      // this set's buffers; a reallocation loses the previous batch's word lists, so the
-      // canvas grids are then zeroed whole
-      const int blk_cap = (int)std::min<int64_t>(c->pb_part.n / c3h::vox_part_words(), INT_MAX);
-      if (c->pb_cvox != cvox || c->pb_slots < B || blk_cap < va.total) {
-        // (re)allocation: nothing in flight may still use the set's old buffers
-        HIPCHK(hipStreamSynchronize(vs));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        const int bc = std::max(va.total, blk_cap);
-        ENSURE(c->pb_grid, (size_t)B * cvox);
-        ENSURE(c->pb_lim, (size_t)B * 4);
-        ENSURE(c->pb_part, (size_t)bc * c3h::vox_part_words());
-        ENSURE(c->pb_wlist, (size_t)bc * chunk);
-        ENSURE(c->pb_flags, (size_t)B * c3h::kVbFlagCap);
-        ENSURE(c->pb_bucket, (size_t)B * c3h::kVbBucketCap);
-        ENSURE(c->pb_moved, (size_t)B * c3h::kVbMovedCap);
-        ENSURE(c->pb_xcnt, (size_t)B * 4);
-        HIPCHK(hipMemsetAsync(c->pb_grid.p, 0, (size_t)B * cvox * 4, vs));
-        c->pb_cvox = cvox;
-        c->pb_slots = B;
-        c->pb_prev_total = 0;
-        c->pb_prev_nf = 0;
-      }
-      va.prev_nf = c->pb_prev_nf;
-      va.prev_total = c->pb_prev_total;
-      for (int j = 0; j <= c3h::kMaxBatch; ++j)
-        va.prev_blk0[j] = j < (int)c->pb_prev_blk0.size() ? c->pb_prev_blk0[j] : va.prev_total;
-      if (on_device) {
-        for (int j = 0; j < nb; ++j) va.pts[j] = static_cast<const float4*>(src.base[f0 + j]);
-      } else {  // host frames: one staging copy per batch, ordered on the voxeliser stream
-        uint8_t* stage = src.layout ? ctx->pb_raw.p : reinterpret_cast<uint8_t*>(ctx->pb_stage.p);
-        size_t o = 0;
-        for (int j = 0; j < nb; ++j) {
-          va.pts[j] = reinterpret_cast<const float4*>(stage + o);
-          const size_t bytes = src.bytes(f0 + j);
-          if (bytes > 0) HIPCHK(hipMemcpyAsync(stage + o, src.base[f0 + j], bytes, hipMemcpyHostToDevice, vs));
-          o += PointSrc::staged(bytes);
-        }
-      }
-      if (src.layout) {  // the voxeliser reads the messages in place
-        va.src = 1;
-        va.pc2 = src.plan;
-        for (int j = 0; j < nb; ++j) {
-          const c3h::Pc2Frame fr =
-              c3h::pc2_frame(src.height[f0 + j], src.width[f0 + j], src.layout->point_step, src.row_step[f0 + j]);
-          va.pc2_width[j] = fr.width;
-          va.pc2_row_step[j] = fr.row_step;
-          va.pc2_magic[j] = fr.magic;
-          va.pc2_shift[j] = (uint8_t)fr.shift;
-        }
-      }
-      va.inv = 1.0f / leaf;
-      va.leaf = leaf;
-      va.z_limit = z_limit;
-      for (int a = 0; a < 3; ++a) {
-        va.C[a] = canvas[a];
-        va.off[a] = p->subdiv > 0 ? p->offset[a] : 0;
-      }
-      va.subdiv = p->subdiv;
-      va.inv_s = p->subdiv > 0 ? (float)(1.0 / p->subdiv) : 0.0f;
-      for (int a = 0; a < 3; ++a) va.tb[a] = tb[a];
-      va.acc = ctx->pb_acc.p;
-      va.accM = ctx->pb_accM.p;
-      va.s_acc = tvox;
-      va.fcnt = ctx->pb_fcnt.p;
-      va.vlist = ctx->pb_vlist.p;
-      va.wlist = c->pb_wlist.p;
-      va.part = c->pb_part.p;
-      // every slot of the set: the previous batch on it may have had more frames than this one
-      for (int j = 0; j < c3h::kMaxBatch; ++j)
-        va.grid[j] = j < c->pb_slots ? c->pb_grid.p + (size_t)j * cvox : nullptr;
-      if (va.prev_nf > c->pb_slots || va.nf > c->pb_slots)
-        return fail(ctx, C3H_ERR_STATE, who + ": internal: frame slots");
-      va.info = ctx->pb_info.p + f0;
-      va.lim = c->pb_lim.p;
-      const uint32_t* grids[c3h::kMaxBatch];
-      c3h_det* outs[c3h::kMaxBatch];
-      for (int j = 0; j < nb; ++j) {
-        grids[j] = c->pb_grid.p + (size_t)j * cvox;
-        outs[j] = d_out + (size_t)(f0 + j) * per_frame;
-      }
-      // the accumulate needs nothing of the batch's C3 launch, so it starts before the
-      // launch is captured (the capture's host work, ~10 us, then runs beside it: a one-batch
-      // call starts sooner).  The set's grids and gate limits were last read by the tick
-      // pushed two batches ago (tile role: one tick after the batch's own, gate role: two),
-      // so this batch's voxels overlap the previous batch's tick
-      if (ch >= 2) HIPCHK(hipStreamWaitEvent(vs, ctx->pb_tick_ev[(ch - 2) & 3], 0));
-      {
-        Timed t(ctx, 0, nb, vs);
-        HIPCHK(c3h::launch_vox_batch_accum(va, vs));
-      }
-      // until the chain below has run, the accumulators hold this batch's sums: an exit in
-      // between has the next call re-zero them
-      struct PbAccGuard {
-        c3h_ctx* c;
-        bool armed;
-        ~PbAccGuard() {
-          if (armed) c->pb_acc_vox = 0;
-        }
-      } pb_acc_guard{ctx, true};
-      // the batch's launches are captured next: the scatter sets its tile stamps and work
-      // lists (the occupancy stream's job), so its first tick carries no occupancy role and
-      // no canvas is streamed (128^3: 8.4 MB, 256^3: 67 MB per frame)
-      c3h_ctx::PipeBatch fresh{};
-      const int h2d0 = c->cap_h2d;
-      rc = pipe_prepare(ctx, grids, outs, nb, k, c->pb_lim.p, &fresh);
-      if (rc == 0) rc = fail(ctx, C3H_ERR_STATE, who + ": the canvas does not fit the pipeline");
-      if (rc < 0) break;
-      const c3h::C3Launch& cl = fresh.l;
-      va.stamp = (cl.gx == canvas[0] && cl.gy == canvas[1] && cl.gz == canvas[2] &&
-                  cl.ntiles <= ((int64_t)1 << 18)) ? 1 : 0;
-      va.axmap = cl.axmap;
-      va.ns0 = cl.nseg[0];
-      va.ns1 = cl.nseg[1];
-      va.ntiles = (int)cl.ntiles;
-      va.epoch = cl.epoch;
-      va.tf = cl.tf;
-      va.work = cl.work;
-      va.s_tf = cl.s_tf;
-      va.s_work = cl.s_work;
-      // the exact pass + off-cell fixup: the tick's direct mode (a row list, one tile per
-      // subdivision) on the canvas itself; otherwise flagged frames take the single-frame path
-      const bool exact = cl.rows && cl.axmap && cl.gx == canvas[0] && cl.gy == canvas[1] &&
-                         cl.gz == canvas[2] && c3h::point_fixup_fits(cl.lmax);
-      if (exact) {
-        va.flags = c->pb_flags.p;
-        va.bucket = c->pb_bucket.p;
-        va.moved = c->pb_moved.p;
-        va.xcnt = c->pb_xcnt.p;
-        c3h::PointFixup& fx = fresh.fx;
-        fx.nf = nb;
-        for (int j = 0; j < nb; ++j) fx.grid[j] = grids[j];
-        fx.moved = c->pb_moved.p;
-        fx.xcnt = c->pb_xcnt.p;
-        fx.info = ctx->pb_info.p + f0;
-        for (int a = 0; a < 3; ++a) {
-          fx.C[a] = canvas[a];
-          fx.thr[a] = cl.thr[a];
-        }
-        fx.axmap = cl.axmap;
-        fx.segs = cl.segs;
-        fx.ns0 = cl.nseg[0];
-        fx.ns1 = cl.nseg[1];
-        fx.seg_stride = cl.seg_stride;
-        fx.sbx = cl.sbx;
-        fx.sby = cl.sby;
-        fx.variant = cl.variant;
-        fx.lut = cl.lut;
-        fx.feat = cl.feat;
-        fx.exist = cl.exist;
-        fx.rows = cl.rows;
-        fx.tf = cl.tf;
-        fx.s_feat = cl.s_feat;
-        fx.s_h = cl.s_h;
-        fx.s_tf = cl.s_tf;
-        fx.epoch = cl.epoch;
-        for (int a = 0; a < 3; ++a) fx.lmax[a] = cl.lmax[a];
-        fresh.fix = true;
-      }
-      if (exact) std::fill(exact_ran.begin() + f0, exact_ran.begin() + f0 + nb, (char)1);
-      // tables / stamp resets the capture enqueued precede the stamps (first batches only)
-      if (va.stamp && vs != ctx->stream && c->cap_h2d != h2d0) {
-        HIPCHK(hipEventRecord(ctx->pb_vox_ev, ctx->stream));
-        HIPCHK(hipStreamWaitEvent(vs, ctx->pb_vox_ev, 0));
-      }
-      {
-        Timed t(ctx, 0, 0, vs);  // (the frames are counted with the accumulate)
-        HIPCHK(c3h::launch_vox_batch_post(va, vs));
-      }
-      pb_acc_guard.armed = false;  // the scatter returns every touched accumulator to zero
-      HIPCHK(hipEventRecord(ctx->pb_vox_ev, vs));
-      c->pb_prev_nf = nb;
-      c->pb_prev_total = va.total;
-      c->pb_prev_blk0.assign(va.blk0, va.blk0 + nb + 1);
-      fresh.stamped = va.stamp != 0;
-      // A stamped batch has no role in its own first tick (that tick runs the tile role of
-      // the batch before it, compress + gate and scoring of older ones), so the tick goes
-      // ahead of this batch's voxeliser and only the next tick waits for it (round 6: the
-      // batch's tile role then runs beside the next voxeliser instead of after it, one
-      // tick less per call after the last voxeliser).  An unstamped batch's first tick
-      // streams its canvases: it waits.
-      if (!fresh.stamped) HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->pb_vox_ev, 0));
-      if (fresh.nosearch)  // no search: the frames' lists are the fresh setRank state
-        HIPCHK(hipMemsetAsync(d_out + (size_t)f0 * per_frame, 0, (size_t)nb * per_frame * sizeof(c3h_det), ctx->stream));
-      rc = pipe_commit(ctx, fresh, k, rc);
-      if (rc > 0) {
-        int modes[6];  // as the single-frame path: the modes the search schedules
-        nm = fresh.nosearch ? mode_schedule(range[0], range[1], range[2], rotate, modes) : rc;
-      }
-      if (rc >= 0) HIPCHK(hipEventRecord(ctx->pb_tick_ev[ch & 3], ctx->stream));
-      if (fresh.stamped) HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->pb_vox_ev, 0));
-    }
-    while (rc >= 0 && !ctx->pipe.empty()) {
-      const int trc = pipe_tick(ctx, nullptr);
-      if (trc != C3H_OK) rc = trc;
-    }
-    if (rc < 0) {
-      ctx->pipe.clear();
-      return rc;
-    }
-    // the records come back through pinned memory: one asynchronous copy and one stream
-    // synchronisation (a pageable copy blocks, then the stream is synchronised again; ~20 us
-    // of a 64-frame call's ~0.75 ms)
-    if (ctx->h_recs_n < (size_t)nframes) {
-      if (ctx->h_recs) HIPCHK(hipHostFree(ctx->h_recs));
-      ctx->h_recs = nullptr;
-      ctx->h_recs_n = 0;
-      void* hp = nullptr;
-      HIPCHK(hipHostMalloc(&hp, (size_t)nframes * sizeof(c3h::VoxFrameRec)));
-      ctx->h_recs = static_cast<c3h::VoxFrameRec*>(hp);
-      ctx->h_recs_n = (size_t)nframes;
-    }
-    const c3h::VoxFrameRec* recs = ctx->h_recs;
-    HIPCHK(hipMemcpyAsync(ctx->h_recs, ctx->pb_info.p, (size_t)nframes * sizeof(c3h::VoxFrameRec),
-                          hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < nframes; ++i) {
-      const c3h::VoxFrameRec& r = recs[i];
-      c3h_frame_info& o = fi[i];
-      bool one = true;
-      for (int a = 0; a < 3; ++a) {
-        o.min_b[a] = r.min_b[a];
-        o.div_b[a] = r.max_b[a] - r.min_b[a] + 1;
-        o.subdiv_b[a] = p->subdiv > 0 ? r.sb[a] : 0;  // getSubdivNum without subdivisions: 0
-        one = one && r.sb[a] == 1;
-      }
-      o.n_valid = r.n_valid;
-      o.n_occ = r.n_occ;
-      o.n_moved = (int32_t)r.moved;
-      o.status = 0;
-      const bool hist1_mismatch = p->subdiv > 0 && canvas_multi && one;
-      const bool empty_sub = p->subdiv > 0 && (r.sb[0] == 0 || r.sb[1] == 0 || r.sb[2] == 0);
-      redo[i] = (r.err || (r.flagged && !exact_ran[i]) || r.n_valid == 0 || hist1_mismatch || empty_sub) ? 1 : 0;
-    }
-  }
-  for (int i = 0; i < nframes; ++i) {
-    if (!redo[i]) continue;
-    int rc = point_src_single(ctx, src, i, leaf, z_limit, p, range, exist_threshold, rotate,
-                              d_out + (size_t)i * per_frame, &fi[i]);
-    if (rc == C3H_ERR_HIP || rc == C3H_ERR_NOMEM) return rc;  // device trouble ends the call
-  }
-  if (!batched) {  // the modes the search schedules (search.cpp:384-417)
-    int modes[6];
-    nm = mode_schedule(range[0], range[1], range[2], rotate, modes);
-  }
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (info) memcpy(info, fi.data(), fi.size() * sizeof(c3h_frame_info));
-  return nm;
-}
-
-}  // namespace
-
-extern "C" {
-
-int c3h_run_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t nframes, int on_device,
-                         float leaf, float z_limit, const int32_t canvas[3], const c3h_extract_params* p,
-                         const int32_t range[3], int32_t exist_threshold, int32_t rotate, c3h_det* d_out,
-                         c3h_frame_info* info) {
-  if (!ctx || !pts || !n || nframes < 0 || !canvas || !p || !range || !d_out || !(leaf > 0)) return C3H_ERR_ARG;
-  if (!ctx->have_setup) return fail(ctx, C3H_ERR_STATE, "c3h_run_point_frames: no axes (call c3h_search_setup)");
-  for (int i = 0; i < nframes; ++i)
-    if (n[i] < 0 || (n[i] > 0 && !pts[i]) || n[i] >= ((int64_t)1 << 24))
-      return fail(ctx, C3H_ERR_ARG, "c3h_run_point_frames: frame point counts must be in [0, 16,777,215]");
-  PointSrc src;
-  src.who = "c3h_run_point_frames";
-  src.base = reinterpret_cast<const void* const*>(pts);
-  src.n = n;
-  src.nframes = nframes;
-  src.on_device = on_device;
-  return run_point_source(ctx, src, leaf, z_limit, canvas, p, range, exist_threshold, rotate, d_out, info);
-}
-
-int c3h_run_pointcloud2_frames(c3h_ctx* ctx, const void* const* data, const uint32_t* height, const uint32_t* width,
-                               const uint32_t* row_step, int32_t nframes, const c3h_pc2_layout* layout, int on_device,
-                               float leaf, float z_limit, const int32_t canvas[3], const c3h_extract_params* p,
-                               const int32_t range[3], int32_t exist_threshold, int32_t rotate, c3h_det* d_out,
-                               c3h_frame_info* info) {
-  if (!ctx || nframes < 0 || (nframes > 0 && (!data || !height || !width || !row_step)) || !layout || !canvas || !p ||
-      !range || !d_out || !(leaf > 0))
-    return C3H_ERR_ARG;
-  if (!ctx->have_setup) return fail(ctx, C3H_ERR_STATE, "c3h_run_pointcloud2_frames: no axes (call c3h_search_setup)");
-  std::vector<int64_t> n((size_t)nframes);
-  uint64_t base_or = 0;
-  uint32_t row_step_or = 0;
-  for (int i = 0; i < nframes; ++i) {
-    int rc = pc2_check(ctx, height[i], width[i], layout->point_step, row_step[i], layout->offsets);
-    if (rc != C3H_OK) return rc;
-    n[i] = (int64_t)height[i] * width[i];
-    if (n[i] > 0 && !data[i]) return fail(ctx, C3H_ERR_ARG, "pointcloud2: no data");
-    if (n[i] >= (int64_t)1 << 24)
-      return fail(ctx, C3H_ERR_RANGE, "c3h_run_pointcloud2_frames: at most 16,777,215 points per message");
-    if (n[i] == 0) continue;
-    // host messages are staged at 16-byte aligned addresses
-    if (on_device) base_or |= (uint64_t)(uintptr_t)data[i];
-    if (!c3h::pc2_flat(height[i], width[i], layout->point_step, row_step[i])) row_step_or |= row_step[i];
-  }
-  PointSrc src;
-  src.who = "c3h_run_pointcloud2_frames";
-  src.base = data;
-  src.n = n.data();
-  src.nframes = nframes;
-  src.on_device = on_device;
-  src.layout = layout;
-  src.height = height;
-  src.width = width;
-  src.row_step = row_step;
-  src.plan = c3h::pc2_plan(layout->point_step, layout->offsets, layout->is_bigendian, base_or, row_step_or);
-  return run_point_source(ctx, src, leaf, z_limit, canvas, p, range, exist_threshold, rotate, d_out, info);
-}
-
 int c3h_set_pipeline(c3h_ctx* ctx, int32_t enable) {
   if (!ctx) return C3H_ERR_ARG;
   QUIESCE(ctx);
@@ -3434,7 +2038,6 @@ int c3h_get_compressed(c3h_ctx* ctx, float* out, int on_device) {
       e = hipMemcpy2DAsync(out, (size_t)Wu * 4, src, (size_t)W * 4, (size_t)Wu * 4, (size_t)ctx->hist_num,
                            on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    release(tmp);
     if (e != hipSuccess) return fail(ctx, C3H_ERR_HIP, std::string("c3h_get_compressed: ") + hipGetErrorString(e));
     return C3H_OK;
   }

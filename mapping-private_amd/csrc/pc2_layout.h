@@ -2,7 +2,7 @@
 // (c3h_run_pointcloud2_frames): the load plan of a call's record layout, the point index ->
 // byte offset mapping of an organised message, and the extraction of the four FLOAT32 words
 // (x, y, z, rgb bits) of a record.  Plain C++: the kernels (voxelize.hip), the launch code
-// (capi.hip) and a host check (tests/pc2_layout_check.cpp) include it.  Memory is reached
+// (capi_batch.hip) and a host check (tests/pc2_layout_check.cpp) include it.  Memory is reached
 // through an accessor type (ld16 / ld4 / ld1 at a byte offset from the message's data[0]),
 // so the host check runs the very loads the kernels issue and sees every byte they touch.
 #pragma once

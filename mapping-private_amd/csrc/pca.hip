@@ -332,13 +332,6 @@ bool solver_load() {
   return g_solver.ok;
 }
 
-template <class T>
-void release(DevBuf<T>& b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.n = 0;
-}
-
 int grid_for(int64_t total) { return (int)std::min<int64_t>((total + 255) / 256, 8192); }
 
 }  // namespace
@@ -378,15 +371,7 @@ int pfail(c3h_pca* p, int code, const std::string& msg) {
 
 template <class T>
 int pensure(c3h_pca* p, DevBuf<T>& b, size_t n) {
-  if (n == 0) n = 1;
-  if (b.n >= n) return C3H_OK;
-  release(b);
-  if (hipMalloc(&b.p, n * sizeof(T)) != hipSuccess) {
-    b.p = nullptr;
-    return pfail(p, C3H_ERR_NOMEM, "hipMalloc failed");
-  }
-  b.n = n;
-  return C3H_OK;
+  return b.reserve(n) == hipSuccess ? C3H_OK : pfail(p, C3H_ERR_NOMEM, "hipMalloc failed");
 }
 
 #define PENSURE(buf, n)                               \
@@ -437,24 +422,8 @@ void c3h_pca_destroy(c3h_pca* p) {
   (void)hipSetDevice(p->device);
   if (p->stream) (void)hipStreamSynchronize(p->stream);
   if (p->blas) (void)g_solver.destroy(p->blas);
-  release(p->acc_plain);
-  release(p->acc_rot);
-  release(p->part);
-  release(p->C);
-  release(p->msum);
-  release(p->tmp);
-  release(p->G);
-  release(p->W);
-  release(p->E);
-  release(p->proj);
-  release(p->maps);
-  release(p->info);
-  release(p->stage);
-  release(p->out_axis);
-  release(p->out_var);
-  release(p->out_mean);
   if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
-  delete p;
+  delete p;  // frees its buffers
 }
 
 const char* c3h_pca_last_error(c3h_pca* p) { return p ? p->err.c_str() : "null PCA handle"; }

@@ -391,15 +391,8 @@ hipError_t launch_tick(const TickParts& p, hipStream_t s) {
     t.xcd &= C3H_TICK_XCD;
   }
   if (diag_env("C3H_TICK_PROF") && p.prof) {  // diagnostics builds only; synchronises
-    DevBuf<long long>& b = *p.prof;
-    if (b.n < (size_t)2 * total) {
-      if (b.p) (void)hipFree(b.p);
-      b.p = nullptr;
-      b.n = 0;
-      if (hipMalloc(&b.p, (size_t)2 * total * 8) != hipSuccess) return hipErrorOutOfMemory;
-      b.n = (size_t)2 * total;
-    }
-    t.prof = b.p;
+    if (p.prof->reserve((size_t)2 * total) != hipSuccess) return hipErrorOutOfMemory;
+    t.prof = p.prof->p;
   }
   c3h_tick_kernel<<<(unsigned)total, kBlock, lds, s>>>(t);
   if (t.prof) tick_prof_dump(t, t.prof, total, s);
