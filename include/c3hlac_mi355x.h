@@ -188,7 +188,10 @@ int c3h_get_feature_info(c3h_ctx* ctx, int32_t subdiv_out[3], int64_t* hist_num,
  * normals_radius_search = 0.02, grsd_colorCHLAC_tools.h:28): covariance of the points
  * within `radius` (float distances, the point included), smallest-eigenvalue eigenvector
  * (double), flipped towards `viewpoint` (NULL = origin), curvature; < 3 neighbours -> NaN.
- * c3h_get_normals: n x 4 floats (nx, ny, nz, curvature) in input order.
+ * A point that c3h_voxelize dropped (non-finite, z >= z_limit: limitPoint) is no point's
+ * neighbour, in the normals and in the RSD, and its own normal is NaN.
+ * c3h_get_normals: n x 4 floats (nx, ny, nz, curvature) in input order, n = the points
+ * given to c3h_voxelize, dropped ones included.
  * c3h_extract_grsd: extractGRSDSignature21 (:131-296): per occupied voxel PCL's
  * PrincipalRadiiRSD (computeRSD: nr_subdiv 5, plane radius 0.2) over the points within
  * max(rsd_radius, leaf sqrt(3)/2) of its centroid, get_type (:99-118), and the 6 x 6 type

@@ -385,10 +385,12 @@ hipError_t launch_offcell_delta(const int32_t* rec, int nrec, const C3Launch& l,
 hipError_t launch_c3_finalize(const unsigned long long* acc64, int64_t hist_num, int variant,
                               float* feat, int32_t* exist, int nframes, hipStream_t s);
 // radius-search grid over a point cloud (rsd.hip): cells of `cell` metres from origin,
-// the points sorted by cell, per cell its [cstart, cend) range in `sorted`
+// the points sorted by cell, per cell its [cstart, cend) range in `sorted`.  Points the
+// voxeliser dropped (non-finite, z >= z_limit: limitPoint) are in no cell
 struct NbrGrid {
   const float4* pts;
   int64_t n;
+  float z_limit;
   float origin[3];
   float cell, inv_cell;
   int dim[3];

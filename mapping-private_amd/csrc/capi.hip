@@ -1475,6 +1475,7 @@ static int nbr_grid(c3h_ctx* ctx, float cell) {
   c3h::NbrGrid g{};
   g.pts = a.pts;
   g.n = a.n;
+  g.z_limit = a.z_limit;
   g.cell = cell;
   g.inv_cell = 1.0f / cell;
   for (int ax = 0; ax < 3; ++ax) {

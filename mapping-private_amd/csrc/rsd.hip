@@ -9,7 +9,8 @@
 //   normals_kernel: one point per thread; double sums of the neighbours within the
 //     radius (the point included, squared distances in float as FLANN compares them);
 //     covariance -> smallest-eigenvalue eigenvector (Jacobi, double), flipped towards
-//     the viewpoint, curvature = lambda_min / trace; < 3 neighbours -> NaN (PCL).
+//     the viewpoint, curvature = lambda_min / trace; < 3 neighbours -> NaN (PCL).  A
+//     point the voxeliser dropped is nobody's neighbour and gets NaN.
 //   rsd_kernel: one downsampled centroid per thread; PCL's computeRSD over the cloud
 //     points within max(rsd_radius, leaf sqrt(3) / 2) of it: the nearest one is the
 //     reference ("begin"), the others' normal angles are binned by their distance to it.
@@ -26,8 +27,9 @@ namespace {
 
 constexpr uint32_t kNoCell = 0xffffffffu;
 
-__device__ __forceinline__ bool pt_finite(const float4& p) {
-  return isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
+// the points c3h_voxelize kept (voxelize.hip point_valid: finite, z < z_limit)
+__device__ __forceinline__ bool pt_kept(const NbrGrid& g, const float4& p) {
+  return isfinite(p.x) && isfinite(p.y) && isfinite(p.z) && p.z < g.z_limit;
 }
 
 __device__ __forceinline__ bool cell_of(const NbrGrid& g, const float4& p, int c[3]) {
@@ -45,7 +47,7 @@ __global__ void nbr_keys_kernel(NbrGrid g, uint32_t* __restrict__ keys, uint32_t
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < g.n; i += (int64_t)gridDim.x * blockDim.x) {
     const float4 p = g.pts[i];
     int c[3];
-    keys[i] = pt_finite(p) && cell_of(g, p, c) ? (uint32_t)(c[0] + g.dim[0] * (c[1] + g.dim[1] * c[2])) : kNoCell;
+    keys[i] = pt_kept(g, p) && cell_of(g, p, c) ? (uint32_t)(c[0] + g.dim[0] * (c[1] + g.dim[1] * c[2])) : kNoCell;
     idx[i] = (uint32_t)i;
   }
 }
@@ -145,7 +147,7 @@ __global__ void normals_kernel(NbrGrid g, float r2, int reach, float vx, float v
     const float4 q = g.pts[i];
     const float nan = __int_as_float(0x7fc00000);
     float4 res = make_float4(nan, nan, nan, nan);
-    if (pt_finite(q)) {
+    if (pt_kept(g, q)) {
       double s[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // n, x, y, z, xx, xy, xz, yy, yz, zz
       for_neighbours(g, q, r2, reach, [&](uint32_t, const float4& p, float) {
         const double x = p.x, y = p.y, z = p.z;

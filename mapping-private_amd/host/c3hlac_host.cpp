@@ -144,6 +144,7 @@ void getVoxelGrid(VoxelGrid& grid, const std::vector<PointXYZRGB>& input,
                   std::vector<PointXYZRGB>& output, float voxel_size, float z_limit) {
   static_assert(sizeof(PointXYZRGB) == 16, "xyzrgb record must be 4 floats");
   grid.leaf_ = voxel_size;
+  grid.n_input_ = input.size();
   c3h_grid_info info;
   grid.ctx_.check(c3h_voxelize(grid.ctx_.get(), reinterpret_cast<const float*>(input.data()),
                                (int64_t)input.size(), 0, voxel_size, z_limit, &info),
@@ -355,9 +356,8 @@ void computeNormal(VoxelGrid& grid, double radius) {
 
 std::vector<float> getNormals(const VoxelGrid& grid) {
   const Context& ctx = grid.context();
-  c3h_grid_info gi;
-  grid_info(ctx, &gi);
-  std::vector<float> out((size_t)gi.n_valid * 4);
+  // c3h_get_normals writes a row for every input point, not only for the n_valid kept ones
+  std::vector<float> out(grid.inputSize() * 4);
   ctx.check(c3h_get_normals(ctx.get(), out.data(), 0), "c3h_get_normals");
   return out;
 }

@@ -88,12 +88,15 @@ class VoxelGrid {
   std::vector<uint32_t> getPackedGrid() const;
   const Context& context() const { return ctx_; }
   float leaf() const { return leaf_; }
+  // points given to the last getVoxelGrid, dropped ones included (the rows of getNormals)
+  size_t inputSize() const { return n_input_; }
 
  private:
   friend void getVoxelGrid(VoxelGrid&, const std::vector<PointXYZRGB>&, std::vector<PointXYZRGB>&,
                            float, float);
   Context ctx_;
   float leaf_ = 0.0f;
+  size_t n_input_ = 0;
 };
 
 // getVoxelGrid (c3_hlac_tools.hpp:124-130), with detect_object.cpp's limitPoint
@@ -288,7 +291,8 @@ void extractColorCHLACSignature117(VoxelGrid& grid, std::vector<float>& feature,
 const double rsd_radius_search = 0.01;
 const double normals_radius_search = 0.02;
 void computeNormal(VoxelGrid& grid, double radius = normals_radius_search);
-std::vector<float> getNormals(const VoxelGrid& grid);  // n x 4: nx, ny, nz, curvature
+// one row per input point (nx, ny, nz, curvature), NaN for the points getVoxelGrid dropped
+std::vector<float> getNormals(const VoxelGrid& grid);
 Vector3i extractGRSDSignature21(VoxelGrid& grid, std::vector<std::vector<float> >& feature, float voxel_size,
                                 int subdivision_size = 0, int offset_x = 0, int offset_y = 0, int offset_z = 0,
                                 bool is_normalize = false);

@@ -29,18 +29,23 @@ def _finite(p):
     return np.isfinite(p[:, :3]).all(1)
 
 
-def normals(pts, radius, vp=(0.0, 0.0, 0.0)):
-    """(n, 4) float32 x y z rgb -> (n, 4) float64 nx ny nz curvature (NaN where undefined)."""
+def normals(pts, radius, vp=(0.0, 0.0, 0.0), rows=None):
+    """(n, 4) float32 x y z rgb -> (n, 4) float64 nx ny nz curvature (NaN where undefined).
+    rows: compute only these query rows (neighbours still from all points) -> (len(rows), 4)."""
     xyz = pts[:, :3].astype(np.float32)
     ok = _finite(pts)
     out = np.full((len(pts), 4), np.nan)
-    idx_ok = np.flatnonzero(ok)
-    P = xyz[idx_ok]
+    P = xyz[ok]
     r2 = np.float32(radius) * np.float32(radius)
-    for a, i in enumerate(idx_ok):
-        d = P - xyz[i]
+    query = np.flatnonzero(ok) if rows is None else [int(i) for i in rows if ok[i]]
+    px = np.ascontiguousarray(P[:, 0])
+    for i in query:
+        # rows of a large cloud: only the slab |dx| <= 1.001 radius can hold a neighbour
+        # (dx^2 <= d2 < r2); the candidates keep their order, so the sums are the same
+        Q = P if rows is None else P[np.abs(px - xyz[i, 0]) <= np.float32(radius * 1.001)]
+        d = Q - xyz[i]
         d2 = ((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]).astype(np.float32)
-        nb = P[d2 < r2].astype(np.float64)
+        nb = Q[d2 < r2].astype(np.float64)
         if len(nb) < 3:
             continue
         m = nb.mean(0)
@@ -52,7 +57,7 @@ def normals(pts, radius, vp=(0.0, 0.0, 0.0)):
         s = w.sum()
         out[i, :3] = n
         out[i, 3] = w[0] / s if s != 0 else 0.0
-    return out
+    return out if rows is None else out[np.asarray(rows, np.int64)]
 
 
 def compute_rsd(surface, nrm, centre, max_dist, nr_subdiv=5, plane_radius=0.2):
@@ -117,13 +122,21 @@ REL13 = [(i, j, -1) for i in (-1, 0, 1) for j in (-1, 0, 1)] + [(i, -1, 0) for i
 REL26 = REL13 + [(-a, -b, -c) for a, b, c in REL13]
 
 
-def grsd(cloud_pts, nrm, g, layout, cent, leaf, subdiv=0, offset=(0, 0, 0), rsd_radius=0.01):
+def grsd(cloud_pts, nrm, g, layout, cent, leaf, subdiv=0, offset=(0, 0, 0), rsd_radius=0.01,
+         types=None):
     """extractGRSDSignature21 on a voxelised cloud: g = oracle grid (div_b, min_b),
     layout = leaf layout (-1 empty), cent = downsampled centroids (n_occ, 4) in layout
-    order.  Returns (features (hist_num, 20) raw counts, subdiv_b, radii (n_occ, 2), types)."""
-    max_dist = max(rsd_radius, leaf / 2 * np.sqrt(3))
-    radii = np.array([compute_rsd(cloud_pts, nrm, c[:3], max_dist) for c in cent])
-    types = np.array([get_type(a, b) for a, b in radii], np.int32)
+    order.  Returns (features (hist_num, 20) raw counts, subdiv_b, radii (n_occ, 2), types).
+    types given (one per centroid): no RSD is computed, the transitions are counted from
+    those types (returned as types; radii is None)."""
+    if types is None:
+        max_dist = max(rsd_radius, leaf / 2 * np.sqrt(3))
+        radii = np.array([compute_rsd(cloud_pts, nrm, c[:3], max_dist) for c in cent]).reshape(-1, 2)
+        types = np.array([get_type(a, b) for a, b in radii], np.int32)
+    else:
+        radii = None
+        types = np.asarray(types, np.int32)
+        assert types.shape == (len(cent),)
     div = np.array(g.div_b[:3])
     mnb = np.array(g.min_b[:3])
     if subdiv > 0:

@@ -8,7 +8,7 @@
 //   facade_demo thr <cloud.pcd> <leaf>                  (GPU: calc_scene_auto_threshold flow)
 //   facade_demo rot <dim> <mode>                        (host only: rotateFeature90 of 0..dim-1)
 //   facade_demo train <rows.bin> <out_dir> <D> <n_model> (GPU: pca_scene.cpp + pca_models.cpp)
-//   facade_demo vosch <cloud.pcd> <leaf>                (GPU: example_GRSD_CCHLAC / setVOSCH flow)
+//   facade_demo vosch <cloud.pcd> <leaf> [z_limit]      (GPU: example_GRSD_CCHLAC / setVOSCH flow)
 //   facade_demo readdata <F.bin> <N.bin> <dir> <dim>     (GPU: SearchObj::readData + search)
 //   facade_demo estim <param_dir> <cloud.pcd> <out_prefix> (GPU: extract_c3_hlac_scene.cpp's flow
 //                                                        through C3HLAC{981,117}Estimation)
@@ -191,18 +191,22 @@ static int train(const char* rows_path, const std::string& out, int D, int n_mod
 
 // example_GRSD_CCHLAC.cpp's flow: loadPCDFile -> computeNormal -> getVoxelGrid ->
 // extractGRSDSignature21 + extractVOSCH (whole cloud)
-static int vosch(const char* path, float leaf) {
+static int vosch(const char* path, float leaf, float z_limit) {
   std::vector<PointXYZRGB> cloud, down;
   loadPCDFile(path, cloud);
   VoxelGrid grid;
-  getVoxelGrid(grid, cloud, down, leaf);
+  getVoxelGrid(grid, cloud, down, leaf, z_limit);
   computeNormal(grid, normals_radius_search);
+  const std::vector<float> nrm = getNormals(grid);  // a row per input point, NaN where dropped
+  size_t nan_rows = 0;
+  for (size_t i = 0; i + 3 < nrm.size(); i += 4) nan_rows += std::isnan(nrm[i]) ? 1 : 0;
   std::vector<std::vector<float> > grsd, vosch_f;
   extractGRSDSignature21(grid, grsd, leaf);
   extractVOSCH(grid, vosch_f, 127, 127, 127, leaf);
   printf("{\"grsd\": [");
   for (size_t i = 0; i < grsd[0].size(); ++i) printf(i ? ", %.9g" : "%.9g", grsd[0][i]);
-  printf("], \"vosch_dim\": %d, \"vosch_head\": [", (int)vosch_f[0].size());
+  printf("], \"normal_rows\": %zu, \"normal_nan_rows\": %zu, \"vosch_dim\": %d, \"vosch_head\": [", nrm.size() / 4,
+         nan_rows, (int)vosch_f[0].size());
   for (int i = 0; i < 22; ++i) printf(i ? ", %.9g" : "%.9g", vosch_f[0][i]);
   printf("]}\n");
   return 0;
@@ -371,7 +375,8 @@ int main(int argc, char** argv) {
     if (argc == 4 && !strcmp(argv[1], "thr")) return thr(argv[2], (float)atof(argv[3]));
     if (argc == 4 && !strcmp(argv[1], "rot")) return rot(atoi(argv[2]), atoi(argv[3]));
     if (argc == 6 && !strcmp(argv[1], "train")) return train(argv[2], argv[3], atoi(argv[4]), atoi(argv[5]));
-    if (argc == 4 && !strcmp(argv[1], "vosch")) return vosch(argv[2], (float)atof(argv[3]));
+    if ((argc == 4 || argc == 5) && !strcmp(argv[1], "vosch"))
+      return vosch(argv[2], (float)atof(argv[3]), argc == 5 ? (float)atof(argv[4]) : INFINITY);
     if (argc == 5 && !strcmp(argv[1], "estim")) return estim(argv[2], argv[3], argv[4]);
     if (argc == 6 && !strcmp(argv[1], "readdata")) return readdata(argv[2], argv[3], argv[4], atoi(argv[5]));
   } catch (const Error& e) {

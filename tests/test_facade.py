@@ -196,6 +196,28 @@ def test_facade_vosch_flow(ctx, demo):
 
 
 @pytest.mark.gpu
+def test_facade_normals_with_dropped_points(ctx, demo):
+    """getNormals returns a row per input point, NaN for the points getVoxelGrid's z_limit
+    dropped (it used to size its buffer by the kept points while the library wrote a row
+    for every input point); GRSD behind a z_limit equals the binding's."""
+    path = FIX / "pcd" / "noisy_torus_blue.pcd"
+    pts = c3hlac.read_pcd(path)
+    zl = float(np.median(pts[:, 2]))
+    out = subprocess.run([str(demo), "vosch", str(path), "0.01", repr(zl)], check=True, capture_output=True,
+                         text=True).stdout
+    j = json.loads(out)
+    gi = ctx.voxelize(pts, 0.01, zl)
+    assert 0 < gi.n_valid < len(pts)
+    ctx.compute_normals(0.02)
+    nrm = ctx.normals(len(pts))
+    assert np.isnan(nrm[pts[:, 2] >= np.float32(zl)]).all()
+    assert j["normal_rows"] == len(pts)
+    assert j["normal_nan_rows"] == int(np.isnan(nrm[:, 0]).sum()) >= len(pts) - gi.n_valid
+    ctx.extract_grsd(0)
+    assert np.array_equal(np.float32(j["grsd"]), ctx.features()[0])
+
+
+@pytest.mark.gpu
 def test_facade_read_data_integral_tables(ctx, demo, tmp_path):
     """SearchObj::readData (search.cpp:169-210): binary integral tables of compressed
     features and exist counts -> search; the same lists as the binding's search on the

@@ -11,7 +11,8 @@ example_GRSD_CCHLAC.cpp:
   way towards the viewpoint, curvature within 1e-5;
 - RSD radii from the device normals within 1e-5 relative of the oracle's computeRSD, types
   equal except where a radius sits within 1e-4 of a get_type threshold;
-- GRSD transition counts bit-exact given equal types (whole cloud and subdivisions);
+- GRSD transition counts bit-exact from the device's own types (whole cloud, subdivisions
+  with offset and normalize, the wide leaf), never under a condition;
 - VOSCH = [GRSD-20 | C3-HLAC-117] rows, exist by the setVOSCH rule, searchable at F=137."""
 import numpy as np
 import pytest
@@ -21,6 +22,7 @@ import grsd_oracle as go
 import pyoracle as po
 from c3hlac import synth
 from conftest import GOLDEN, THR
+from feature_frames_data import grsd_exist
 
 pytestmark = pytest.mark.gpu
 PCD = GOLDEN / "ref_fixtures" / "pcd"
@@ -59,8 +61,11 @@ def test_normals_rsd_grsd_whole_cloud(ctx, name):
     near |= np.abs(radii_ref[:, 1] - radii_ref[:, 0] - 0.050) < 1e-4
     assert np.array_equal(types[~near], types_ref[~near]), name
     assert (types != types_ref).sum() <= near.sum()
-    if np.array_equal(types, types_ref):  # equal types: the transition counts are exact
-        assert np.array_equal(ctx.features()[0], feat_ref[0].astype(np.float32)), name
+    # the transition counts are exact given the device's own types, whatever they are
+    feat_dev = go.grsd(pts, dn, g, layout, cloud, 0.01, types=types)[0]
+    assert np.array_equal(ctx.features()[0], feat_dev[0].astype(np.float32)), name
+    if np.array_equal(types, types_ref):
+        assert np.array_equal(feat_dev, feat_ref)
     print(name, "voxels", len(types), "type mismatches", int((types != types_ref).sum()),
           "types", np.bincount(types, minlength=5).tolist())
     # every voxel sees 26 neighbours; bins (i, j > i) and bin 20 (5, 5) hold the rest
@@ -77,9 +82,11 @@ def test_grsd_subdivisions_and_normalize(ctx):
     assert list(sb) == list(sb_ref) and H == len(feat_ref)
     _, types = ctx.rsd()
     print("subdiv: type mismatches", int((types != types_ref).sum()), "of", len(types))
-    if np.array_equal(types, types_ref):
-        np.testing.assert_array_equal(ctx.features(), (feat_ref * np.float32(20.0 / 26)).astype(np.float32))
+    feat_dev = go.grsd(pts, dn, g, layout, cloud, 0.005, subdiv=4, offset=(1, 0, 2), types=types)[0]
+    assert feat_dev.sum() > 0 and (feat_dev.sum(1) > 0).sum() > 1  # more than one subdivision filled
+    np.testing.assert_array_equal(ctx.features(), (feat_dev * np.float32(20.0 / 26)).astype(np.float32))
     assert ctx.exist().shape == (H,)
+    np.testing.assert_array_equal(ctx.exist(), grsd_exist(ctx.features()))
 
 
 def test_vosch_rows_and_search(ctx):
@@ -88,6 +95,10 @@ def test_vosch_rows_and_search(ctx):
     ctx.compute_normals(0.04)
     ctx.extract_grsd(6)
     grsd = ctx.features().copy()
+    _, types = ctx.rsd()
+    g, layout, cloud = po.voxelize(pts, 0.02)
+    np.testing.assert_array_equal(
+        grsd, go.grsd(pts, None, g, layout, cloud, 0.02, subdiv=6, types=types)[0].astype(np.float32))
     sb, H = ctx.extract(117, THR, 6)
     c3, ex = ctx.features().copy(), ctx.exist().copy()
     sbv, Hv = ctx.extract_vosch(THR, 6)
@@ -134,5 +145,5 @@ def test_grsd_leaf_wider_than_four_normal_radii(ctx):
     tie = near(rmin, 0.100) | near(rmax, 0.175) | near(rmin, 0.015) | (np.abs(rmax - rmin - 0.050) <= 1e-6)
     assert tie.all(), diff[~tie]
     assert len(diff) <= max(1, len(types) // 100)
-    if len(diff) == 0:
-        assert np.array_equal(ctx.features()[0], feat_ref[0].astype(np.float32))
+    feat_dev = go.grsd(pts, dn, g, layout, cloud, 0.1, types=types)[0]
+    assert np.array_equal(ctx.features()[0], feat_dev[0].astype(np.float32))
