@@ -255,9 +255,15 @@ int c3h_search_setup(c3h_ctx* ctx, const float* axis_p, const float* var, int32_
  * subdivisions (e.g. BASELINE config 5; D <= 128) rounds the normalised features and the
  * whitened axis to f16, and the matrix-core projection (c3h_set_score_engine) rounds each
  * position's box row -- scaled by a power of two, |Q f|/|f| is scale-free -- and the model
- * basis to f16; both accumulate in f32 on v_mfma_f32_32x32x16_f16.  Scores then agree with
- * the float64 oracle within 2e-3 relative (fp16 = 0, the default: fp32, 1e-5).  The VALU
- * kernels and the pipelined c3h_run_frames path always run in fp32.
+ * basis to f16 (f16 subnormals are kept); both accumulate in f32 on
+ * v_mfma_f32_32x32x16_f16.  Scores then agree with the float64 oracle within
+ * |score - oracle| <= max(2e-3 * oracle, 5e-4): 2e-3 relative for scores of 0.25 and above,
+ * 5e-4 absolute below (f16 operand rounding is an absolute error of about 1e-4 in the score,
+ * whatever its size; fp16 = 0, the default: fp32, 1e-5 relative).  Features (after the
+ * feature_max normalisation) and whitened axis entries must not exceed 65504, the largest
+ * f16, where the f16 compress runs; the projection has no such limit.  Against the same
+ * roundings taken in float64 (oracle/np_ref.py scores_f16) the scores agree within 5e-6
+ * relative.  The VALU kernels and the pipelined c3h_run_frames path always run in fp32.
  * The setting also applies to c3h_extract: at fp16 a large dense C3-HLAC-981 extract (the
  * matrix-core C3 kernel) writes its feature rows as f16 only.  Setting fp16 = 0 afterwards
  * searches those rounded rows (widened to f32) until the next extract, so the 1e-5 bound of

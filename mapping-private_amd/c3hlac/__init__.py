@@ -247,7 +247,10 @@ class Context:
         self._chk(self.lib.c3h_set_remove_overlap(self.h, int(bool(enable))), "set_remove_overlap")
 
     def set_search_precision(self, fp16):
-        """c3h_set_search_precision: fp16 matrix-core compress for large grids."""
+        """c3h_set_search_precision: f16 operands on the matrix cores for the compress of grids
+        of >= 65,536 subdivisions (D <= 128) and for the matrix-core projection (any size;
+        set_score_engine); set before extract, a large dense C3-HLAC-981 extract writes its
+        feature rows as f16."""
         self._chk(self.lib.c3h_set_search_precision(self.h, int(bool(fp16))), "set_search_precision")
 
     def set_features(self, feat, subdiv, exist=None, rule=0):

@@ -239,6 +239,133 @@ def scores(sb, feat, exist, axis_p, axis_q, r, thr, rotate=True, fmax=None):
     return out
 
 
+# ---------------------------------------------------------------- search (fp16 precision)
+# c3h_set_search_precision(ctx, 1) restated with the kernels' documented roundings and
+# nothing else of them: float16 only rounds operands, every sum is float64 except the box
+# sums (float32 in the kernels' own order, so bit-exact by construction).  What is left
+# between this and the GPU is the f32 accumulation order of the matrix instruction, which
+# F16_REF_RTOL covers -- two orders of magnitude below the distance between f16 operand
+# rounding and the float64 oracle, and below what an indexing slip moves.
+#
+# The fp16 precision accepts features (after the fmax normalisation) and whitened axis
+# entries up to 65504, the largest finite float16: compress_f16 raises beyond it.  The
+# projection has no such limit (each box row is scaled by a power of two first).
+
+# Relative tolerance between scores_f16 and the f16 kernels' scores: 8 x the largest
+# deviation of two f32 accumulation orders from scores_f16 over the shape table of
+# tests/search_fp16_cases.py (measured 4.48e-7 -> 3.6e-6, rounded up to 5e-6 so that a
+# last-bit change of the measurement does not trip it; tests/test_search_fp16_ref_cpu.py
+# asserts 8 x <= constant <= 16 x the fresh measurement).
+F16_REF_RTOL = 5e-6
+
+# The fp16 precision's published contract against the float64 oracle (include/
+# c3hlac_mi355x.h): |score - oracle| <= max(F16_CONTRACT_RTOL * oracle, F16_CONTRACT_ATOL).
+F16_CONTRACT_RTOL = 2e-3
+F16_CONTRACT_ATOL = 5e-4
+F16_MIN_NORMAL = 2.0 ** -14
+
+
+def _round_f16(x, flush_subnormals=False):
+    """x rounded to the nearest float16 (ties to even), returned as float64."""
+    with np.errstate(over="ignore"):
+        h = np.asarray(x).astype(np.float16).astype(np.float64)
+    if flush_subnormals:
+        h = np.where(np.abs(h) < F16_MIN_NORMAL, 0.0, h)
+    return h
+
+
+def compress_f16(feat, axis_p_whitened, fmax=None):
+    """The fp16 compress (compress_f16_kernel): -> (G_ref (H, D) float64, bound (H, D)).
+
+    The fmax normalisation in float32 as scores() does it, features and whitened axis
+    rounded to float16, products and sums in float64.  bound[h, d] = K 2^-24 sum_k |a_k b_k|
+    with K = F rounded up to 16: the first-order bound on an f32 accumulation of the K exact
+    products in any order, so |G_gpu - G_ref| <= bound whatever the kernel's order is."""
+    f = np.asarray(feat).astype(np.float32).copy()
+    if fmax is not None:
+        fm = np.asarray(fmax, np.float32)
+        for t in range(min(len(fm), f.shape[1])):
+            col = f[:, t]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                f[:, t] = np.where(fm[t] == 0, 0, np.where(col == fm[t], 1, col / fm[t]))
+    a = _round_f16(f)
+    b = _round_f16(np.asarray(axis_p_whitened).astype(np.float32))
+    if not (np.isfinite(a).all() and np.isfinite(b).all()):
+        raise ValueError("fp16 search precision: an operand exceeds 65504 (the largest float16)")
+    K = (f.shape[1] + 15) // 16 * 16
+    return a @ b.T, K * 2.0 ** -24 * (np.abs(a) @ np.abs(b).T)
+
+
+def flat_bases(D, M, r, seed):
+    """axis_q (M, r, D) float32: per model the first r columns of a random orthonormal
+    D x D matrix, no row scaling -- every basis column weighs the same in the score, so a
+    column credited to the wrong model moves it (synth.random_bases' rows decay as
+    0.85^(i/2), which hides the last columns of a model below 1e-4 of the score)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    qs = []
+    for _ in range(M):
+        q, rr = np.linalg.qr(rng.standard_normal((D, D)))
+        qs.append((q * np.sign(np.diag(rr))[None, :])[:, :r].T)
+    return np.stack(qs).astype(np.float32)
+
+
+def box_rows_f32(Gv, xr, yr, zr):
+    """Gv[z,y,x,d] float32 -> box rows (P, D) float32, one cell added at a time in
+    (dz, dy, dx) order from zero, as boxsum_body does (bit-exact by construction)."""
+    Z, Y, X = Gv.shape[:3]
+    ze, ye, xe = Z - zr + 1, Y - yr + 1, X - xr + 1
+    s = np.zeros((ze, ye, xe) + Gv.shape[3:], np.float32)
+    for dz in range(zr):
+        for dy in range(yr):
+            for dx in range(xr):
+                s = s + Gv[dz:dz + ze, dy:dy + ye, dx:dx + xe]
+    return s.reshape(ze * ye * xe, -1)
+
+
+def f16_operands(sb, G, exist, axis_q, ranges, thr, rotate=True, flush_subnormals=False, scale=True):
+    """The f16 projection's operands: -> (modes, q16).  modes = [(mode, xe, ye, gate (P,)
+    bool, h (P, D) float64)] with h the box rows scaled by 2^-ex (frexp of the row's largest
+    magnitude) and rounded to float16; q16 (M, r, D) float64 the basis rounded to float16.
+    scale=False omits the power of two (a mutant for the tests; inf where a row overflows)."""
+    xn, yn, zn = sb
+    G = np.asarray(G, np.float32) * (np.asarray(exist).reshape(-1, 1) != 0)
+    Gv = G.reshape(zn, yn, xn, -1)
+    Ev = np.asarray(exist).astype(np.int64).reshape(zn, yn, xn)
+    q16 = _round_f16(np.asarray(axis_q, np.float32), flush_subnormals)
+    modes = []
+    for mode in mode_schedule(ranges, rotate):
+        xr, yr, zr = _ranges(mode, ranges)
+        if xn - xr + 1 <= 0 or yn - yr + 1 <= 0 or zn - zr + 1 <= 0:
+            continue
+        gate = box_sums(Ev, xr, yr, zr).reshape(-1) > thr
+        fb = box_rows_f32(Gv, xr, yr, zr)
+        if scale:
+            _, ex = np.frexp(np.abs(fb).max(1))
+            fb = np.ldexp(fb, -ex[:, None])  # exact: a power of two, no underflow in float32
+        modes.append((mode, xn - xr + 1, yn - yr + 1, gate, _round_f16(fb, flush_subnormals)))
+    return modes, q16
+
+
+def scores_f16(sb, G, exist, axis_q, ranges, thr, rotate=True, flush_subnormals=False):
+    """Per-position scores of the fp16 search precision in scores()' layout, float64.
+
+    G (H, D) float32 as Context.compressed() returns it (rows whose exist is 0 count as
+    zero).  Per mode: float32 box rows, gate e > thr, each row scaled by the power of two
+    that puts its largest magnitude in [0.5, 1) and rounded to float16, ff = sum h^2 over
+    the rounded values, basis rounded to float16, q = Q16 h and score = |q| / sqrt(ff) in
+    float64; -1 where gated out.  flush_subnormals zeroes operands below 2^-14."""
+    modes, q16 = f16_operands(sb, G, exist, axis_q, ranges, thr, rotate, flush_subnormals)
+    out = []
+    for mode, xe, ye, gate, h in modes:
+        M, r, D = q16.shape
+        q = (h @ q16.reshape(M * r, D).T).reshape(-1, M, r)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            sc = np.sqrt((q * q).sum(2)).T / np.sqrt((h * h).sum(1))[None, :]
+        sc[:, ~gate] = -1.0
+        out.append((mode, xe, ye, sc))
+    return out
+
+
 def replay(mode_scores, r, rank, lists=None):
     """Reference rank update (search.cpp:464-474, 327-356) over per-mode score arrays."""
     M = mode_scores[0][3].shape[0] if mode_scores else 1

@@ -5,7 +5,9 @@ The engines below switch on at >= 65,536 subdivisions (c3h_internal.h kBoxsumRow
 search.hip kCompressMfmaRows) -- BASELINE config 5's regime:
 - compress_f32c_kernel (f32 matrix cores; the same k-ordered fma
   chain as the VALU compress_kernel, so G must be bit-identical to it),
-- compress_f16_kernel + score_mfma_f16_kernel (fp16 search precision, 2e-3),
+- compress_f16_kernel + score_mfma_f16s_kernel (fp16 search precision, 2e-3; r = 20 and
+  r = 70 are both >= 16, so launch_score_mfma_f16_kq dispatches the basis-in-LDS kernel;
+  score_mfma_f16_kernel, r < 16, is run by test_gpu_search_fp16.py),
 - boxsum_kernel, score_mfma_kernel (f32 matrix cores; bit-identical to the VALU engine),
 - scores_argmax_kernel + argmax_finalize_kernel (the parallel rank-1 argmax).
 Earlier tests ran them only on grids periodic with the subdivision side, where every
