@@ -459,6 +459,63 @@ int c3h_stream_feature_frames(c3h_ctx* ctx, const float* const* d_feat, const in
                               const int32_t canvas_b[3], int32_t dim, int32_t exist_rule,
                               const int32_t range[3], int32_t exist_threshold, int32_t rotate,
                               c3h_det* d_out);
+/* Point clouds in, VOSCH / GRSD rows out, for a batch of frames: the per-frame work of
+ * color_voxel_recognition_2's detect_object_vosch_multi.cpp ahead of its search -- limitPoint +
+ * getVoxelGrid, computeNormal (grsd_colorCHLAC_tools.hpp:63-87), extractVOSCH (:832-843) or
+ * extractGRSDSignature21 (:131-296) -- i.e. c3h_voxelize + c3h_compute_normals +
+ * c3h_extract_vosch (dim 137) / c3h_extract_grsd (dim 20) for nframes clouds, frame i = pts[i]
+ * (n[i] x 4 floats as c3h_voxelize takes them; device pointers with on_device = 1, which must
+ * stay valid until the call's work is done, else host memory).
+ * c3h_extract_vosch_frames: frame i's rows start at d_rows + i * row_cap * dim (device), row
+ * h = x + y * xn + z * xn * yn in the frame's own counts, and are byte for byte the rows the
+ * three single-frame calls leave in a context.  info[i] (host, may be NULL) carries div_b, min_b,
+ * n_valid, n_occ and subdiv_b as they report them, n_moved = the voxels whose centroid lies in
+ * another cell (0 where the frame has no row), and the status: 0, C3H_ERR_RANGE for a frame with
+ * more than row_cap rows, else the error the single-frame route fails with on that frame (a
+ * cloud without a valid point: C3H_ERR_STATE, as c3h_compute_normals).  A frame with a negative
+ * status leaves its slot untouched and does not affect the other frames.
+ * Frames go in batches of c3h_set_batch.  Per frame, in turn, the single-frame code runs the
+ * voxeliser, the exact centroids, the leaf layout and (dim 137) the C3-HLAC-117 extract, whose
+ * columns go straight into columns 20 .. 136; c3h_voxelize's one host synchronisation per frame
+ * stays (a batched voxeliser that keeps every centroid would remove it).  Everything else runs
+ * once per batch over the concatenated frames: one keys kernel, one stable radix sort of
+ * (frame, cell) keys and one ranges kernel build every frame's radius-search grid, the normals
+ * run by occupied cell with the cell's neighbourhood staged in LDS (cells of fewer than 16 points
+ * per point, as the single-frame kernel walks them), then the RSD radii, the GRSD
+ * transitions and columns 0 .. 19 of every row.  At most 2^32 - 1 points per batch
+ * (C3H_ERR_RANGE for the call). */
+typedef struct {
+  c3h_grsd_params grsd;    /* subdiv, offset, rsd_radius, normalize */
+  float normals_radius;    /* normals_radius_search (0.02) */
+  float viewpoint[3];
+  int32_t thr[3];          /* the C3-HLAC-117 part; ignored at dim 20 */
+  int32_t color_mode;
+} c3h_vosch_params;
+int c3h_extract_vosch_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t nframes,
+                             int on_device, float leaf, float z_limit, const c3h_vosch_params* p,
+                             int32_t dim /* 137 VOSCH | 20 GRSD */, int64_t row_cap, float* d_rows,
+                             c3h_frame_info* info);
+/* The whole callback of detect_object_vosch_multi.cpp for a batch: the same front end writes
+ * into rows the context owns (row_cap = the canvas_b product), then the body of
+ * c3h_run_feature_frames searches them with the exist rule C3H_EXIST_VOSCH (dim 137) or
+ * C3H_EXIST_GRSD (dim 20): setVOSCH / setGRSD + search() from fresh lists (search_new.h:34-76),
+ * frame i's M x rank records in d_out + i * M * rank (device).  A failed frame, or one whose
+ * counts exceed canvas_b on an axis (C3H_ERR_RANGE), goes in with counts (0, 0, 0): it yields the
+ * setRank state and keeps its negative status in info.  c3h_set_rank, c3h_set_batch,
+ * c3h_set_score_engine, c3h_set_pipeline and c3h_set_remove_overlap apply as they do there.
+ * dim must equal the F of c3h_search_setup (C3H_ERR_ARG before anything is enqueued).  Returns
+ * the number of searched modes or an error. */
+int c3h_run_vosch_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t nframes,
+                               int on_device, float leaf, float z_limit, const c3h_vosch_params* p,
+                               int32_t dim, const int32_t canvas_b[3], const int32_t range[3],
+                               int32_t exist_threshold, int32_t rotate, c3h_det* d_out, c3h_frame_info* info);
+/* Stages of frame `frame` of the last of the two calls above, so that a comparison can say which
+ * stage differs: c3h_get_normals' n x 4 floats (dropped points NaN) and c3h_get_rsd's radii and
+ * types (returns their count; none for a frame without rows).  Valid while that call had at most
+ * one batch (nframes <= c3h_set_batch) and until the next such call; C3H_ERR_STATE otherwise and
+ * for a frame with a negative status. */
+int c3h_get_frame_normals(c3h_ctx* ctx, int32_t frame, float* out, int on_device);
+int c3h_get_frame_rsd(c3h_ctx* ctx, int32_t frame, float* radii, int32_t* types, int on_device);
 /* Frames per pipeline batch / launch in c3h_run_frames and c3h_stream_frames
  * (1..64, default 32; the fast search path only). */
 int c3h_set_batch(c3h_ctx* ctx, int32_t frames);

@@ -392,6 +392,96 @@ class Context:
                                                      ptr(d_out), info), "run_point_frames")
         return nm, self._frame_info(info, len(frames))
 
+    @staticmethod
+    def _vosch_params(thr, subdiv, offset, rsd_radius, normalize, normals_radius, viewpoint, color_mode):
+        p = _capi.VoschParams()
+        p.grsd = Context._grsd_params(subdiv, offset, rsd_radius, normalize)
+        p.normals_radius = float(normals_radius)
+        p.viewpoint = (C.c_float * 3)(*[float(v) for v in viewpoint])
+        p.thr = (C.c_int32 * 3)(*[int(t) for t in thr])
+        p.color_mode = int(color_mode)
+        return p
+
+    def extract_vosch_frames(self, frames, leaf, dim=137, row_cap=None, thr=(0, 0, 0), subdiv=0, offset=(0, 0, 0),
+                             rsd_radius=0.01, normalize=False, normals_radius=0.02, viewpoint=(0.0, 0.0, 0.0),
+                             color_mode=COLOR_C3_DOUBLE, z_limit=float("inf"), rows=None):
+        """c3h_extract_vosch_frames: voxelize + compute_normals + extract_vosch (dim 137) or
+        extract_grsd (dim 20) for a batch of point clouds (a list as run_point_frames takes it, or
+        a PointFrames).  rows: a contiguous float32 device tensor of len(frames) * row_cap * dim
+        elements to write into (None: a new zeroed one; a caller's tensor must be complete on its
+        stream before the call, as every device input of this class).  Returns (views, info): views[i] the
+        (rows of frame i, dim) view of its slot (None for a frame with a negative status), info
+        the structured array of run_point_frames (n_moved: voxels whose centroid lies in another
+        cell; status 0 or the C3H_ERR_* of that frame)."""
+        import torch
+        if not isinstance(frames, PointFrames):
+            frames = self.prepare_point_frames(frames)
+        nf = len(frames)
+        if row_cap is None:
+            raise ValueError("extract_vosch_frames: row_cap (rows per frame slot) is required")
+        row_cap, dim = int(row_cap), int(dim)
+        if rows is None:
+            rows = torch.zeros(max(nf * row_cap * dim, 1), dtype=torch.float32, device="cuda:%d" % self.device)
+            # (the fill runs on torch's stream, the library on the context's: the fill first)
+            torch.cuda.current_stream(rows.device).synchronize()
+        if rows.dtype != torch.float32 or not rows.is_contiguous() or rows.numel() < nf * row_cap * dim or \
+                rows.device.type != "cuda" or (rows.device.index or 0) != self.device:
+            raise ValueError("extract_vosch_frames: rows must be a contiguous float32 tensor of >= %d elements on cuda:%d"
+                             % (nf * row_cap * dim, self.device))
+        p = self._vosch_params(thr, subdiv, offset, rsd_radius, normalize, normals_radius, viewpoint, color_mode)
+        info = (_capi.FrameInfo * max(nf, 1))()
+        self._chk(self.lib.c3h_extract_vosch_frames(self.h, ptr(frames.ptrs), ptr(frames.ns), nf, int(frames.on_device),
+                                                    float(leaf), float(z_limit), C.byref(p), dim, row_cap, ptr(rows),
+                                                    info), "extract_vosch_frames")
+        self.synchronize()
+        self._vf_ns = frames.ns.copy()
+        fi = self._frame_info(info, nf)
+        flat = rows.view(-1)
+        views = []
+        for i in range(nf):
+            h = int(np.prod(fi["subdiv_b"][i].astype(np.int64)))
+            views.append(flat[i * row_cap * dim:(i * row_cap + h) * dim].view(h, dim) if fi["status"][i] >= 0 else None)
+        return views, fi
+
+    def run_vosch_point_frames(self, frames, leaf, canvas_b, ranges, exist_threshold, dim=137, thr=(0, 0, 0), subdiv=0,
+                               offset=(0, 0, 0), rsd_radius=0.01, normalize=False, normals_radius=0.02,
+                               viewpoint=(0.0, 0.0, 0.0), color_mode=COLOR_C3_DOUBLE, z_limit=float("inf"),
+                               rotate=True, d_out=None):
+        """c3h_run_vosch_point_frames: point clouds in, detections out -- the front end of
+        extract_vosch_frames into rows the context owns, then run_feature_frames' search with the
+        setVOSCH (dim 137) / setGRSD (dim 20) exist rule.  d_out = device pointer (int) or tensor of
+        len(frames) * M * rank records.  Returns (modes, info); a frame with a negative status holds
+        the setRank state."""
+        if not isinstance(frames, PointFrames):
+            frames = self.prepare_point_frames(frames)
+        nf = len(frames)
+        self._check_d_out("run_vosch_point_frames", d_out, nf)
+        p = self._vosch_params(thr, subdiv, offset, rsd_radius, normalize, normals_radius, viewpoint, color_mode)
+        info = (_capi.FrameInfo * max(nf, 1))()
+        nm = self._chk(self.lib.c3h_run_vosch_point_frames(
+            self.h, ptr(frames.ptrs), ptr(frames.ns), nf, int(frames.on_device), float(leaf), float(z_limit), C.byref(p),
+            int(dim), i32x3(canvas_b), i32x3(ranges), int(exist_threshold), int(bool(rotate)), ptr(d_out), info),
+            "run_vosch_point_frames")
+        self._vf_ns = frames.ns.copy()
+        if nf:
+            self._refresh()
+        return nm, self._frame_info(info, nf)
+
+    def frame_normals(self, i):
+        """c3h_get_frame_normals: the (n, 4) normals of frame i of the last extract_vosch_frames /
+        run_vosch_point_frames call, one row per input point (dropped points NaN)."""
+        out = np.zeros((int(self._vf_ns[i]), 4), np.float32)
+        self._chk(self.lib.c3h_get_frame_normals(self.h, int(i), ptr(out), 0), "get_frame_normals")
+        return out
+
+    def frame_rsd(self, i):
+        """c3h_get_frame_rsd: (radii, types) per occupied voxel of frame i of the last call."""
+        n = self._chk(self.lib.c3h_get_frame_rsd(self.h, int(i), None, None, 0), "get_frame_rsd")
+        radii = np.zeros((n, 2), np.float32)
+        types = np.zeros(n, np.int32)
+        self._chk(self.lib.c3h_get_frame_rsd(self.h, int(i), ptr(radii), ptr(types), 0), "get_frame_rsd")
+        return radii, types
+
     def _check_d_out(self, what, d_out, nframes):
         if d_out is not None and hasattr(d_out, "data_ptr"):
             need = nframes * max(self.M, 1) * self.rank * DET_DTYPE.itemsize

@@ -39,6 +39,11 @@ class GrsdParams(C.Structure):
                 ("normalize", C.c_int32)]
 
 
+class VoschParams(C.Structure):
+    _fields_ = [("grsd", GrsdParams), ("normals_radius", C.c_float), ("viewpoint", C.c_float * 3),
+                ("thr", C.c_int32 * 3), ("color_mode", C.c_int32)]
+
+
 class Det(C.Structure):
     _fields_ = [("score", C.c_double), ("x", C.c_int32), ("y", C.c_int32), ("z", C.c_int32),
                 ("mode", C.c_int32)]
@@ -125,6 +130,13 @@ _SIGS = {
     "c3h_get_rsd": (C.c_int, [_P, _P, _P, C.c_int]),
     "c3h_extract_vosch": (C.c_int, [_P, C.POINTER(GrsdParams), C.POINTER(C.c_int32), C.c_int32,
                                     C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "c3h_extract_vosch_frames": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int, C.c_float, C.c_float, _P, C.c_int32,
+                                           C.c_int64, _P, _P]),
+    "c3h_run_vosch_point_frames": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int, C.c_float, C.c_float, _P, C.c_int32,
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P,
+                                             _P]),
+    "c3h_get_frame_normals": (C.c_int, [_P, C.c_int32, _P, C.c_int]),
+    "c3h_get_frame_rsd": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int]),
     "c3h_set_search_precision": (C.c_int, [_P, C.c_int32]),
     "c3h_set_score_engine": (C.c_int, [_P, C.c_int32]),
     "c3h_set_remove_overlap": (C.c_int, [_P, C.c_int32]),

@@ -14,6 +14,7 @@
 #include "../../include/c3hlac_mi355x.h"
 #include "occ_sched.h"
 #include "pc2_layout.h"
+#include "vosch_frames.h"
 
 namespace c3h {
 
@@ -417,6 +418,50 @@ hipError_t launch_grsd(const GrsdArgs& a, hipStream_t s);
 hipError_t launch_grsd_feat(const int32_t* trans, int64_t H, float norm, float* out, int stride, hipStream_t s);
 hipError_t launch_vosch_concat(const float* grsd, const float* c3, const int32_t* exist, int64_t H, float* out,
                                hipStream_t s);
+// ---- batched VOSCH / GRSD front (vosch_front.hip; c3h_extract_vosch_frames) ---------------
+// The frames of a batch share one set of launches.  Their points, search cells, centroids and
+// feature rows are concatenated (prefixes: vosch_frames.h); what differs per frame sits in a
+// device table, not in kernel arguments.  A frame's NbrGrid / GrsdArgs hold pointers to its own
+// slices, with positions and point indices local to the frame, so the single-frame device
+// functions (rsd_dev.h) run on them unchanged.
+struct VfFrame {
+  NbrGrid g;             // the normals' search grid
+  NbrGrid g2;            // the RSD's: g, or a grid of the RSD's own radius (grsd_frames' wide-leaf rule)
+  GrsdArgs ga;           // layout unused: the neighbour voxels are looked up in vkeys
+  const int32_t* vkeys;  // linear voxel index of the frame's ga.nc occupied voxels, ascending (leaf order)
+  float* rows;           // the frame's output rows (H x dim)
+};
+struct VfTable {
+  VfFrame fr[kVfMaxFrames];
+  int64_t ppre[kVfMaxFrames + 1];   // points
+  int64_t cpre[kVfMaxFrames + 1];   // search cells of g
+  int64_t c2pre[kVfMaxFrames + 1];  // search cells of g2
+  int64_t vpre[kVfMaxFrames + 1];   // occupied voxels
+  int64_t hpre[kVfMaxFrames + 1];   // rows (subdivisions)
+  int nf;
+};
+// Search grids of every frame at once (which: 0 = g, 1 = g2 with c2pre): composite keys, one
+// stable radix sort, the frames' cell ranges.  keys / keys2: ptot words of 4 (key.wide: 8) bytes;
+// keys2 holds the sorted keys.  cstart / cend: the concatenated tables, zeroed here.
+// tmp == nullptr: size query.
+hipError_t vf_nbr_build(const VfTable* d_tab, int which, const VfKey& key, int64_t ptot, int64_t ctot, void* keys,
+                        void* keys2, uint32_t* idx, uint32_t* idx2, uint32_t* cstart, uint32_t* cend, void* tmp,
+                        size_t* tmp_bytes, hipStream_t s);
+constexpr int kVfMaxReach = 2;  // the cell-staged normals hold (2 * reach + 1)^3 cell ranges in LDS
+// keys: the sorted key array (keys2 of vf_nbr_build)
+// list: vf_dense_cap(ptot) + 1 words (the dense cells of the batch behind their counter)
+constexpr int kVfDenseMin = 16;  // points from which a cell's queries are served from LDS
+inline int64_t vf_dense_cap(int64_t ptot) { return ptot / kVfDenseMin + 1; }
+hipError_t launch_vf_normals(const VfTable* d_tab, const VfKey& key, int64_t ptot, int64_t ctot, const void* keys,
+                             unsigned long long* list, float radius, int reach, const float vp[3], float4* out,
+                             hipStream_t s);
+hipError_t launch_vf_rsd(const VfTable* d_tab, int64_t vtot, const float4* nrm, float max_dist, int reach,
+                         float2* radii, int32_t* types, hipStream_t s);
+hipError_t launch_vf_grsd(const VfTable* d_tab, int64_t vtot, hipStream_t s);
+hipError_t launch_vf_rows(const VfTable* d_tab, int64_t htot, const int32_t* trans, float norm, int dim, hipStream_t s);
+hipError_t launch_vf_vox_keys(const int32_t* layout, int64_t nvox, int64_t nc, int32_t* vkeys, hipStream_t s);
+hipError_t launch_vf_c3_cols(const float* c3, const int32_t* exist, int64_t H, float* rows, hipStream_t s);
+
 // sensor_msgs/PointCloud2 bytes -> n x float4 (x, y, z, rgb bits) (ingest.hip)
 hipError_t launch_pc2_convert(const void* data, uint32_t height, uint32_t width, uint32_t point_step,
                               uint32_t row_step, const int32_t off[4], int big, float* out, hipStream_t s);
@@ -643,6 +688,24 @@ struct c3h_ctx {
   c3h::DevBuf<int32_t> rsd_types, grsd_trans;
   c3h::DevBuf<float> grsd_feat, vosch_feat;
   int64_t rsd_n = 0;                // centroids with valid radii / types
+  // batched VOSCH / GRSD front (c3h_extract_vosch_frames; vosch_front.hip): the device table of
+  // the batch in flight, the concatenated points (host input only), sort buffers, cell tables,
+  // normals, centroids, voxel keys, radii, types and transitions of its frames
+  c3h::DevBuf<c3h::VfTable> vf_tab;
+  c3h::DevBuf<float4> vf_pts, vf_normals, vf_cent;
+  c3h::DevBuf<uint64_t> vf_keys, vf_keys2;
+  c3h::DevBuf<unsigned long long> vf_dense;  // counter + the batch's dense cells
+  c3h::DevBuf<uint32_t> vf_idx, vf_idx2, vf_cstart, vf_cend;
+  c3h::DevBuf<uint8_t> vf_tmp;
+  c3h::DevBuf<int32_t> vf_vkeys, vf_types, vf_trans;
+  c3h::DevBuf<float2> vf_radii;
+  c3h::DevBuf<float> vf_rows;       // c3h_run_vosch_point_frames: the frames' rows (canvas rows each)
+  // what the getters (c3h_get_frame_normals / c3h_get_frame_rsd) may read: the last call's
+  // frames while it had one batch (vf_nframes < 0: more than one, the buffers hold the last)
+  int vf_nframes = 0;
+  std::vector<int64_t> vf_ppre, vf_vpre, vf_n;
+  std::vector<int32_t> vf_status;
+  std::vector<c3h::VfTable> vf_htab;  // host copy of the table (kept alive for the async upload)
   // voxeliser state (voxelize.hip): toroidal accumulators, entry / grid-word lists by
   // epoch parity, counters; the grid words the previous frame wrote are cleared by the next
   c3h::DevBuf<ulonglong2> vacc;

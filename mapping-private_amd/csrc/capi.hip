@@ -1530,24 +1530,17 @@ int c3h_get_normals(c3h_ctx* ctx, float* out, int on_device) {
   return C3H_OK;
 }
 
-// extractGRSDSignature21 (grsd_colorCHLAC_tools.hpp:131-296) into grsd_feat (H x 20)
-static int grsd_frames(c3h_ctx* ctx, const c3h_grsd_params* p, int32_t sb[3], int64_t* Hout) {
-  if (!ctx->normals_valid) return fail(ctx, C3H_ERR_STATE, "extract_grsd: c3h_compute_normals first");
-  const int* div = ctx->info.div_b;
-  int64_t H = 1;
-  float inv_s = 0.0f;
-  sb[0] = sb[1] = sb[2] = 0;
-  *Hout = 0;
-  if (p->subdiv > 0) {
-    inv_s = 1.0 / p->subdiv;
-    if (div[0] <= p->offset[0] || div[1] <= p->offset[1] || div[2] <= p->offset[2]) return C3H_OK;  // :150-153
-    for (int a = 0; a < 3; ++a) sb[a] = (int)ceilf((div[a] - p->offset[a]) * inv_s);
-    H = (int64_t)sb[0] * sb[1] * sb[2];
-  } else if (p->subdiv < 0) {
-    return C3H_OK;  // :159-162: invalid subdivision size -> empty
-  } else {
-    sb[0] = sb[1] = sb[2] = 1;
-  }
+}  // extern "C"
+
+// The head of extractGRSDSignature21 (grsd_colorCHLAC_tools.hpp:131-296) on the grid of the last
+// c3h_voxelize: the subdivision counts (H = 0: the reference's silent-empty cases, nothing was
+// enqueued), the exact centroids, the leaf layout (tmp_i32) and the downsampled centroids in
+// leaf-layout order (dsamp).  c3h_extract_grsd / c3h_extract_vosch go on from here with this
+// frame's RSD; the batched front (capi_vosch.hip) collects the centroids of a batch of frames.
+int c3h::grsd_frame_head(c3h_ctx* ctx, const c3h_grsd_params* p, int32_t sb[3], int64_t* Hout, float* inv_s) {
+  const int64_t H = c3h::vf_subdivisions(ctx->info.div_b, p->subdiv, p->offset, sb, inv_s);  // :150-162
+  *Hout = H;
+  if (H == 0) return C3H_OK;
   const int64_t nc = ctx->info.n_occ;
   const int64_t nvox = grid_voxels(ctx);
   int rc = exact_centroids(ctx);
@@ -1558,6 +1551,21 @@ static int grsd_frames(c3h_ctx* ctx, const c3h_grsd_params* p, int32_t sb[3], in
   ENSURE(ctx->dsamp, (size_t)std::max<int64_t>(nc, 1));
   HIPCHK(c3h::launch_vox_downsampled(ctx->vargs, ctx->vcent.p, ctx->vcounts.p, ctx->tmp_i32.p,
                                      reinterpret_cast<float*>(ctx->dsamp.p), ctx->stream));
+  return C3H_OK;
+}
+
+extern "C" {
+
+// extractGRSDSignature21 (grsd_colorCHLAC_tools.hpp:131-296) into grsd_feat (H x 20)
+static int grsd_frames(c3h_ctx* ctx, const c3h_grsd_params* p, int32_t sb[3], int64_t* Hout) {
+  if (!ctx->normals_valid) return fail(ctx, C3H_ERR_STATE, "extract_grsd: c3h_compute_normals first");
+  const int* div = ctx->info.div_b;
+  int64_t H = 0;
+  float inv_s = 0.0f;
+  *Hout = 0;
+  int rc = c3h::grsd_frame_head(ctx, p, sb, &H, &inv_s);
+  if (rc != C3H_OK || H == 0) return rc;
+  const int64_t nc = ctx->info.n_occ;
   // RSD radius: max(rsd_radius_search, voxel_size / 2 * sqrt(3)) (:172)
   const float max_dist = (float)std::max((double)p->rsd_radius, (double)ctx->info.leaf / 2 * std::sqrt(3.0));
   if (max_dist > 4 * ctx->nbr.cell) {

@@ -99,6 +99,7 @@ int extract_frames(c3h_ctx* ctx, const uint32_t* const* grids, int nf, const c3h
                    int32_t subdiv_out[3], int64_t* hist_num);
 int search_frames(c3h_ctx* ctx, int nf, const int32_t range[3], int32_t thr, int32_t rotate,
                   c3h_det* const* d_outs, int clean);
+int grsd_frame_head(c3h_ctx* ctx, const c3h_grsd_params* p, int32_t sb[3], int64_t* Hout, float* inv_s);
 int search_setup_dev(c3h_ctx* ctx, const float* axis_p, const float* var, int32_t D, int32_t F,
                      const float* axis_q, int32_t M, int32_t r, const float* fmax, int32_t fmax_len, int32_t D_user);
 

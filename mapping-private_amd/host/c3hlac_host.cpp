@@ -1,6 +1,8 @@
 // c3hlac_host.cpp -- the reference-named C++ facade over the C-ABI (see c3hlac_host.h).
 #include "c3hlac_host.h"
 
+#include <dlfcn.h>
+
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -881,6 +883,63 @@ void SearchGRSD::setGRSD(int dim, VoxelGrid& grid, double voxel_size, int subdiv
   (void)dim;
   ensureSetup(20);
   set_external(*this, grid, voxel_size, subdiv, nullptr);
+}
+
+// detect_object_vosch_multi.cpp's callback for a batch of clouds: the reference's radii
+// (normals 0.02, RSD 0.01: grsd_colorCHLAC_tools.h:28-29), no offsets, not normalised
+std::vector<c3h_det> SearchObj::searchBatchPoints(int dim, const int* thr, const std::vector<const float*>& clouds,
+                                                  const std::vector<int64_t>& n, double voxel_size, int subdiv,
+                                                  const Vector3i& canvas_b, bool rotate,
+                                                  std::vector<c3h_frame_info>* info) {
+  if (clouds.size() != n.size()) throw Error(C3H_ERR_ARG, "searchBatch: one point count per cloud");
+  ensureSetup(dim);
+  const int nf = (int)clouds.size();
+  const size_t per_frame = (size_t)std::max((int)axis_q_.size(), 1) * std::max(rank_, 1);
+  c3h_vosch_params p{};
+  p.grsd.subdiv = subdiv;
+  p.grsd.rsd_radius = 0.01f;
+  p.normals_radius = 0.02f;
+  for (int a = 0; a < 3; ++a) p.thr[a] = thr ? thr[a] : 0;
+  p.color_mode = C3H_COLOR_C3_DOUBLE;
+  const int32_t cb[3] = {canvas_b[0], canvas_b[1], canvas_b[2]};
+  std::vector<c3h_det> out((size_t)nf * per_frame);
+  if (info) info->assign((size_t)nf, c3h_frame_info{});
+  // the records land in device memory; this library is plain C++, so the three HIP calls it
+  // needs here come from the runtime the kernel library has already loaded
+  typedef int (*malloc_fn)(void**, size_t);
+  typedef int (*free_fn)(void*);
+  typedef int (*memcpy_fn)(void*, const void*, size_t, int);
+  const malloc_fn hipMalloc = (malloc_fn)dlsym(RTLD_DEFAULT, "hipMalloc");
+  const free_fn hipFree = (free_fn)dlsym(RTLD_DEFAULT, "hipFree");
+  const memcpy_fn hipMemcpy = (memcpy_fn)dlsym(RTLD_DEFAULT, "hipMemcpy");
+  const int hipSuccess = 0, hipMemcpyDeviceToHost = 2;
+  if (!hipMalloc || !hipFree || !hipMemcpy) throw Error(C3H_ERR_HIP, "searchBatch: no HIP runtime loaded");
+  void* d_out = nullptr;
+  if (hipMalloc(&d_out, std::max<size_t>(out.size(), 1) * sizeof(c3h_det)) != hipSuccess)
+    throw Error(C3H_ERR_NOMEM, "searchBatch: hipMalloc");
+  const int rc = c3h_run_vosch_point_frames(ctx_.get(), clouds.data(), n.data(), nf, 0, (float)voxel_size, INFINITY, &p,
+                                            dim, cb, range_, threshold_, rotate ? 1 : 0, (c3h_det*)d_out,
+                                            info ? info->data() : nullptr);
+  int rs = rc < 0 ? rc : c3h_synchronize(ctx_.get());
+  if (rs >= 0 && !out.empty() &&
+      hipMemcpy(out.data(), d_out, out.size() * sizeof(c3h_det), hipMemcpyDeviceToHost) != hipSuccess)
+    rs = C3H_ERR_HIP;
+  (void)hipFree(d_out);
+  ctx_.check(rs, "c3h_run_vosch_point_frames");
+  return out;
+}
+
+std::vector<c3h_det> SearchVOSCH::searchBatch(int r, int g, int b, const std::vector<const float*>& clouds,
+                                              const std::vector<int64_t>& n, double voxel_size, int subdiv,
+                                              const Vector3i& canvas_b, bool rotate, std::vector<c3h_frame_info>* info) {
+  const int thr[3] = {r, g, b};
+  return searchBatchPoints(137, thr, clouds, n, voxel_size, subdiv, canvas_b, rotate, info);
+}
+
+std::vector<c3h_det> SearchGRSD::searchBatch(const std::vector<const float*>& clouds, const std::vector<int64_t>& n,
+                                             double voxel_size, int subdiv, const Vector3i& canvas_b, bool rotate,
+                                             std::vector<c3h_frame_info>* info) {
+  return searchBatchPoints(20, nullptr, clouds, n, voxel_size, subdiv, canvas_b, rotate, info);
 }
 
 }  // namespace c3hlac

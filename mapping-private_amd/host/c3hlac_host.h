@@ -439,6 +439,12 @@ class SearchObj {
   const c3h_det& det(int m, int num) const;
   void ensureSetup(int F);
   void run(bool rotate, bool remove_overlap);
+  // c3h_run_vosch_point_frames: clouds in (n[i] x 4 floats x y z rgb, host), per frame the
+  // setVOSCH / setGRSD + search() of this object from fresh lists; returns frame-major
+  // M x rank records, info (may be nullptr) the frames' c3h_frame_info
+  std::vector<c3h_det> searchBatchPoints(int dim, const int* thr, const std::vector<const float*>& clouds,
+                                         const std::vector<int64_t>& n, double voxel_size, int subdivision_size,
+                                         const Vector3i& canvas_b, bool rotate, std::vector<c3h_frame_info>* info);
 };
 
 // SearchObjMulti (search.h:181-270): M models scored per position, one list per model.
@@ -484,6 +490,11 @@ class SearchVOSCH : public SearchObj {
   using SearchObj::SearchObj;
   void setVOSCH(int dim, int color_threshold_r, int color_threshold_g, int color_threshold_b, VoxelGrid& grid,
                 double voxel_size, int subdivision_size);
+  // a batch of clouds through getVoxelGrid + setVOSCH + search() in one call (c3h_run_vosch_point_frames)
+  std::vector<c3h_det> searchBatch(int color_threshold_r, int color_threshold_g, int color_threshold_b,
+                                   const std::vector<const float*>& clouds, const std::vector<int64_t>& n,
+                                   double voxel_size, int subdivision_size, const Vector3i& canvas_b,
+                                   bool rotate = true, std::vector<c3h_frame_info>* info = nullptr);
 };
 class SearchVOSCHMulti : public SearchObjMulti {
  public:
@@ -495,6 +506,10 @@ class SearchGRSD : public SearchObj {
  public:
   using SearchObj::SearchObj;
   void setGRSD(int dim, VoxelGrid& grid, double voxel_size, int subdivision_size);
+  // a batch of clouds through getVoxelGrid + setGRSD + search() in one call (c3h_run_vosch_point_frames)
+  std::vector<c3h_det> searchBatch(const std::vector<const float*>& clouds, const std::vector<int64_t>& n,
+                                   double voxel_size, int subdivision_size, const Vector3i& canvas_b,
+                                   bool rotate = true, std::vector<c3h_frame_info>* info = nullptr);
 };
 
 }  // namespace c3hlac

@@ -1,0 +1,89 @@
+"""Batched VOSCH / GRSD front (c3h_extract_vosch_frames) without a GPU.
+
+(a) csrc/vosch_frames.h on the host: vosch_frames_check.cpp (its own main) built with
+    -fsanitize=address,undefined and run: the prefixes and the frame of an index at every
+    boundary (empty frames in the middle and at both ends), each frame's search grid against a
+    literal transcription of nbr_grid(), the composite key's widths, packing, order and
+    capacity errors, the subdivision counts against grsd_frames' statements.
+
+(b) The oracle alone (pyoracle.voxelize, grsd_oracle) on the frames of vosch_frames_data.py, so
+    that the GPU checks are not vacuous: the batch holds frames with different div_b and
+    subdiv_b, a frame with more than one non-empty subdivision, every get_type class, and a
+    frame with voxels whose centroid lies in another cell (the edge cloud: 1 at leaf 0.01,
+    where bowl1_0000.pcd has none in its 206 voxels; the fine batch at leaf 0.004 holds that
+    view's 945 voxels, 14 of them off their cell).  These are conditions on the inputs, not
+    tolerances."""
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import grsd_oracle as go
+import pyoracle as po
+import vosch_frames_data as vd
+from conftest import ROOT
+
+
+@pytest.fixture(scope="module")
+def checker(tmp_path_factory):
+    cxx = shutil.which("g++")
+    assert cxx, "g++ is needed to build the vosch-frames check"
+    exe = tmp_path_factory.mktemp("vosch_frames") / "vosch_frames_check"
+    src = ROOT / "tests" / "vosch_frames_check.cpp"
+    inc = ROOT / "mapping-private_amd" / "csrc"
+    p = subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off",
+                        "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I", str(inc), str(src),
+                        "-o", str(exe)], capture_output=True, text=True, timeout=180)
+    assert p.returncode == 0, p.stderr
+    return exe
+
+
+def test_vosch_frames_header_on_the_host(checker):
+    p = subprocess.run([str(checker)], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])
+    lines = p.stdout.strip().splitlines()
+    assert lines[-1] == "vosch_frames ok"
+    stats = {ln.split(":")[0]: int(ln.split()[-1]) for ln in lines[:-1]}
+    assert stats["prefix"] >= 2000 and stats["grid"] >= 240 and stats["key"] >= 14 * 64 * 3 and stats["subdiv"] >= 200, stats
+
+
+@pytest.fixture(scope="module")
+def grids():
+    return {name: po.voxelize(pts, vd.LEAF) for name, pts in vd.batch() if len(pts) > 1}
+
+
+def test_batch_geometry_differs_between_frames(grids):
+    div = {name: tuple(g.div_b[:3]) for name, (g, _, _) in grids.items()}
+    sub = {name: vd.subdivisions(d) for name, d in div.items()}
+    assert len(set(div.values())) >= 4, div
+    assert len(set(sub.values())) >= 3, sub
+    # the plane and the torus are thinner than the z offset: the reference's silent-empty case (no row)
+    flat = ("noisy_plane_purple", "noisy_torus_blue")
+    assert all(sub[name] == (0, 0, 0) for name in flat), sub
+    assert all(min(s) >= 1 for name, s in sub.items() if name not in flat), sub
+    # the z limit of the second run changes the edge cloud's grid, and only cuts it
+    edge = dict(vd.batch())["edge"]
+    g1 = po.voxelize(edge, vd.LEAF, 1.0)[0]
+    assert tuple(g1.div_b[:3]) != div["edge"] and 0 < g1.n_occ < grids["edge"][0].n_occ
+
+
+def test_frames_with_voxels_whose_centroid_lies_in_another_cell(grids):
+    g, layout, cloud = grids["edge"]
+    assert vd.moved_voxels(g, layout, cloud, vd.LEAF) == 1
+    g, layout, cloud = po.voxelize(dict(vd.fine_batch())["bowl1_0000"], vd.FINE_LEAF)
+    assert g.n_occ == 945 and vd.moved_voxels(g, layout, cloud, vd.FINE_LEAF) == 14
+    assert min(vd.subdivisions(g.div_b[:3])) >= 1
+
+
+def test_edge_cloud_fills_subdivisions_with_every_type():
+    pts = dict(vd.batch())["edge"]
+    g, layout, cloud = po.voxelize(pts, vd.LEAF)
+    nrm = go.normals(pts, vd.RADIUS)
+    feat, sb, _, types = go.grsd(pts, nrm, g, layout, cloud, vd.LEAF, subdiv=vd.SUBDIV, offset=vd.OFFSET)
+    assert tuple(sb) == vd.subdivisions(g.div_b[:3])
+    assert (feat.sum(1) > 0).sum() > 1, "more than one non-empty subdivision"
+    assert set(np.unique(types).tolist()) == {0, 1, 2, 3, 4}, np.bincount(types, minlength=5)
+    # EMPTY neighbours (class 5) are counted too: column (i, 5) bins of the upper triangle
+    iu = [(i, j) for i in range(6) for j in range(i, 6)][:20]
+    assert feat[:, [k for k, (_, j) in enumerate(iu) if j == 5]].sum() > 0

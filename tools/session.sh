@@ -34,6 +34,11 @@
 #   wide             63 models of r = 70 on the batch path (tools/wide_models_bench.py), this tree
 #                    and lib/variants/parent.so (the parent commit's library) in alternation,
 #                    three rounds                          -> wide.jsonl
+#   vosch_frames[=S,F]  clouds in, detections out: the per-frame loop against c3h_run_vosch_point_frames
+#                    (tools/vosch_frames_bench.py, setting A | B, F frames; default A,64) -> vosch_frames_S.jsonl
+#   vosch_frames_parent=S,F  the loop alone on lib/variants/parent.so -> vosch_frames_parent_S.jsonl
+#   vosch_frames_prof=S,F    one alternation under rocprofv3 --kernel-trace --stats (the stages of
+#                    either route by kernel)                -> vosch_frames_prof_S/
 # Variants: VARIANT=name selects lib/variants/name.so for the python steps (C3HLAC_LIB).
 set -o pipefail
 TAG=$1
@@ -94,6 +99,16 @@ for step in "$@"; do
         done
       done
       unset C3HLAC_LIB ;;
+    vosch_frames|vosch_frames=*) a=${step#vosch_frames}; a=${a#=}; IFS=, read S F <<< "${a:-A,64}"
+      timeout -k 10 900 python -u tools/vosch_frames_bench.py --setting $S --frames $F \
+        >> $O/vosch_frames_$S.jsonl 2>> $O/vosch_frames.err || exit 30 ;;
+    vosch_frames_parent=*) a=${step#vosch_frames_parent=}; IFS=, read S F <<< "$a"
+      C3HLAC_LIB=$R/mapping-private_amd/lib/variants/parent.so timeout -k 10 900 python -u tools/vosch_frames_bench.py \
+        --setting $S --frames $F --route loop >> $O/vosch_frames_parent_$S.jsonl 2>> $O/vosch_frames.err || exit 31 ;;
+    vosch_frames_prof=*) a=${step#vosch_frames_prof=}; IFS=, read S F <<< "$a"
+      prof 600 rocprofv3 --kernel-trace --stats -d $O/vosch_frames_prof_$S -o run --output-format csv -- \
+            python3 $R/tools/vosch_frames_bench.py --setting $S --frames $F --reps 1 --searches small \
+            > $O/vosch_frames_prof_$S.jsonl 2> $O/vosch_frames_prof.err || exit 32 ;;
     *) echo "unknown step $step" >&2; exit 2 ;;
   esac
 done
