@@ -474,16 +474,17 @@ int c3h_stream_feature_frames(c3h_ctx* ctx, const float* const* d_feat, const in
  * more than row_cap rows, else the error the single-frame route fails with on that frame (a
  * cloud without a valid point: C3H_ERR_STATE, as c3h_compute_normals).  A frame with a negative
  * status leaves its slot untouched and does not affect the other frames.
- * Frames go in batches of c3h_set_batch.  Per frame, in turn, the single-frame code runs the
+ * Frames go in batches of c3h_set_batch.  Per frame, in turn, the library runs c3h_voxelize's
  * voxeliser, the exact centroids, the leaf layout and (dim 137) the C3-HLAC-117 extract, whose
  * columns go straight into columns 20 .. 136; c3h_voxelize's one host synchronisation per frame
  * stays (a batched voxeliser that keeps every centroid would remove it).  Everything else runs
  * once per batch over the concatenated frames: one keys kernel, one stable radix sort of
  * (frame, cell) keys and one ranges kernel build every frame's radius-search grid, the normals
  * run by occupied cell with the cell's neighbourhood staged in LDS (cells of fewer than 16 points
- * per point, as the single-frame kernel walks them), then the RSD radii, the GRSD
+ * per point), then the RSD radii, the GRSD
  * transitions and columns 0 .. 19 of every row.  At most 2^32 - 1 points per batch
- * (C3H_ERR_RANGE for the call). */
+ * (C3H_ERR_RANGE for the call).  c3h_compute_normals and c3h_extract_grsd / c3h_extract_vosch
+ * are this front over one frame, in the same buffers. */
 typedef struct {
   c3h_grsd_params grsd;    /* subdiv, offset, rsd_radius, normalize */
   float normals_radius;    /* normals_radius_search (0.02) */
@@ -512,8 +513,10 @@ int c3h_run_vosch_point_frames(c3h_ctx* ctx, const float* const* pts, const int6
 /* Stages of frame `frame` of the last of the two calls above, so that a comparison can say which
  * stage differs: c3h_get_normals' n x 4 floats (dropped points NaN) and c3h_get_rsd's radii and
  * types (returns their count; none for a frame without rows).  Valid while that call had at most
- * one batch (nframes <= c3h_set_batch) and until the next such call; C3H_ERR_STATE otherwise and
- * for a frame with a negative status. */
+ * one batch (nframes <= c3h_set_batch) and until the next such call or the next
+ * c3h_compute_normals, c3h_extract_grsd or c3h_extract_vosch, which take the same buffers for
+ * their one frame (as a batch call, voxelising, invalidates c3h_get_normals / c3h_get_rsd);
+ * C3H_ERR_STATE otherwise and for a frame with a negative status. */
 int c3h_get_frame_normals(c3h_ctx* ctx, int32_t frame, float* out, int on_device);
 int c3h_get_frame_rsd(c3h_ctx* ctx, int32_t frame, float* radii, int32_t* types, int on_device);
 /* Frames per pipeline batch / launch in c3h_run_frames and c3h_stream_frames

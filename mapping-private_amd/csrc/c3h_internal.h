@@ -385,7 +385,7 @@ hipError_t launch_offcell_delta(const int32_t* rec, int nrec, const C3Launch& l,
                                 const int sb[3], float inv_s, hipStream_t s);
 hipError_t launch_c3_finalize(const unsigned long long* acc64, int64_t hist_num, int variant,
                               float* feat, int32_t* exist, int nframes, hipStream_t s);
-// radius-search grid over a point cloud (rsd.hip): cells of `cell` metres from origin,
+// radius-search grid over a point cloud (vosch_front.hip): cells of `cell` metres from origin,
 // the points sorted by cell, per cell its [cstart, cend) range in `sorted`.  Points the
 // voxeliser dropped (non-finite, z >= z_limit: limitPoint) are in no cell
 struct NbrGrid {
@@ -402,43 +402,35 @@ struct NbrGrid {
 struct GrsdArgs {
   const float4* cent;     // downsampled centroids, leaf-layout order
   int64_t nc;
-  const int32_t* layout;  // leaf layout (-1 empty)
   const int32_t* types;   // per centroid
   int32_t* trans;         // hist_num x 6 x 6
   int div_b[3], min_b[3], off[3], sb[3];
   float leaf, inv_leaf, inv_s;
   int hist1;              // one histogram for the whole cloud
 };
-hipError_t nbr_build(NbrGrid& g, uint32_t* keys, uint32_t* keys2, uint32_t* idx, uint32_t* idx2, void* tmp,
-                     size_t* tmp_bytes, hipStream_t s);
-hipError_t launch_normals(const NbrGrid& g, float radius, const float vp[3], float4* out, hipStream_t s);
-hipError_t launch_rsd(const NbrGrid& g, const float4* nrm, const float4* cent, int64_t nc, float max_dist,
-                      float2* radii, int32_t* types, hipStream_t s);
-hipError_t launch_grsd(const GrsdArgs& a, hipStream_t s);
-hipError_t launch_grsd_feat(const int32_t* trans, int64_t H, float norm, float* out, int stride, hipStream_t s);
-hipError_t launch_vosch_concat(const float* grsd, const float* c3, const int32_t* exist, int64_t H, float* out,
-                               hipStream_t s);
-// ---- batched VOSCH / GRSD front (vosch_front.hip; c3h_extract_vosch_frames) ---------------
-// The frames of a batch share one set of launches.  Their points, search cells, centroids and
+// ---- the normals / RSD / GRSD front (vosch_front.hip) -------------------------------------
+// The frames of a batch share one set of launches; c3h_compute_normals and c3h_extract_grsd /
+// c3h_extract_vosch run a batch of one.  The frames' points, search cells, centroids and
 // feature rows are concatenated (prefixes: vosch_frames.h); what differs per frame sits in a
 // device table, not in kernel arguments.  A frame's NbrGrid / GrsdArgs hold pointers to its own
-// slices, with positions and point indices local to the frame, so the single-frame device
-// functions (rsd_dev.h) run on them unchanged.
+// slices, with positions and point indices local to the frame, which is what the device
+// functions (rsd_dev.h) work on.
 struct VfFrame {
   NbrGrid g;             // the normals' search grid
-  NbrGrid g2;            // the RSD's: g, or a grid of the RSD's own radius (grsd_frames' wide-leaf rule)
-  GrsdArgs ga;           // layout unused: the neighbour voxels are looked up in vkeys
+  NbrGrid g2;            // the RSD's: g, or a grid of the RSD's own radius (the wide-leaf rule)
+  GrsdArgs ga;           // the neighbour voxels are looked up in vkeys
   const int32_t* vkeys;  // linear voxel index of the frame's ga.nc occupied voxels, ascending (leaf order)
+  const int32_t* layout; // or, while the frame's leaf layout is at hand (a single frame), the layout itself
   float* rows;           // the frame's output rows (H x dim)
 };
 struct VfTable {
-  VfFrame fr[kVfMaxFrames];
   int64_t ppre[kVfMaxFrames + 1];   // points
   int64_t cpre[kVfMaxFrames + 1];   // search cells of g
   int64_t c2pre[kVfMaxFrames + 1];  // search cells of g2
   int64_t vpre[kVfMaxFrames + 1];   // occupied voxels
   int64_t hpre[kVfMaxFrames + 1];   // rows (subdivisions)
   int nf;
+  VfFrame fr[kVfMaxFrames];         // last: a call uploads the table up to fr[nf]
 };
 // Search grids of every frame at once (which: 0 = g, 1 = g2 with c2pre): composite keys, one
 // stable radix sort, the frames' cell ranges.  keys / keys2: ptot words of 4 (key.wide: 8) bytes;
@@ -450,9 +442,10 @@ hipError_t vf_nbr_build(const VfTable* d_tab, int which, const VfKey& key, int64
 constexpr int kVfMaxReach = 2;  // the cell-staged normals hold (2 * reach + 1)^3 cell ranges in LDS
 // keys: the sorted key array (keys2 of vf_nbr_build)
 // list: vf_dense_cap(ptot) + 1 words (the dense cells of the batch behind their counter)
+// nf: the frames of the table; one frame takes the per-point kernel, keys and list unused
 constexpr int kVfDenseMin = 16;  // points from which a cell's queries are served from LDS
 inline int64_t vf_dense_cap(int64_t ptot) { return ptot / kVfDenseMin + 1; }
-hipError_t launch_vf_normals(const VfTable* d_tab, const VfKey& key, int64_t ptot, int64_t ctot, const void* keys,
+hipError_t launch_vf_normals(const VfTable* d_tab, int nf, const VfKey& key, int64_t ptot, int64_t ctot, const void* keys,
                              unsigned long long* list, float radius, int reach, const float vp[3], float4* out,
                              hipStream_t s);
 hipError_t launch_vf_rsd(const VfTable* d_tab, int64_t vtot, const float4* nrm, float max_dist, int reach,
@@ -461,6 +454,22 @@ hipError_t launch_vf_grsd(const VfTable* d_tab, int64_t vtot, hipStream_t s);
 hipError_t launch_vf_rows(const VfTable* d_tab, int64_t htot, const int32_t* trans, float norm, int dim, hipStream_t s);
 hipError_t launch_vf_vox_keys(const int32_t* layout, int64_t nvox, int64_t nc, int32_t* vkeys, hipStream_t s);
 hipError_t launch_vf_c3_cols(const float* c3, const int32_t* exist, int64_t H, float* rows, hipStream_t s);
+// What the host knows of one frame of the front: the normals' half after its c3h_voxelize, the
+// GRSD half after its head (capi_vosch.hip fills a VfFrame from it)
+struct VfHostFrame {
+  VfGrid g, g2;          // g2 = g unless the RSD has a grid of its own
+  const float4* pts;     // the points c3h_voxelize read, n of them
+  int64_t n;
+  float z_limit;
+  c3h_grid_info gi;
+  int32_t sb[3], off[3];
+  int64_t H, nc;         // rows; centroids (0 where H is 0)
+  float inv_s;
+  const float4* cent;    // nc downsampled centroids, leaf-layout order
+  int32_t* vkeys;        // their linear voxel indices (a batch),
+  const int32_t* layout; //   or the leaf layout they came from (a single frame)
+  float* rows;           // H rows of the call's dim
+};
 
 // sensor_msgs/PointCloud2 bytes -> n x float4 (x, y, z, rgb bits) (ingest.hip)
 hipError_t launch_pc2_convert(const void* data, uint32_t height, uint32_t width, uint32_t point_step,
@@ -677,19 +686,14 @@ struct c3h_ctx {
   c3h::DevBuf<float> pts;           // staging copy of host points
   c3h::DevBuf<uint32_t> raw;        // staging copy of host PointCloud2 bytes
   c3h::DevBuf<float> dsbuf;         // host readback staging of the downsampled cloud
-  // normals / RSD / GRSD (rsd.hip): radius-search grid of the last voxelize's points
-  c3h::DevBuf<float4> normals;
+  // normals / RSD / GRSD of the last c3h_voxelize's points (capi_vosch.hip): a batch of one
+  // frame in the vf_* buffers below
   bool normals_valid = false;
-  c3h::NbrGrid nbr{};
-  c3h::DevBuf<uint32_t> nkeys, nkeys2, nidx, nidx2, ncstart, ncend;
-  c3h::DevBuf<uint8_t> ntmp;
+  c3h::VfHostFrame vf_one{};        // that frame (g: the grid the cell tables hold now)
   c3h::DevBuf<float4> dsamp;        // downsampled centroids (leaf-layout order)
-  c3h::DevBuf<float2> rsd_radii;
-  c3h::DevBuf<int32_t> rsd_types, grsd_trans;
-  c3h::DevBuf<float> grsd_feat, vosch_feat;
   int64_t rsd_n = 0;                // centroids with valid radii / types
-  // batched VOSCH / GRSD front (c3h_extract_vosch_frames; vosch_front.hip): the device table of
-  // the batch in flight, the concatenated points (host input only), sort buffers, cell tables,
+  // the front (vosch_front.hip): the device table of the batch in flight, the concatenated
+  // points (host input only), sort buffers (the sorted voxeliser borrows them), cell tables,
   // normals, centroids, voxel keys, radii, types and transitions of its frames
   c3h::DevBuf<c3h::VfTable> vf_tab;
   c3h::DevBuf<float4> vf_pts, vf_normals, vf_cent;
@@ -699,13 +703,15 @@ struct c3h_ctx {
   c3h::DevBuf<uint8_t> vf_tmp;
   c3h::DevBuf<int32_t> vf_vkeys, vf_types, vf_trans;
   c3h::DevBuf<float2> vf_radii;
-  c3h::DevBuf<float> vf_rows;       // c3h_run_vosch_point_frames: the frames' rows (canvas rows each)
+  c3h::DevBuf<float> vf_rows;       // c3h_run_vosch_point_frames: the frames' rows (canvas rows each);
+                                    // c3h_extract_vosch: the 137-wide rows before they become feat
   // what the getters (c3h_get_frame_normals / c3h_get_frame_rsd) may read: the last call's
   // frames while it had one batch (vf_nframes < 0: more than one, the buffers hold the last)
   int vf_nframes = 0;
   std::vector<int64_t> vf_ppre, vf_vpre, vf_n;
   std::vector<int32_t> vf_status;
-  std::vector<c3h::VfTable> vf_htab;  // host copy of the table (kept alive for the async upload)
+  c3h::VfTable* vf_htab = nullptr;  // pinned host copy of the table (its upload is asynchronous)
+  hipEvent_t vf_up_ev = nullptr;    // behind the table's last upload: the host copy may change again
   // voxeliser state (voxelize.hip): toroidal accumulators, entry / grid-word lists by
   // epoch parity, counters; the grid words the previous frame wrote are cleared by the next
   c3h::DevBuf<ulonglong2> vacc;

@@ -672,6 +672,8 @@ void c3h_destroy(c3h_ctx* ctx) {
     (void)hipEventDestroy(e.second);
   }
   if (ctx->h_small) (void)hipHostFree(ctx->h_small);
+  if (ctx->vf_htab) (void)hipHostFree(ctx->vf_htab);
+  if (ctx->vf_up_ev) (void)hipEventDestroy(ctx->vf_up_ev);
   if (ctx->h_recs) (void)hipHostFree(ctx->h_recs);
   if (ctx->h_dl) (void)hipHostFree(ctx->h_dl);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -893,11 +895,13 @@ int c3h_voxelize(c3h_ctx* ctx, const float* xyzrgb, int64_t n, int on_device, fl
     ENSURE(ctx->voffcell, (size_t)std::max<uint64_t>(nvalid, 1) * 8);
     ENSURE(ctx->vbucket, npts);
     ENSURE(ctx->tmp_u32, (size_t)c3h::scan_blocks((int64_t)nvalid));
-    ENSURE(ctx->nkeys, npts);
-    ENSURE(ctx->nkeys2, npts);
-    ENSURE(ctx->nidx, npts);
-    ENSURE(ctx->nidx2, npts);
-    c3h::VoxSortBufs sb{ctx->nkeys.p, ctx->nkeys2.p, ctx->nidx.p, ctx->nidx2.p, ctx->vbucket.p, ctx->tmp_u32.p,
+    // the sort's scratch: the front's sort buffers (every normals / GRSD result is invalid by now)
+    ENSURE(ctx->vf_keys, (npts + 1) / 2);
+    ENSURE(ctx->vf_keys2, (npts + 1) / 2);
+    ENSURE(ctx->vf_idx, npts);
+    ENSURE(ctx->vf_idx2, npts);
+    c3h::VoxSortBufs sb{reinterpret_cast<uint32_t*>(ctx->vf_keys.p), reinterpret_cast<uint32_t*>(ctx->vf_keys2.p),
+                        ctx->vf_idx.p, ctx->vf_idx2.p, ctx->vbucket.p, ctx->tmp_u32.p,
                         reinterpret_cast<int32_t*>(ctx->voffs.p), nullptr, 0};
     int mn[3], dv[3];
     for (int ax = 0; ax < 3; ++ax) {
@@ -906,9 +910,9 @@ int c3h_voxelize(c3h_ctx* ctx, const float* xyzrgb, int64_t n, int on_device, fl
     }
     HIPCHK(c3h::launch_vox_sorted(a, mn, dv, (int64_t)nvalid, sb, ctx->vcounts.p, ctx->vcent.p, ctx->voffcell.p,
                                   ctx->stream));
-    ENSURE(ctx->ntmp, std::max<size_t>(sb.tmp_bytes, 1));
-    sb.tmp = ctx->ntmp.p;
-    sb.tmp_bytes = ctx->ntmp.n;
+    ENSURE(ctx->vf_tmp, std::max<size_t>(sb.tmp_bytes, 1));
+    sb.tmp = ctx->vf_tmp.p;
+    sb.tmp_bytes = ctx->vf_tmp.n;
     {
       Timed t(ctx, 0);
       HIPCHK(c3h::launch_vox_sorted(a, mn, dv, (int64_t)nvalid, sb, ctx->vcounts.p, ctx->vcent.p, ctx->voffcell.p,
@@ -1468,75 +1472,13 @@ int c3h_voxelize_pointcloud2(c3h_ctx* ctx, const void* data, uint32_t height, ui
   return c3h_voxelize(ctx, ctx->pts.p, n, 1, leaf, z_limit, info);
 }
 
-// ---- normals, RSD, GRSD, VOSCH (rsd.hip; grsd_colorCHLAC_tools.hpp) -----------------
-// radius-search grid over the points of the last c3h_voxelize (those it kept)
-static int nbr_grid(c3h_ctx* ctx, float cell) {
-  const c3h::VoxArgs& a = ctx->vargs;
-  c3h::NbrGrid g{};
-  g.pts = a.pts;
-  g.n = a.n;
-  g.z_limit = a.z_limit;
-  g.cell = cell;
-  g.inv_cell = 1.0f / cell;
-  for (int ax = 0; ax < 3; ++ax) {
-    const double lo = (double)ctx->info.min_b[ax] * ctx->info.leaf, hi = (double)(ctx->info.max_b[ax] + 1) * ctx->info.leaf;
-    g.origin[ax] = (float)(lo - cell);
-    g.dim[ax] = (int)std::ceil((hi - lo) / cell) + 3;
-  }
-  const int64_t ncell = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
-  if (ncell > ((int64_t)1 << 27)) return fail(ctx, C3H_ERR_RANGE, "normals: more than 2^27 search cells");
-  const size_t n = (size_t)std::max<int64_t>(g.n, 1);
-  ENSURE(ctx->nkeys, n);
-  ENSURE(ctx->nkeys2, n);
-  ENSURE(ctx->nidx, n);
-  ENSURE(ctx->nidx2, n);
-  ENSURE(ctx->ncstart, (size_t)ncell);
-  ENSURE(ctx->ncend, (size_t)ncell);
-  g.cstart = ctx->ncstart.p;
-  g.cend = ctx->ncend.p;
-  size_t tb = 0;
-  HIPCHK(c3h::nbr_build(g, ctx->nkeys.p, ctx->nkeys2.p, ctx->nidx.p, ctx->nidx2.p, nullptr, &tb, ctx->stream));
-  ENSURE(ctx->ntmp, std::max<size_t>(tb, 1));
-  tb = ctx->ntmp.n;
-  HIPCHK(c3h::nbr_build(g, ctx->nkeys.p, ctx->nkeys2.p, ctx->nidx.p, ctx->nidx2.p, ctx->ntmp.p, &tb, ctx->stream));
-  ctx->nbr = g;
-  return C3H_OK;
-}
-
-int c3h_compute_normals(c3h_ctx* ctx, float radius, const float viewpoint[3]) {
-  if (!ctx || !(radius > 0)) return C3H_ERR_ARG;
-  QUIESCE(ctx);
-  if (!ctx->have_grid || !ctx->table_valid)
-    return fail(ctx, C3H_ERR_STATE, "compute_normals: needs the points of a c3h_voxelize");
-  HIPCHK(hipSetDevice(ctx->device));
-  ctx->normals_valid = false;
-  int rc = nbr_grid(ctx, radius);
-  if (rc != C3H_OK) return rc;
-  ENSURE(ctx->normals, (size_t)std::max<int64_t>(ctx->vargs.n, 1));
-  const float vp0[3] = {0.0f, 0.0f, 0.0f};
-  HIPCHK(c3h::launch_normals(ctx->nbr, radius, viewpoint ? viewpoint : vp0, ctx->normals.p, ctx->stream));
-  ctx->normals_valid = true;
-  return C3H_OK;
-}
-
-int c3h_get_normals(c3h_ctx* ctx, float* out, int on_device) {
-  if (!ctx || !out) return C3H_ERR_ARG;
-  QUIESCE(ctx);
-  if (!ctx->normals_valid) return fail(ctx, C3H_ERR_STATE, "get_normals: c3h_compute_normals first");
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipMemcpyAsync(out, ctx->normals.p, (size_t)ctx->vargs.n * 16,
-                        on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return C3H_OK;
-}
-
 }  // extern "C"
 
 // The head of extractGRSDSignature21 (grsd_colorCHLAC_tools.hpp:131-296) on the grid of the last
 // c3h_voxelize: the subdivision counts (H = 0: the reference's silent-empty cases, nothing was
 // enqueued), the exact centroids, the leaf layout (tmp_i32) and the downsampled centroids in
-// leaf-layout order (dsamp).  c3h_extract_grsd / c3h_extract_vosch go on from here with this
-// frame's RSD; the batched front (capi_vosch.hip) collects the centroids of a batch of frames.
+// leaf-layout order (dsamp).  The front (capi_vosch.hip) goes on from here: c3h_extract_grsd /
+// c3h_extract_vosch with this frame alone, a batch with the collected centroids of its frames.
 int c3h::grsd_frame_head(c3h_ctx* ctx, const c3h_grsd_params* p, int32_t sb[3], int64_t* Hout, float* inv_s) {
   const int64_t H = c3h::vf_subdivisions(ctx->info.div_b, p->subdiv, p->offset, sb, inv_s);  // :150-162
   *Hout = H;
@@ -1555,139 +1497,6 @@ int c3h::grsd_frame_head(c3h_ctx* ctx, const c3h_grsd_params* p, int32_t sb[3], 
 }
 
 extern "C" {
-
-// extractGRSDSignature21 (grsd_colorCHLAC_tools.hpp:131-296) into grsd_feat (H x 20)
-static int grsd_frames(c3h_ctx* ctx, const c3h_grsd_params* p, int32_t sb[3], int64_t* Hout) {
-  if (!ctx->normals_valid) return fail(ctx, C3H_ERR_STATE, "extract_grsd: c3h_compute_normals first");
-  const int* div = ctx->info.div_b;
-  int64_t H = 0;
-  float inv_s = 0.0f;
-  *Hout = 0;
-  int rc = c3h::grsd_frame_head(ctx, p, sb, &H, &inv_s);
-  if (rc != C3H_OK || H == 0) return rc;
-  const int64_t nc = ctx->info.n_occ;
-  // RSD radius: max(rsd_radius_search, voxel_size / 2 * sqrt(3)) (:172)
-  const float max_dist = (float)std::max((double)p->rsd_radius, (double)ctx->info.leaf / 2 * std::sqrt(3.0));
-  if (max_dist > 4 * ctx->nbr.cell) {
-    // a wide RSD radius (large leaves: leaf sqrt(3)/2 > 4 x the normal radius) gets a search
-    // grid of its own radius; the normals are already computed, and the RSD's per-bin
-    // min/max angles do not depend on the neighbour visiting order
-    rc = nbr_grid(ctx, max_dist);
-    if (rc != C3H_OK) return rc;
-  }
-  ENSURE(ctx->rsd_radii, (size_t)std::max<int64_t>(nc, 1));
-  ENSURE(ctx->rsd_types, (size_t)std::max<int64_t>(nc, 1));
-  HIPCHK(c3h::launch_rsd(ctx->nbr, ctx->normals.p, ctx->dsamp.p, nc, max_dist, ctx->rsd_radii.p, ctx->rsd_types.p,
-                         ctx->stream));
-  ctx->rsd_n = nc;
-  ENSURE(ctx->grsd_trans, (size_t)H * 36);
-  HIPCHK(hipMemsetAsync(ctx->grsd_trans.p, 0, (size_t)H * 36 * 4, ctx->stream));
-  c3h::GrsdArgs ga{};
-  ga.cent = ctx->dsamp.p;
-  ga.nc = nc;
-  ga.layout = ctx->tmp_i32.p;
-  ga.types = ctx->rsd_types.p;
-  ga.trans = ctx->grsd_trans.p;
-  for (int a = 0; a < 3; ++a) {
-    ga.div_b[a] = div[a];
-    ga.min_b[a] = ctx->info.min_b[a];
-    ga.off[a] = p->subdiv > 0 ? p->offset[a] : 0;
-    ga.sb[a] = sb[a];
-  }
-  ga.leaf = ctx->info.leaf;
-  ga.inv_leaf = 1.0f / ctx->info.leaf;
-  ga.inv_s = inv_s;
-  ga.hist1 = H == 1 ? 1 : 0;
-  HIPCHK(c3h::launch_grsd(ga, ctx->stream));
-  ENSURE(ctx->grsd_feat, (size_t)H * 20);
-  // NORMALIZE_GRSD = 20 / 26 (grsd_colorCHLAC_tools.h:32) when is_normalize
-  HIPCHK(c3h::launch_grsd_feat(ctx->grsd_trans.p, H, p->normalize ? (float)(20.0 / 26) : 1.0f, ctx->grsd_feat.p, 20,
-                               ctx->stream));
-  *Hout = H;
-  return C3H_OK;
-}
-
-int c3h_extract_grsd(c3h_ctx* ctx, const c3h_grsd_params* p, int32_t subdiv_out[3], int64_t* hist_num) {
-  if (!ctx || !p) return C3H_ERR_ARG;
-  QUIESCE(ctx);
-  if (!ctx->have_grid || !ctx->table_valid) return fail(ctx, C3H_ERR_STATE, "extract_grsd: no c3h_voxelize grid");
-  HIPCHK(hipSetDevice(ctx->device));
-  ctx->have_feat = false;
-  ctx->feat_listed = false;
-  ctx->g_valid = false;
-  ctx->rows_valid = false;
-  ctx->exist_gates_rows = false;
-  int32_t sb[3];
-  int64_t H = 0;
-  int rc = grsd_frames(ctx, p, sb, &H);
-  if (rc != C3H_OK) return rc;
-  ctx->feat16_pending = false;
-  ENSURE(ctx->feat, (size_t)std::max<int64_t>(H, 1) * 20);
-  ENSURE(ctx->exist, (size_t)std::max<int64_t>(H, 1));
-  if (H > 0) {
-    HIPCHK(hipMemcpyAsync(ctx->feat.p, ctx->grsd_feat.p, (size_t)H * 20 * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(c3h::launch_exist_rule(ctx->feat.p, H, 20, C3H_EXIST_GRSD, ctx->exist.p, ctx->stream));
-  }
-  ctx->hist_num = H;
-  ctx->feat_dim = 20;
-  for (int a = 0; a < 3; ++a) ctx->subdiv_b[a] = sb[a];
-  ctx->nframes_feat = 1;
-  ctx->feat_sparse = false;
-  ctx->have_feat = true;
-  if (subdiv_out) memcpy(subdiv_out, sb, sizeof(sb));
-  if (hist_num) *hist_num = H;
-  return C3H_OK;
-}
-
-int c3h_get_rsd(c3h_ctx* ctx, float* radii, int32_t* types, int on_device) {
-  if (!ctx) return C3H_ERR_ARG;
-  QUIESCE(ctx);
-  if (ctx->rsd_n == 0 && !ctx->normals_valid) return fail(ctx, C3H_ERR_STATE, "get_rsd: no RSD computed");
-  HIPCHK(hipSetDevice(ctx->device));
-  const hipMemcpyKind k = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  if (radii && ctx->rsd_n) HIPCHK(hipMemcpyAsync(radii, ctx->rsd_radii.p, (size_t)ctx->rsd_n * 8, k, ctx->stream));
-  if (types && ctx->rsd_n) HIPCHK(hipMemcpyAsync(types, ctx->rsd_types.p, (size_t)ctx->rsd_n * 4, k, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return (int)std::min<int64_t>(ctx->rsd_n, INT_MAX);
-}
-
-// extractVOSCH (grsd_colorCHLAC_tools.hpp:832-843): [GRSD-20 | C3-HLAC-117] per subdivision
-int c3h_extract_vosch(c3h_ctx* ctx, const c3h_grsd_params* p, const int32_t thr[3], int32_t color_mode,
-                      int32_t subdiv_out[3], int64_t* hist_num) {
-  if (!ctx || !p || !thr) return C3H_ERR_ARG;
-  QUIESCE(ctx);
-  if (!ctx->have_grid || !ctx->table_valid) return fail(ctx, C3H_ERR_STATE, "extract_vosch: no c3h_voxelize grid");
-  HIPCHK(hipSetDevice(ctx->device));
-  int32_t sb[3];
-  int64_t H = 0;
-  int rc = grsd_frames(ctx, p, sb, &H);
-  if (rc != C3H_OK) return rc;
-  c3h_extract_params e{};
-  e.variant = 117;
-  for (int a = 0; a < 3; ++a) {
-    e.thr[a] = thr[a];
-    e.offset[a] = p->offset[a];
-  }
-  e.subdiv = p->subdiv;
-  e.color_mode = color_mode;
-  const uint32_t* g = ctx->grid_ptr;
-  int32_t sb2[3];
-  int64_t H2 = 0;
-  rc = extract_frames(ctx, &g, 1, &e, sb2, &H2);
-  if (rc != C3H_OK) return rc;
-  if (H2 != H) return fail(ctx, C3H_ERR_STATE, "extract_vosch: GRSD / C3 subdivisions differ");
-  ENSURE(ctx->vosch_feat, (size_t)std::max<int64_t>(H, 1) * 137);
-  HIPCHK(c3h::launch_vosch_concat(ctx->grsd_feat.p, ctx->feat.p, ctx->exist.p, H, ctx->vosch_feat.p, ctx->stream));
-  std::swap(ctx->feat, ctx->vosch_feat);
-  ctx->feat_dim = 137;
-  ctx->feat_sparse = false;
-  ctx->g_valid = false;
-  ctx->rows_valid = false;
-  ctx->exist_gates_rows = false;
-  if (subdiv_out) memcpy(subdiv_out, sb, sizeof(sb));
-  if (hist_num) *hist_num = H;
-  return C3H_OK;
-}
 
 // SearchObj::setData (search.cpp:539-658) with caller-computed features (VOSCH, GRSD,
 // ConVOSCH, or C3-HLAC rows from elsewhere): the next search consumes them

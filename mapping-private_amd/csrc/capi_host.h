@@ -1,6 +1,6 @@
-// capi_host.h -- what the two host units of the C-ABI share: capi.hip (the context, the
-// single-frame path, the readbacks) and capi_batch.hip (the lanes, the pipeline, the batch
-// entry points).  Host only; private to those two files.
+// capi_host.h -- what the host units of the C-ABI share: capi.hip (the context, the
+// single-frame path, the readbacks), capi_batch.hip (the lanes, the pipeline, the batch
+// entry points) and capi_vosch.hip (normals, RSD, GRSD, VOSCH).  Host only; private to them.
 #pragma once
 #include <string>
 
@@ -92,7 +92,7 @@ inline int pc2_check(c3h_ctx* ctx, uint32_t height, uint32_t width, uint32_t poi
   return C3H_OK;
 }
 
-// the single-frame path's steps the batch code sequences (capi.hip)
+// the single-frame path's steps the batch code and the GRSD front sequence (capi.hip)
 int mode_schedule(int r1, int r2, int r3, int rotate, int* modes);
 bool extract_params_ok(const c3h_extract_params* p);
 int extract_frames(c3h_ctx* ctx, const uint32_t* const* grids, int nf, const c3h_extract_params* p,

@@ -1,15 +1,20 @@
-// capi_vosch.hip -- point clouds in, VOSCH / GRSD rows out, for a batch of frames
-// (c3h_extract_vosch_frames, c3h_run_vosch_point_frames and their getters).
+// capi_vosch.hip -- normals, RSD, GRSD and VOSCH rows of point clouds: the host side of the
+// front (vosch_front.hip) for one frame (c3h_compute_normals, c3h_extract_grsd,
+// c3h_extract_vosch and their getters) and for a batch of frames (c3h_extract_vosch_frames,
+// c3h_run_vosch_point_frames and theirs).
 //
-// Per frame, in turn, the single-frame code computes what only it can: the voxel grid
+// Per frame, in turn, the host code of capi.hip computes what only it can: the voxel grid
 // (c3h_voxelize, which synchronises the host once per frame), the exact centroids, the leaf
 // layout and, at dim 137, the C3-HLAC-117 rows (extract_frames), whose columns go straight into
-// the frame's output rows.  What a frame leaves for the batch is small: its geometry on the
-// host, its centroids in leaf order and their voxel keys in batch slots.  Everything else --
-// search grids, normals, RSD, GRSD transitions, columns 0 .. 19 -- runs once per batch
-// (vosch_front.hip) over a device table of per-frame records.
+// the frame's output rows.  What a frame leaves for the front is small: its geometry on the
+// host (VfHostFrame), its centroids in leaf order and their voxel keys.  Everything else --
+// search grids, normals, RSD, GRSD transitions, columns 0 .. 19 -- runs once per batch over a
+// device table of per-frame records.  The single-frame entry points are a batch of one frame in
+// two steps: c3h_compute_normals fills the normals' half of the record and runs that stage,
+// c3h_extract_grsd / c3h_extract_vosch complete the record and run the rest.
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 
 #include "capi_host.h"
@@ -18,67 +23,288 @@ using c3h::fail;
 
 namespace {
 
-struct FrontFrame {
-  c3h::VfGrid g, g2;
-  int32_t sb[3];
-  int64_t H, nc, n;
-  float inv_s;
-  c3h_grid_info gi;
-  const float4* pts;
+enum { kStageNormals = 1, kStageGrsd = 2 };
+
+struct FrontParams {
+  float radius;    // the cell of every frame's g (the normals' radius)
+  float vp[3];     // kStageNormals: the viewpoint
+  float max_dist;  // kStageGrsd: the RSD radius,
+  float norm;      //   the factor of the rows
+  int dim;         //   and their stride
 };
 
-// One frame through the single-frame head.  Returns its status (0, or the error the
-// single-frame route -- c3h_voxelize, c3h_compute_normals, c3h_extract_vosch / _grsd -- gives);
-// on success the frame's centroids, voxel keys and C3 columns are enqueued.
-int front_head(c3h_ctx* ctx, const float* pts, int64_t n, int on_device, float leaf, float z_limit,
-               const c3h_vosch_params* p, int dim, int64_t row_cap, float max_dist, bool wide, int64_t p0, int64_t v0,
-               float* rows, FrontFrame* fr) {
-  int rc = c3h_voxelize(ctx, pts, n, on_device, leaf, z_limit, &fr->gi);
-  if (rc != C3H_OK) return rc;
+// RSD radius: max(rsd_radius_search, voxel_size / 2 * sqrt(3)) (grsd_colorCHLAC_tools.hpp:172)
+float rsd_max_dist(const c3h_grsd_params* gp, float leaf) {
+  return (float)std::max((double)gp->rsd_radius, (double)leaf / 2 * std::sqrt(3.0));
+}
+// A wide RSD radius (large leaves: leaf sqrt(3)/2 > 4 x the normal radius) gets a search grid of
+// its own radius; the normals are already computed, and the RSD's per-bin min/max angles do not
+// depend on the neighbour visiting order
+bool rsd_wide(float max_dist, float cell) { return max_dist > 4 * cell; }
+
+int nbr_grid(c3h_ctx* ctx, float cell, c3h::VfGrid* g) {
+  if (c3h::vf_nbr_grid(ctx->info.min_b, ctx->info.max_b, ctx->info.leaf, cell, g) != c3h::kVfOk)
+    return fail(ctx, C3H_ERR_RANGE, "normals: more than 2^27 search cells");
+  return C3H_OK;
+}
+
+int points_ready(c3h_ctx* ctx) {
   if (!ctx->have_grid || !ctx->table_valid)
     return fail(ctx, C3H_ERR_STATE, "compute_normals: needs the points of a c3h_voxelize");
-  if (c3h::vf_nbr_grid(fr->gi.min_b, fr->gi.max_b, ctx->info.leaf, p->normals_radius, &fr->g) != c3h::kVfOk)
-    return fail(ctx, C3H_ERR_RANGE, "normals: more than 2^27 search cells");
+  return C3H_OK;
+}
+
+// The normals' half of a frame (the rest of *fr is the caller's): the points of the last
+// c3h_voxelize and their search grid
+int frame_normals(c3h_ctx* ctx, float radius, c3h::VfHostFrame* fr) {
+  fr->gi = ctx->info;
+  fr->pts = ctx->vargs.pts;
+  fr->n = ctx->vargs.n;
+  fr->z_limit = ctx->vargs.z_limit;
+  const int rc = nbr_grid(ctx, radius, &fr->g);
   fr->g2 = fr->g;
-  fr->H = c3h::vf_subdivisions(fr->gi.div_b, p->grsd.subdiv, p->grsd.offset, fr->sb, &fr->inv_s);
-  if (fr->H > row_cap) return fail(ctx, C3H_ERR_RANGE, "vosch frames: a frame has more rows than row_cap");
-  rc = c3h::grsd_frame_head(ctx, &p->grsd, fr->sb, &fr->H, &fr->inv_s);
+  return rc;
+}
+
+// The GRSD half: the head of extractGRSDSignature21, the voxel keys of its centroids (ctx->dsamp)
+// into vkeys (nullptr, a single frame: its kernels run before the next head and read the leaf
+// layout itself), the RSD's own grid where the wide rule asks for one
+int frame_grsd(c3h_ctx* ctx, const c3h_grsd_params* gp, int32_t* vkeys, c3h::VfHostFrame* fr) {
+  int rc = c3h::grsd_frame_head(ctx, gp, fr->sb, &fr->H, &fr->inv_s);
   if (rc != C3H_OK) return rc;
-  if (fr->H > 0 && wide && c3h::vf_nbr_grid(fr->gi.min_b, fr->gi.max_b, ctx->info.leaf, max_dist, &fr->g2) != c3h::kVfOk)
-    return fail(ctx, C3H_ERR_RANGE, "normals: more than 2^27 search cells");
-  fr->n = n;
-  fr->nc = fr->H > 0 ? fr->gi.n_occ : 0;
-  fr->pts = reinterpret_cast<const float4*>(pts);
-  if (!on_device) {  // c3h_voxelize staged the host points in ctx->pts: the next frame overwrites them
-    HIPCHK(hipMemcpyAsync(ctx->vf_pts.p + p0, ctx->pts.p, (size_t)n * 16, hipMemcpyDeviceToDevice, ctx->stream));
-    fr->pts = ctx->vf_pts.p + p0;
-  }
-  if (fr->nc > 0) {
-    const int64_t nvox = (int64_t)fr->gi.div_b[0] * fr->gi.div_b[1] * fr->gi.div_b[2];
-    HIPCHK(hipMemcpyAsync(ctx->vf_cent.p + v0, ctx->dsamp.p, (size_t)fr->nc * 16, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(c3h::launch_vf_vox_keys(ctx->tmp_i32.p, nvox, fr->nc, ctx->vf_vkeys.p + v0, ctx->stream));
-  }
-  if (dim == 137) {  // the C3 part of extractVOSCH, as c3h_extract_vosch runs it
-    c3h_extract_params e{};
-    e.variant = 117;
-    for (int a = 0; a < 3; ++a) {
-      e.thr[a] = p->thr[a];
-      e.offset[a] = p->grsd.offset[a];
-    }
-    e.subdiv = p->grsd.subdiv;
-    e.color_mode = p->color_mode;
-    const uint32_t* g = ctx->grid_ptr;
-    int32_t sb2[3];
-    int64_t H2 = 0;
-    rc = c3h::extract_frames(ctx, &g, 1, &e, sb2, &H2);
+  fr->nc = fr->H > 0 ? ctx->info.n_occ : 0;
+  for (int a = 0; a < 3; ++a) fr->off[a] = gp->subdiv > 0 ? gp->offset[a] : 0;
+  fr->cent = ctx->dsamp.p;
+  fr->vkeys = vkeys;
+  fr->g2 = fr->g;
+  const float max_dist = rsd_max_dist(gp, ctx->info.leaf);
+  if (fr->H > 0 && rsd_wide(max_dist, fr->g.cell)) {
+    rc = nbr_grid(ctx, max_dist, &fr->g2);
     if (rc != C3H_OK) return rc;
-    if (H2 != fr->H) return fail(ctx, C3H_ERR_STATE, "extract_vosch: GRSD / C3 subdivisions differ");
-    HIPCHK(c3h::launch_vf_c3_cols(ctx->feat.p, ctx->exist.p, fr->H, rows, ctx->stream));
+  }
+  fr->layout = vkeys ? nullptr : ctx->tmp_i32.p;
+  if (fr->nc > 0 && vkeys) {
+    const int64_t nvox = (int64_t)fr->gi.div_b[0] * fr->gi.div_b[1] * fr->gi.div_b[2];
+    HIPCHK(c3h::launch_vf_vox_keys(ctx->tmp_i32.p, nvox, fr->nc, vkeys, ctx->stream));
   }
   return C3H_OK;
 }
 
-// The front end of both entry points: frame i's rows at d_rows + i * row_cap * dim, info[i]
+// The table's last upload has read the host copy, which may change again; the kernels behind
+// that upload stay in flight (they read the device copy, in stream order)
+int table_wait(c3h_ctx* ctx) {
+  if (ctx->vf_up_ev) HIPCHK(hipEventSynchronize(ctx->vf_up_ev));
+  return C3H_OK;
+}
+
+// The host table for a call of nf frames
+int front_begin(c3h_ctx* ctx, int nf, c3h::VfTable** ht) {
+  const int rc = table_wait(ctx);
+  if (rc != C3H_OK) return rc;
+  if (!ctx->vf_htab) HIPCHK(hipHostMalloc(&ctx->vf_htab, sizeof(c3h::VfTable)));
+  *ht = ctx->vf_htab;
+  memset(*ht, 0, offsetof(c3h::VfTable, fr) + (size_t)nf * sizeof(c3h::VfFrame));
+  (*ht)->nf = nf;
+  return C3H_OK;
+}
+
+// frame j's share of the concatenations (a failed frame: VfHostFrame{}, nothing)
+void push_prefixes(c3h::VfTable* ht, int j, const c3h::VfHostFrame& fr) {
+  ht->ppre[j + 1] = ht->ppre[j] + fr.n;
+  ht->cpre[j + 1] = ht->cpre[j] + fr.g.ncell;
+  ht->c2pre[j + 1] = ht->c2pre[j] + fr.g2.ncell;
+  ht->vpre[j + 1] = ht->vpre[j] + fr.nc;
+  ht->hpre[j + 1] = ht->hpre[j] + fr.H;
+}
+
+// frame j's record of the table, from its prefixes and the front's buffers (both final)
+void fill_record(c3h_ctx* ctx, c3h::VfTable* ht, int j, const c3h::VfHostFrame& fr) {
+  c3h::VfFrame& t = ht->fr[j];
+  for (int which = 0; which < 2; ++which) {
+    const c3h::VfGrid& vg = which ? fr.g2 : fr.g;
+    c3h::NbrGrid& g = which ? t.g2 : t.g;
+    g.pts = fr.pts;
+    g.n = fr.n;
+    g.z_limit = fr.z_limit;
+    g.cell = vg.cell;
+    g.inv_cell = vg.inv_cell;
+    for (int a = 0; a < 3; ++a) {
+      g.origin[a] = vg.origin[a];
+      g.dim[a] = vg.dim[a];
+    }
+    g.sorted = ctx->vf_idx2.p + ht->ppre[j];
+    g.cstart = ctx->vf_cstart.p + (which ? ht->c2pre[j] : ht->cpre[j]);
+    g.cend = ctx->vf_cend.p + (which ? ht->c2pre[j] : ht->cpre[j]);
+  }
+  c3h::GrsdArgs& ga = t.ga;
+  ga.cent = fr.cent;
+  ga.nc = fr.nc;
+  ga.types = ctx->vf_types.p + ht->vpre[j];
+  ga.trans = ctx->vf_trans.p + ht->hpre[j] * 36;
+  for (int a = 0; a < 3; ++a) {
+    ga.div_b[a] = fr.gi.div_b[a];
+    ga.min_b[a] = fr.gi.min_b[a];
+    ga.off[a] = fr.off[a];
+    ga.sb[a] = fr.sb[a];
+  }
+  ga.leaf = fr.gi.leaf;
+  ga.inv_leaf = 1.0f / fr.gi.leaf;
+  ga.inv_s = fr.inv_s;
+  ga.hist1 = fr.H == 1 ? 1 : 0;
+  t.vkeys = fr.vkeys;
+  t.layout = fr.layout;
+  t.rows = fr.rows;
+}
+
+// The front over the nb frames of the host table, whose prefixes are pushed: the buffers of the
+// stages, the records, the upload, the launches.  A batch runs both stages at once.  A single
+// frame runs them in two calls; nothing the second reserves holds a result of the first.
+int front_run(c3h_ctx* ctx, c3h::VfTable* ht, const c3h::VfHostFrame* ff, int nb, int stages, const FrontParams& q) {
+  const int64_t ptot = ht->ppre[nb], ctot = ht->cpre[nb], c2tot = ht->c2pre[nb], vtot = ht->vpre[nb], htot = ht->hpre[nb];
+  if (ptot == 0) return C3H_OK;
+  const bool wide = (stages & kStageGrsd) && vtot > 0 && rsd_wide(q.max_dist, q.radius);
+  int64_t max_cells = 1;
+  for (int j = 0; j < nb; ++j) max_cells = std::max(max_cells, std::max(ff[j].g.ncell, ff[j].g2.ncell));
+  c3h::VfKey key{};
+  if (c3h::vf_key(max_cells, nb, ptot, &key) != c3h::kVfOk)
+    return fail(ctx, C3H_ERR_RANGE, "vosch frames: the batch does not fit the composite sort key");
+  ENSURE(ctx->vf_tab, 1);
+  size_t tb = 0;
+  if ((stages & kStageNormals) || wide) {  // a search grid is built
+    const size_t kw = key.wide ? 1 : 2;  // keys per 64-bit word
+    ENSURE(ctx->vf_keys, ((size_t)ptot + kw - 1) / kw);
+    ENSURE(ctx->vf_keys2, ((size_t)ptot + kw - 1) / kw);
+    ENSURE(ctx->vf_idx, ptot);
+    ENSURE(ctx->vf_idx2, ptot);
+    ENSURE(ctx->vf_cstart, std::max(ctot, c2tot));
+    ENSURE(ctx->vf_cend, std::max(ctot, c2tot));
+    HIPCHK(c3h::vf_nbr_build(ctx->vf_tab.p, 0, key, ptot, ctot, ctx->vf_keys.p, ctx->vf_keys2.p, ctx->vf_idx.p,
+                             ctx->vf_idx2.p, ctx->vf_cstart.p, ctx->vf_cend.p, nullptr, &tb, ctx->stream));
+    ENSURE(ctx->vf_tmp, std::max<size_t>(tb, 1));
+    tb = ctx->vf_tmp.n;
+  }
+  if (stages & kStageNormals) {
+    ENSURE(ctx->vf_normals, ptot);
+    ENSURE(ctx->vf_dense, c3h::vf_dense_cap(ptot) + 1);
+  }
+  if (stages & kStageGrsd) {
+    ENSURE(ctx->vf_types, vtot);
+    ENSURE(ctx->vf_radii, vtot);
+    ENSURE(ctx->vf_trans, htot * 36);
+  }
+  for (int j = 0; j < nb; ++j) fill_record(ctx, ht, j, ff[j]);
+  HIPCHK(hipMemcpyAsync(ctx->vf_tab.p, ht, offsetof(c3h::VfTable, fr) + (size_t)nb * sizeof(c3h::VfFrame),
+                        hipMemcpyHostToDevice, ctx->stream));
+  if (!ctx->vf_up_ev) HIPCHK(hipEventCreateWithFlags(&ctx->vf_up_ev, hipEventDisableTiming));
+  HIPCHK(hipEventRecord(ctx->vf_up_ev, ctx->stream));
+  if (stages & kStageNormals) {
+    HIPCHK(c3h::vf_nbr_build(ctx->vf_tab.p, 0, key, ptot, ctot, ctx->vf_keys.p, ctx->vf_keys2.p, ctx->vf_idx.p,
+                             ctx->vf_idx2.p, ctx->vf_cstart.p, ctx->vf_cend.p, ctx->vf_tmp.p, &tb, ctx->stream));
+    const int reach = c3h::vf_reach(q.radius, 1.0f / q.radius);
+    if (reach > c3h::kVfMaxReach) return fail(ctx, C3H_ERR_STATE, "vosch frames: internal: normals reach");
+    HIPCHK(c3h::launch_vf_normals(ctx->vf_tab.p, nb, key, ptot, ctot, ctx->vf_keys2.p, ctx->vf_dense.p, q.radius, reach, q.vp,
+                                  ctx->vf_normals.p, ctx->stream));
+  }
+  if (!(stages & kStageGrsd)) return C3H_OK;
+  if (vtot > 0) {
+    const float rsd_cell = wide ? q.max_dist : q.radius;
+    if (wide)  // (the normals are done with the first grid: its buffers take the second)
+      HIPCHK(c3h::vf_nbr_build(ctx->vf_tab.p, 1, key, ptot, c2tot, ctx->vf_keys.p, ctx->vf_keys2.p, ctx->vf_idx.p,
+                               ctx->vf_idx2.p, ctx->vf_cstart.p, ctx->vf_cend.p, ctx->vf_tmp.p, &tb, ctx->stream));
+    HIPCHK(c3h::launch_vf_rsd(ctx->vf_tab.p, vtot, ctx->vf_normals.p, q.max_dist, c3h::vf_reach(q.max_dist, 1.0f / rsd_cell),
+                              ctx->vf_radii.p, ctx->vf_types.p, ctx->stream));
+  }
+  if (htot > 0) {
+    HIPCHK(hipMemsetAsync(ctx->vf_trans.p, 0, (size_t)htot * 36 * 4, ctx->stream));
+    HIPCHK(c3h::launch_vf_grsd(ctx->vf_tab.p, vtot, ctx->stream));
+    HIPCHK(c3h::launch_vf_rows(ctx->vf_tab.p, htot, ctx->vf_trans.p, q.norm, q.dim, ctx->stream));
+  }
+  return C3H_OK;
+}
+
+// NORMALIZE_GRSD = 20 / 26 (grsd_colorCHLAC_tools.h:32) when is_normalize
+float grsd_norm(const c3h_grsd_params* gp) { return gp->normalize ? (float)(20.0 / 26) : 1.0f; }
+
+// The C3 part of extractVOSCH (grsd_colorCHLAC_tools.hpp:832-843) on the grid of the last
+// c3h_voxelize: its C3-HLAC-117 rows (ctx->feat, ctx->exist) into columns 20 .. 136 of rows
+int c3_cols(c3h_ctx* ctx, const c3h_grsd_params* gp, const int32_t thr[3], int32_t color_mode, int64_t H, float* rows) {
+  c3h_extract_params e{};
+  e.variant = 117;
+  for (int a = 0; a < 3; ++a) {
+    e.thr[a] = thr[a];
+    e.offset[a] = gp->offset[a];
+  }
+  e.subdiv = gp->subdiv;
+  e.color_mode = color_mode;
+  const uint32_t* g = ctx->grid_ptr;
+  int32_t sb2[3];
+  int64_t H2 = 0;
+  const int rc = c3h::extract_frames(ctx, &g, 1, &e, sb2, &H2);
+  if (rc != C3H_OK) return rc;
+  if (H2 != H) return fail(ctx, C3H_ERR_STATE, "extract_vosch: GRSD / C3 subdivisions differ");
+  HIPCHK(c3h::launch_vf_c3_cols(ctx->feat.p, ctx->exist.p, H, rows, ctx->stream));
+  return C3H_OK;
+}
+
+// extractGRSDSignature21 (grsd_colorCHLAC_tools.hpp:131-296) of the frame c3h_compute_normals
+// left in ctx->vf_one: columns 0 .. 19 of H rows of dim floats in `dest`
+int grsd_frames(c3h_ctx* ctx, const c3h_grsd_params* gp, int dim, c3h::DevBuf<float>& dest, int32_t sb[3], int64_t* Hout) {
+  if (!ctx->normals_valid) return fail(ctx, C3H_ERR_STATE, "extract_grsd: c3h_compute_normals first");
+  c3h::VfHostFrame& fr = ctx->vf_one;
+  *Hout = 0;
+  ctx->vf_nframes = 0;
+  int rc = table_wait(ctx);
+  if (rc != C3H_OK) return rc;
+  rc = frame_grsd(ctx, gp, nullptr, &fr);
+  memcpy(sb, fr.sb, sizeof(fr.sb));
+  if (rc != C3H_OK) return rc;
+  ENSURE(dest, (size_t)std::max<int64_t>(fr.H, 1) * dim);
+  if (fr.H == 0) return C3H_OK;
+  fr.rows = dest.p;
+  c3h::VfTable* const ht = ctx->vf_htab;
+  push_prefixes(ht, 0, fr);
+  FrontParams q{};
+  q.radius = fr.g.cell;
+  q.max_dist = rsd_max_dist(gp, ctx->info.leaf);
+  q.norm = grsd_norm(gp);
+  q.dim = dim;
+  rc = front_run(ctx, ht, &fr, 1, kStageGrsd, q);
+  if (rc != C3H_OK) return rc;
+  ctx->rsd_n = fr.nc;
+  fr.g = fr.g2;  // the cell tables hold the RSD's grid from now on
+  *Hout = fr.H;
+  return C3H_OK;
+}
+
+// One frame of a batch through the single-frame head.  Returns its status (0, or the error the
+// single-frame route -- c3h_voxelize, c3h_compute_normals, c3h_extract_vosch / _grsd -- gives);
+// on success the frame's centroids, voxel keys and C3 columns are enqueued.
+int front_head(c3h_ctx* ctx, const float* pts, int64_t n, int on_device, float leaf, float z_limit,
+               const c3h_vosch_params* p, int dim, int64_t row_cap, int64_t p0, int64_t v0, float* rows,
+               c3h::VfHostFrame* fr) {
+  int rc = c3h_voxelize(ctx, pts, n, on_device, leaf, z_limit, nullptr);
+  if (rc == C3H_OK) rc = points_ready(ctx);
+  if (rc == C3H_OK) rc = frame_normals(ctx, p->normals_radius, fr);
+  if (rc != C3H_OK) return rc;
+  fr->rows = rows;
+  float inv_s;
+  if (c3h::vf_subdivisions(fr->gi.div_b, p->grsd.subdiv, p->grsd.offset, fr->sb, &inv_s) > row_cap)
+    return fail(ctx, C3H_ERR_RANGE, "vosch frames: a frame has more rows than row_cap");
+  rc = frame_grsd(ctx, &p->grsd, ctx->vf_vkeys.p + v0, fr);
+  if (rc != C3H_OK) return rc;
+  if (!on_device) {  // fr->pts is ctx->pts, where c3h_voxelize staged the host points: the next frame overwrites them
+    HIPCHK(hipMemcpyAsync(ctx->vf_pts.p + p0, ctx->pts.p, (size_t)n * 16, hipMemcpyDeviceToDevice, ctx->stream));
+    fr->pts = ctx->vf_pts.p + p0;
+  }
+  if (fr->nc > 0) {  // and ctx->dsamp
+    HIPCHK(hipMemcpyAsync(ctx->vf_cent.p + v0, ctx->dsamp.p, (size_t)fr->nc * 16, hipMemcpyDeviceToDevice, ctx->stream));
+    fr->cent = ctx->vf_cent.p + v0;
+  }
+  if (dim == 137) return c3_cols(ctx, &p->grsd, p->thr, p->color_mode, fr->H, fr->rows);
+  return C3H_OK;
+}
+
+// The front end of both batch entry points: frame i's rows at d_rows + i * row_cap * dim, info[i]
 // filled (info != nullptr).  Returns C3H_OK or the error that stopped the call.
 int vosch_front(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t nframes, int on_device, float leaf,
                 float z_limit, const c3h_vosch_params* p, int32_t dim, int64_t row_cap, float* d_rows,
@@ -90,39 +316,37 @@ int vosch_front(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t
   ctx->vf_status.assign((size_t)nframes, 0);
   ctx->vf_ppre.assign((size_t)nframes + 1, 0);
   ctx->vf_vpre.assign((size_t)nframes + 1, 0);
-  // RSD radius: max(rsd_radius_search, voxel_size / 2 * sqrt(3)) (grsd_colorCHLAC_tools.hpp:172); beyond
-  // 4 x the normals' cell the RSD gets a grid of its own radius (grsd_frames)
-  const float max_dist = (float)std::max((double)p->grsd.rsd_radius, (double)leaf / 2 * std::sqrt(3.0));
-  const bool wide = max_dist > 4 * p->normals_radius;
-  const float vp0[3] = {p->viewpoint[0], p->viewpoint[1], p->viewpoint[2]};
-  ctx->vf_htab.resize(1);  // lives with the context: its upload is asynchronous
-  c3h::VfTable* const ht = ctx->vf_htab.data();
-  std::vector<FrontFrame> ff((size_t)B);
+  FrontParams q{};
+  q.radius = p->normals_radius;
+  for (int a = 0; a < 3; ++a) q.vp[a] = p->viewpoint[a];
+  q.max_dist = rsd_max_dist(&p->grsd, leaf);
+  q.norm = grsd_norm(&p->grsd);
+  q.dim = dim;
+  std::vector<c3h::VfHostFrame> ff((size_t)B);
   for (int b0 = 0; b0 < nframes; b0 += B) {
     const int nb = std::min(B, nframes - b0);
     int64_t upper = 0;
     for (int j = 0; j < nb; ++j) upper += std::max<int64_t>(n[b0 + j], 0);
     if (upper > c3h::kVfMaxPoints) return fail(ctx, C3H_ERR_RANGE, "vosch frames: a batch holds 2^32 points or more");
-    // the previous batch's table upload and launches read *ht and the buffers that may grow now
+    // the previous batch's launches read the buffers that may grow now
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    c3h::VfTable* ht = nullptr;
+    int rc = front_begin(ctx, nb, &ht);
+    if (rc != C3H_OK) return rc;
     if (!on_device) ENSURE(ctx->vf_pts, upper);
     ENSURE(ctx->vf_cent, upper);
     ENSURE(ctx->vf_vkeys, upper);
-    memset(ht, 0, sizeof(c3h::VfTable));
-    ht->nf = nb;
-    int64_t max_cells = 1;
     for (int j = 0; j < nb; ++j) {
       const int i = b0 + j;
-      FrontFrame& fr = ff[(size_t)j];
-      fr = FrontFrame{};
+      c3h::VfHostFrame& fr = ff[(size_t)j];
+      fr = c3h::VfHostFrame{};
       c3h_frame_info& fi = info[i];
       memset(&fi, 0, sizeof(fi));
-      float* rows = d_rows + (size_t)i * row_cap * dim;
-      const int st = front_head(ctx, pts[i], n[i], on_device, leaf, z_limit, p, dim, row_cap, max_dist, wide, ht->ppre[j],
-                                ht->vpre[j], rows, &fr);
+      const int st = front_head(ctx, pts[i], n[i], on_device, leaf, z_limit, p, dim, row_cap, ht->ppre[j], ht->vpre[j],
+                                d_rows + (size_t)i * row_cap * dim, &fr);
       fi.status = st;
       ctx->vf_status[(size_t)i] = st;
-      if (st < 0) fr = FrontFrame{};  // no points, cells, centroids or rows in the batch
+      if (st < 0) fr = c3h::VfHostFrame{};  // no points, cells, centroids or rows in the batch
       else {
         for (int a = 0; a < 3; ++a) {
           fi.div_b[a] = fr.gi.div_b[a];
@@ -132,101 +356,15 @@ int vosch_front(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t
         fi.n_valid = fr.gi.n_valid;
         fi.n_occ = fr.gi.n_occ;
         fi.n_moved = fr.H > 0 ? (int32_t)ctx->n_offcell : 0;
-        max_cells = std::max(max_cells, std::max(fr.g.ncell, fr.g2.ncell));
       }
-      ht->ppre[j + 1] = ht->ppre[j] + fr.n;
-      ht->cpre[j + 1] = ht->cpre[j] + (st < 0 ? 0 : fr.g.ncell);
-      ht->c2pre[j + 1] = ht->c2pre[j] + (st < 0 ? 0 : fr.g2.ncell);
-      ht->vpre[j + 1] = ht->vpre[j] + fr.nc;
-      ht->hpre[j + 1] = ht->hpre[j] + fr.H;
+      push_prefixes(ht, j, fr);
       if (nframes <= B) {
         ctx->vf_ppre[(size_t)i + 1] = ht->ppre[j + 1];
         ctx->vf_vpre[(size_t)i + 1] = ht->vpre[j + 1];
       }
     }
-    const int64_t ptot = ht->ppre[nb], ctot = ht->cpre[nb], c2tot = ht->c2pre[nb], vtot = ht->vpre[nb], htot = ht->hpre[nb];
-    if (ptot == 0) continue;
-    c3h::VfKey key{};
-    if (c3h::vf_key(max_cells, nb, ptot, &key) != c3h::kVfOk)
-      return fail(ctx, C3H_ERR_RANGE, "vosch frames: the batch does not fit the composite sort key");
-    const size_t kw = key.wide ? 1 : 2;  // keys per 64-bit word
-    ENSURE(ctx->vf_keys, ((size_t)ptot + kw - 1) / kw);
-    ENSURE(ctx->vf_keys2, ((size_t)ptot + kw - 1) / kw);
-    ENSURE(ctx->vf_idx, ptot);
-    ENSURE(ctx->vf_idx2, ptot);
-    ENSURE(ctx->vf_cstart, std::max(ctot, c2tot));
-    ENSURE(ctx->vf_cend, std::max(ctot, c2tot));
-    ENSURE(ctx->vf_normals, ptot);
-    ENSURE(ctx->vf_types, vtot);
-    ENSURE(ctx->vf_radii, vtot);
-    ENSURE(ctx->vf_trans, htot * 36);
-    ENSURE(ctx->vf_tab, 1);
-    ENSURE(ctx->vf_dense, c3h::vf_dense_cap(ptot) + 1);
-    for (int j = 0; j < nb; ++j) {
-      const FrontFrame& fr = ff[(size_t)j];
-      c3h::VfFrame& t = ht->fr[j];
-      for (int which = 0; which < 2; ++which) {
-        const c3h::VfGrid& vg = which ? fr.g2 : fr.g;
-        c3h::NbrGrid& g = which ? t.g2 : t.g;
-        g.pts = fr.pts;
-        g.n = fr.n;
-        g.z_limit = z_limit;
-        g.cell = vg.cell;
-        g.inv_cell = vg.inv_cell;
-        for (int a = 0; a < 3; ++a) {
-          g.origin[a] = vg.origin[a];
-          g.dim[a] = vg.dim[a];
-        }
-        g.sorted = ctx->vf_idx2.p + ht->ppre[j];
-        g.cstart = ctx->vf_cstart.p + (which ? ht->c2pre[j] : ht->cpre[j]);
-        g.cend = ctx->vf_cend.p + (which ? ht->c2pre[j] : ht->cpre[j]);
-      }
-      c3h::GrsdArgs& ga = t.ga;
-      ga.cent = ctx->vf_cent.p + ht->vpre[j];
-      ga.nc = fr.nc;
-      ga.layout = nullptr;
-      ga.types = ctx->vf_types.p + ht->vpre[j];
-      ga.trans = ctx->vf_trans.p + ht->hpre[j] * 36;
-      for (int a = 0; a < 3; ++a) {
-        ga.div_b[a] = fr.gi.div_b[a];
-        ga.min_b[a] = fr.gi.min_b[a];
-        ga.off[a] = p->grsd.subdiv > 0 ? p->grsd.offset[a] : 0;
-        ga.sb[a] = fr.sb[a];
-      }
-      ga.leaf = fr.gi.leaf;
-      ga.inv_leaf = 1.0f / fr.gi.leaf;
-      ga.inv_s = fr.inv_s;
-      ga.hist1 = fr.H == 1 ? 1 : 0;
-      t.vkeys = ctx->vf_vkeys.p + ht->vpre[j];
-      t.rows = d_rows + (size_t)(b0 + j) * row_cap * dim;
-    }
-    HIPCHK(hipMemcpyAsync(ctx->vf_tab.p, ht, sizeof(c3h::VfTable), hipMemcpyHostToDevice, ctx->stream));
-    size_t tb = 0;
-    HIPCHK(c3h::vf_nbr_build(ctx->vf_tab.p, 0, key, ptot, ctot, ctx->vf_keys.p, ctx->vf_keys2.p, ctx->vf_idx.p,
-                             ctx->vf_idx2.p, ctx->vf_cstart.p, ctx->vf_cend.p, nullptr, &tb, ctx->stream));
-    ENSURE(ctx->vf_tmp, std::max<size_t>(tb, 1));
-    tb = ctx->vf_tmp.n;
-    HIPCHK(c3h::vf_nbr_build(ctx->vf_tab.p, 0, key, ptot, ctot, ctx->vf_keys.p, ctx->vf_keys2.p, ctx->vf_idx.p,
-                             ctx->vf_idx2.p, ctx->vf_cstart.p, ctx->vf_cend.p, ctx->vf_tmp.p, &tb, ctx->stream));
-    const int reach = c3h::vf_reach(p->normals_radius, 1.0f / p->normals_radius);
-    if (reach > c3h::kVfMaxReach) return fail(ctx, C3H_ERR_STATE, "vosch frames: internal: normals reach");
-    HIPCHK(c3h::launch_vf_normals(ctx->vf_tab.p, key, ptot, ctot, ctx->vf_keys2.p, ctx->vf_dense.p, p->normals_radius, reach, vp0,
-                                  ctx->vf_normals.p, ctx->stream));
-    if (vtot > 0) {
-      const float rsd_cell = wide ? max_dist : p->normals_radius;
-      if (wide)  // (the normals are done with the first grid: its buffers take the second)
-        HIPCHK(c3h::vf_nbr_build(ctx->vf_tab.p, 1, key, ptot, c2tot, ctx->vf_keys.p, ctx->vf_keys2.p, ctx->vf_idx.p,
-                                 ctx->vf_idx2.p, ctx->vf_cstart.p, ctx->vf_cend.p, ctx->vf_tmp.p, &tb, ctx->stream));
-      HIPCHK(c3h::launch_vf_rsd(ctx->vf_tab.p, vtot, ctx->vf_normals.p, max_dist, c3h::vf_reach(max_dist, 1.0f / rsd_cell),
-                                ctx->vf_radii.p, ctx->vf_types.p, ctx->stream));
-    }
-    if (htot > 0) {
-      HIPCHK(hipMemsetAsync(ctx->vf_trans.p, 0, (size_t)htot * 36 * 4, ctx->stream));
-      HIPCHK(c3h::launch_vf_grsd(ctx->vf_tab.p, vtot, ctx->stream));
-      // NORMALIZE_GRSD = 20 / 26 (grsd_colorCHLAC_tools.h:32) when is_normalize
-      HIPCHK(c3h::launch_vf_rows(ctx->vf_tab.p, htot, ctx->vf_trans.p, p->grsd.normalize ? (float)(20.0 / 26) : 1.0f, dim,
-                                 ctx->stream));
-    }
+    rc = front_run(ctx, ht, ff.data(), nb, kStageNormals | kStageGrsd, q);
+    if (rc != C3H_OK) return rc;
   }
   ctx->vf_nframes = nframes <= B ? nframes : -1;
   return C3H_OK;
@@ -251,6 +389,109 @@ int frame_check(c3h_ctx* ctx, const char* who, int32_t frame) {
 }  // namespace
 
 extern "C" {
+
+// ---- one frame: the points of the last c3h_voxelize -----------------------------------------
+int c3h_compute_normals(c3h_ctx* ctx, float radius, const float viewpoint[3]) {
+  if (!ctx || !(radius > 0)) return C3H_ERR_ARG;
+  QUIESCE(ctx);
+  int rc = points_ready(ctx);
+  if (rc != C3H_OK) return rc;
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->normals_valid = false;
+  c3h::VfHostFrame& fr = ctx->vf_one;
+  fr = c3h::VfHostFrame{};
+  rc = frame_normals(ctx, radius, &fr);
+  if (rc != C3H_OK) return rc;
+  ctx->vf_nframes = 0;  // the frame takes the buffers of the last batch
+  c3h::VfTable* ht = nullptr;
+  rc = front_begin(ctx, 1, &ht);
+  if (rc != C3H_OK) return rc;
+  push_prefixes(ht, 0, fr);
+  FrontParams q{};
+  q.radius = radius;
+  for (int a = 0; a < 3; ++a) q.vp[a] = viewpoint ? viewpoint[a] : 0.0f;
+  rc = front_run(ctx, ht, &fr, 1, kStageNormals, q);
+  if (rc != C3H_OK) return rc;
+  ctx->normals_valid = true;
+  return C3H_OK;
+}
+
+int c3h_get_normals(c3h_ctx* ctx, float* out, int on_device) {
+  if (!ctx || !out) return C3H_ERR_ARG;
+  QUIESCE(ctx);
+  if (!ctx->normals_valid) return fail(ctx, C3H_ERR_STATE, "get_normals: c3h_compute_normals first");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipMemcpyAsync(out, ctx->vf_normals.p, (size_t)ctx->vargs.n * 16,
+                        on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return C3H_OK;
+}
+
+int c3h_extract_grsd(c3h_ctx* ctx, const c3h_grsd_params* p, int32_t subdiv_out[3], int64_t* hist_num) {
+  if (!ctx || !p) return C3H_ERR_ARG;
+  QUIESCE(ctx);
+  if (!ctx->have_grid || !ctx->table_valid) return fail(ctx, C3H_ERR_STATE, "extract_grsd: no c3h_voxelize grid");
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->have_feat = false;
+  ctx->feat_listed = false;
+  ctx->g_valid = false;
+  ctx->rows_valid = false;
+  ctx->exist_gates_rows = false;
+  int32_t sb[3];
+  int64_t H = 0;
+  int rc = grsd_frames(ctx, p, 20, ctx->feat, sb, &H);
+  if (rc != C3H_OK) return rc;
+  ctx->feat16_pending = false;
+  ENSURE(ctx->exist, (size_t)std::max<int64_t>(H, 1));
+  if (H > 0) HIPCHK(c3h::launch_exist_rule(ctx->feat.p, H, 20, C3H_EXIST_GRSD, ctx->exist.p, ctx->stream));
+  ctx->hist_num = H;
+  ctx->feat_dim = 20;
+  for (int a = 0; a < 3; ++a) ctx->subdiv_b[a] = sb[a];
+  ctx->nframes_feat = 1;
+  ctx->feat_sparse = false;
+  ctx->have_feat = true;
+  if (subdiv_out) memcpy(subdiv_out, sb, sizeof(sb));
+  if (hist_num) *hist_num = H;
+  return C3H_OK;
+}
+
+int c3h_get_rsd(c3h_ctx* ctx, float* radii, int32_t* types, int on_device) {
+  if (!ctx) return C3H_ERR_ARG;
+  QUIESCE(ctx);
+  if (ctx->rsd_n == 0 && !ctx->normals_valid) return fail(ctx, C3H_ERR_STATE, "get_rsd: no RSD computed");
+  HIPCHK(hipSetDevice(ctx->device));
+  const hipMemcpyKind k = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (radii && ctx->rsd_n) HIPCHK(hipMemcpyAsync(radii, ctx->vf_radii.p, (size_t)ctx->rsd_n * 8, k, ctx->stream));
+  if (types && ctx->rsd_n) HIPCHK(hipMemcpyAsync(types, ctx->vf_types.p, (size_t)ctx->rsd_n * 4, k, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return (int)std::min<int64_t>(ctx->rsd_n, INT32_MAX);
+}
+
+// extractVOSCH (grsd_colorCHLAC_tools.hpp:832-843): [GRSD-20 | C3-HLAC-117] per subdivision
+int c3h_extract_vosch(c3h_ctx* ctx, const c3h_grsd_params* p, const int32_t thr[3], int32_t color_mode,
+                      int32_t subdiv_out[3], int64_t* hist_num) {
+  if (!ctx || !p || !thr) return C3H_ERR_ARG;
+  QUIESCE(ctx);
+  if (!ctx->have_grid || !ctx->table_valid) return fail(ctx, C3H_ERR_STATE, "extract_vosch: no c3h_voxelize grid");
+  HIPCHK(hipSetDevice(ctx->device));
+  int32_t sb[3];
+  int64_t H = 0;
+  int rc = grsd_frames(ctx, p, 137, ctx->vf_rows, sb, &H);
+  if (rc != C3H_OK) return rc;
+  rc = c3_cols(ctx, p, thr, color_mode, H, ctx->vf_rows.p);
+  if (rc != C3H_OK) return rc;
+  std::swap(ctx->feat, ctx->vf_rows);  // (extract_frames left the 117-wide rows in feat)
+  ctx->feat_dim = 137;
+  ctx->feat_sparse = false;
+  ctx->g_valid = false;
+  ctx->rows_valid = false;
+  ctx->exist_gates_rows = false;
+  if (subdiv_out) memcpy(subdiv_out, sb, sizeof(sb));
+  if (hist_num) *hist_num = H;
+  return C3H_OK;
+}
+
+// ---- a batch of frames ------------------------------------------------------------------------
 
 int c3h_extract_vosch_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t nframes, int on_device,
                              float leaf, float z_limit, const c3h_vosch_params* p, int32_t dim, int64_t row_cap,

@@ -1,13 +1,11 @@
 // rsd_dev.h -- the arithmetic of the normals, the RSD radii and the GRSD transitions as device
-// functions: the single-frame kernels (rsd.hip) and the batched ones (vosch_front.hip) call the
-// same bodies, so a frame's results do not depend on the route it takes.  The library is built
+// functions the kernels of the front (vosch_front.hip, where the algorithm is described) call,
+// whichever of them serves a point or a voxel.  The library is built
 // with -ffp-contract=off: every product and sum below rounds where it is written.
 #pragma once
 #include "c3h_internal.h"
 
 namespace c3h {
-
-constexpr uint32_t kNoCell = 0xffffffffu;
 
 // the points c3h_voxelize kept (voxelize.hip point_valid: finite, z < z_limit)
 __device__ __forceinline__ bool pt_kept(const NbrGrid& g, const float4& p) {

@@ -1,4 +1,4 @@
-// vosch_frames.h -- host arithmetic of the batched VOSCH / GRSD front (c3h_extract_vosch_frames):
+// vosch_frames.h -- host arithmetic of the normals / RSD / GRSD front (one frame or a batch):
 // the prefixes that concatenate the frames' points, search cells, centroids and rows, the frame
 // of a concatenated index, each frame's radius-search grid and the composite (frame | cell)
 // sort key with its capacity checks.  Plain C++: the kernels (vosch_front.hip), the launch code
@@ -44,7 +44,7 @@ C3H_VF_HD inline int vf_frame_of(const int64_t* pre, int nf, int64_t i) {
 
 // ---- a frame's radius-search grid ------------------------------------------------------------
 // Cells of `cell` metres over the frame's voxel box [min_b, max_b] * leaf with one cell of margin
-// below and two above: the arithmetic of the single-frame nbr_grid() (capi.hip), to the bit.
+// below and two above.  The only copy of this arithmetic: every search grid comes from here.
 struct VfGrid {
   float origin[3];
   float cell, inv_cell;
@@ -62,7 +62,7 @@ inline int vf_nbr_grid(const int32_t min_b[3], const int32_t max_b[3], float lea
   g->ncell = (int64_t)g->dim[0] * g->dim[1] * g->dim[2];
   return g->ncell > kVfMaxCells ? kVfErrCells : kVfOk;
 }
-// cells a query visits per axis side: ceil(radius / cell), at least 1 (launch_normals / launch_rsd)
+// cells a query visits per axis side: ceil(radius / cell), at least 1
 inline int vf_reach(float radius, float inv_cell) {
   const int r = (int)std::ceil(radius * inv_cell);
   return r > 1 ? r : 1;
@@ -70,9 +70,9 @@ inline int vf_reach(float radius, float inv_cell) {
 
 // ---- the composite sort key --------------------------------------------------------------------
 // key = frame << cell_bits | cell, sorted on its low cell_bits + frame_bits bits by one stable
-// radix sort: per frame the order is the single-frame sort's, cell order then input order.  The
+// radix sort: per frame the order is cell order, then input order.  The
 // all-ones cell value marks a point that is in no cell (dropped by the voxeliser), so it sorts
-// behind the frame's cells as the single-frame kNoCell does; cell_bits therefore holds the value
+// behind the frame's cells; cell_bits therefore holds the value
 // max_cells itself.  Keys are 32-bit words when they fit, else 64-bit.
 struct VfKey {
   int cell_bits, frame_bits, bits;

@@ -1,27 +1,47 @@
-// vosch_front.hip -- the batched GRSD side of c3h_extract_vosch_frames: the search grids, the
-// normals, the RSD radii, the GRSD transitions and the feature rows of every frame of a batch in
-// one set of launches (the single-frame kernels: rsd.hip; the shared arithmetic: rsd_dev.h).
+// vosch_front.hip -- normals, RSD radii, GRSD transition histograms and feature rows on the GPU
+// (the VOSCH / GRSD features of color_chlac/include/color_chlac/
+// grsd_colorCHLAC_tools.hpp:63-296, 832-843) for every frame of a batch in one set of launches;
+// a single frame (c3h_compute_normals, c3h_extract_grsd / c3h_extract_vosch) is a batch of one.
+// The arithmetic is in rsd_dev.h.
+//
+// Radius searches run over a dense grid of cells of the normal radius: the points are sorted by
+// cell (rocPRIM radix sort of (cell, point) pairs: stable, so a cell lists its points in input
+// order) and every cell keeps its [start, end) range.  A query visits the cells within
+// ceil(radius / cell) of its own.
+//   normals: double sums of the neighbours within the radius (the point included, squared
+//     distances in float as FLANN compares them); covariance -> smallest-eigenvalue eigenvector
+//     (Jacobi, double), flipped towards the viewpoint, curvature = lambda_min / trace;
+//     < 3 neighbours -> NaN (PCL).  A point the voxeliser dropped is nobody's neighbour and gets NaN.
+//   RSD: one downsampled centroid per thread; PCL's computeRSD over the cloud points within
+//     max(rsd_radius, leaf sqrt(3) / 2) of it: the nearest one is the reference ("begin"), the
+//     others' normal angles are binned by their distance to it.
+//   GRSD: one occupied voxel per thread; its type against the 26 neighbour voxels (EMPTY where
+//     unoccupied), int atomics into its subdivision's 6 x 6 matrix.
 //
 // The frames' points are concatenated by a prefix of their counts.  One keys kernel files every
 // point under the composite key (frame << cell_bits | cell) of its frame's own search grid, one
-// stable rocPRIM radix sort orders them -- per frame the order of the single-frame sort: cell
-// order, then input order --, one ranges kernel writes the frames' concatenated cell tables.
+// stable rocPRIM radix sort orders them -- per frame: cell order, then input order --, one
+// ranges kernel writes the frames' concatenated cell tables.
 //   vf_dense_list_kernel lists the cells of kVfDenseCell points and more;
 //   vf_normals_kernel: the work unit is such a cell, not a point.  One wave takes a cell:
 //     the points of the (2 reach + 1)^3 cells around it are staged in LDS in chunks of kVfChunk,
 //     in the visiting order of for_neighbours (dz, dy, dx ascending, then sorted order); each
 //     lane owns one query of the cell and walks the staged points with broadcast LDS reads.  A
 //     neighbour is read from global memory once per 64 queries instead of once per pair.  The
-//     distance test, the ten double sums and the eigen solve are the single-frame functions, the
-//     sums are added in the same order: the normals are the single-frame ones bit for bit.
+//     distance test, the ten double sums and the eigen solve are the per-point walk's functions,
+//     the sums are added in the same order: the normals are the per-point walk's bit for bit.
 //     Cells of fewer than kVfDenseCell points are left to
-//   vf_normals_sparse_kernel: one sorted position per thread with the single-frame per-pair walk
+//   vf_normals_sparse_kernel: one sorted position per thread with the per-pair walk
 //     (a wave that stages 27 cells for two or three queries idles its lanes), and the points in
 //     no cell (the voxeliser dropped them: NaN).
-//   vf_rsd_kernel / vf_grsd_kernel: one centroid per thread over all frames, the single-frame
-//     bodies on the frame's table record.  A neighbour voxel's type is found by a binary search
+//   vf_normals_frame_kernel: a table of one frame, one point per thread with the per-pair walk.
+//     The dense cells of one frame are too few waves to fill the device, and the densest of them
+//     is a tail that only a batch hides.
+//   vf_rsd_kernel / vf_grsd_kernel: one centroid per thread over all frames on the frame's table
+//     record.  A neighbour voxel's type is found by a binary search
 //     of its linear index in the frame's sorted voxel keys (a few KB per frame, against a layout
-//     grid of div_b product words per frame that a batch would have to keep 64 of).
+//     grid of div_b product words per frame that a batch would have to keep 64 of); a single
+//     frame still has its leaf layout and looks the voxel up there.
 //   vf_rows_kernel: columns 0 .. 19 of every row of every frame.
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -176,8 +196,7 @@ __global__ __launch_bounds__(64) void vf_normals_kernel(const VfTable* __restric
 }
 
 // The queries of the cells below kVfDenseCell points, and the points in no cell: one sorted
-// position per thread, the per-pair walk of the single-frame kernel (neighbouring threads are
-// neighbouring points).  A dropped point (non-finite, z >= z_limit) gets NaN.
+// position per thread, the per-pair walk (neighbouring threads are neighbouring points).  A dropped point (non-finite, z >= z_limit) gets NaN.
 template <class K>
 __global__ void vf_normals_sparse_kernel(const VfTable* __restrict__ T, int cell_bits, int64_t ptot,
                                          const K* __restrict__ sorted_keys, float r2, int reach, float vx, float vy,
@@ -197,6 +216,14 @@ __global__ void vf_normals_sparse_kernel(const VfTable* __restrict__ T, int cell
   }
 }
 
+// every point of a one-frame table by the per-pair walk, in input order
+__global__ void vf_normals_frame_kernel(const VfTable* __restrict__ T, float r2, int reach, float vx, float vy, float vz,
+                                        float4* __restrict__ out) {
+  const NbrGrid& g = T->fr[0].g;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < g.n; i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = nrm_point(g, g.pts[i], r2, reach, vx, vy, vz);
+}
+
 __global__ void vf_rsd_kernel(const VfTable* __restrict__ T, int64_t vtot, const float4* __restrict__ nrm,
                               float max_dist, int reach, float2* __restrict__ radii, int32_t* __restrict__ types) {
   for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c < vtot; c += (int64_t)gridDim.x * blockDim.x) {
@@ -211,8 +238,10 @@ __global__ void vf_grsd_kernel(const VfTable* __restrict__ T, int64_t vtot) {
     const int f = vf_frame_of(T->vpre, T->nf, c);
     const VfFrame& fr = T->fr[f];
     const int32_t* vk = fr.vkeys;
+    const int32_t* layout = fr.layout;
     const int64_t nc = fr.ga.nc;
     grsd_voxel(fr.ga, c - T->vpre[f], [&](int64_t v) {
+      if (layout) return layout[v];
       int64_t lo = 0, hi = nc;  // the first key >= v
       while (lo < hi) {
         const int64_t mid = (lo + hi) >> 1;
@@ -244,7 +273,7 @@ __global__ void vf_vox_keys_kernel(const int32_t* __restrict__ layout, int64_t n
 }
 
 // columns 20 .. 136 of a frame's VOSCH rows: its C3-HLAC-117 rows, zeros where exist is 0 (rows
-// of empty subdivisions may be stale), as vosch_concat_kernel writes them
+// of empty subdivisions may be stale)
 __global__ void vf_c3_cols_kernel(const float* __restrict__ c3, const int32_t* __restrict__ exist, int64_t H,
                                   float* __restrict__ rows) {
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < H * 117; e += (int64_t)gridDim.x * blockDim.x) {
@@ -290,12 +319,16 @@ hipError_t vf_nbr_build(const VfTable* d_tab, int which, const VfKey& key, int64
                                tmp, tmp_bytes, s);
 }
 
-hipError_t launch_vf_normals(const VfTable* d_tab, const VfKey& key, int64_t ptot, int64_t ctot, const void* keys,
+hipError_t launch_vf_normals(const VfTable* d_tab, int nf, const VfKey& key, int64_t ptot, int64_t ctot, const void* keys,
                              unsigned long long* list, float radius, int reach, const float vp[3], float4* out,
                              hipStream_t s) {
   if (reach < 1 || reach > kVfMaxReach) return hipErrorInvalidValue;
   if (ptot == 0) return hipSuccess;
   const float r2 = radius * radius;
+  if (nf == 1) {
+    vf_normals_frame_kernel<<<grid_blocks(ptot), 256, 0, s>>>(d_tab, r2, reach, vp[0], vp[1], vp[2], out);
+    return hipGetLastError();
+  }
   if (ctot > 0) {
     const int64_t cap = vf_dense_cap(ptot);
     hipError_t e = hipMemsetAsync(list, 0, sizeof(unsigned long long), s);

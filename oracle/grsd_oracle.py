@@ -1,7 +1,7 @@
 """CPU restatement of the GRSD / VOSCH feature path (TEST INFRASTRUCTURE ONLY).
 
 Only tests/ use this module: it is the checker of the GPU normal / RSD / GRSD kernels
-(csrc/rsd.hip), never part of the product path.
+(csrc/vosch_front.hip), never part of the product path.
 
 Restates, for pcl::PointXYZRGB clouds:
   - pcl::NormalEstimation with a radius search (grsd_colorCHLAC_tools.hpp:63-87,

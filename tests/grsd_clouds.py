@@ -69,6 +69,25 @@ def big_plane(n=2 ** 21 + 1000, seed=9):
     return pts
 
 
+def big_cells(seed=10):
+    """A noisy plane at z = 1.01 (one layer of 0.02 cells) for a batch: 270 x 270 cells of 0.02 at
+    about 28.8 points each (more than 65536 of them hold 16 points and more: one wave per such cell
+    exceeds the cell-staged launch's 65536 workgroups), and a strip of five rows of cells at the
+    largest y at about 4 points per cell, which sorts last and holds every sorted position from
+    2^21 on (8192 x 256 threads cover 2^21 in their first pass)."""
+    rng = np.random.default_rng(seed)
+    nd, ns = 2 ** 21 - 100, 270 * 5 * 4  # 28.8 points per dense cell; the strip's 5400 sort behind them
+    pts = np.empty((nd + ns, 4), np.float32)
+    pts[:nd, 0] = rng.uniform(0.0, 5.4, nd)
+    pts[:nd, 1] = rng.uniform(0.0, 5.4, nd)
+    pts[nd:, 0] = rng.uniform(0.0, 5.4, ns)
+    pts[nd:, 1] = rng.uniform(5.401, 5.499, ns)
+    pts[:, 2] = 1.01 + rng.normal(0, 0.001, nd + ns)
+    pts[:, 3] = rng.integers(0, 1 << 24, nd + ns).astype(np.uint32).view(np.float32)
+    order = rng.permutation(nd + ns)  # the strip's rows anywhere in the input
+    return pts[order]
+
+
 def near_threshold(radii):
     """Voxels with an RSD radius within 1e-4 of a get_type threshold (reference radii)."""
     radii = np.asarray(radii, np.float64)

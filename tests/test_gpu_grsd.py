@@ -1,4 +1,4 @@
-"""VOSCH / GRSD on the GPU (csrc/rsd.hip) against oracle/grsd_oracle.py,
+"""VOSCH / GRSD on the GPU (csrc/vosch_front.hip) against oracle/grsd_oracle.py,
 the restatement of the reference's extractGRSDSignature21 / extractVOSCH
 (color_chlac/include/color_chlac/grsd_colorCHLAC_tools.hpp:63-296, 832-843) and of the PCL
 normal / RSD estimation they call (PCL is not part of the reference tree: "parity

@@ -1,4 +1,4 @@
-"""Normals / RSD / GRSD / VOSCH (csrc/rsd.hip and its host code in csrc/capi.hip) on
+"""Normals / RSD / GRSD / VOSCH (csrc/vosch_front.hip and its host code in csrc/capi_vosch.hip) on
 tests/grsd_clouds.py: what the reference's clean shape clouds of test_gpu_grsd.py never
 reach.  The reference is oracle/grsd_oracle.py (float64); tests/test_grsd_oracle_cpu.py
 establishes on the oracle alone what the cloud contains and that the masks used here are
@@ -23,6 +23,7 @@ import feature_frames_data as ffd
 import grsd_clouds as gc
 import grsd_oracle as go
 import pyoracle as po
+import vosch_frames_data as vd
 from conftest import THR
 
 pytestmark = pytest.mark.gpu
@@ -113,7 +114,7 @@ def test_normals_edge_cases(ctx, edge):
 
 @pytest.mark.parametrize("leaf,reach,kw", [(0.01, 1, SUB), (0.01, 1, dict(subdiv=0)), (0.03, 2, SUB)])
 def test_rsd_grsd_edge_cloud(ctx, edge, leaf, reach, kw):
-    # cells of the search grid that rsd_kernel visits around a centroid, per side
+    # cells of the search grid that vf_rsd_kernel visits around a centroid, per side
     max_dist = np.float32(max(0.01, leaf / 2 * np.sqrt(3)))
     assert int(np.ceil(max_dist * (np.float32(1) / np.float32(RADIUS)))) == reach and max_dist <= 4 * RADIUS
     out = _run(ctx, edge["pts"], leaf, **kw)
@@ -197,7 +198,8 @@ def test_silent_empty_returns(ctx, edge):
 
 
 def test_normals_second_grid_stride_pass(ctx):
-    """2^21 + 1000 points: nbr_keys_kernel, nbr_ranges_kernel and normals_kernel run
+    """2^21 + 1000 points: the kernels that serve c3h_compute_normals (vf_keys_kernel,
+    vf_ranges_kernel and vf_normals_frame_kernel, the per-point walk of a one-frame table) run
     8192 x 256 threads, so the last 1000 rows, and the last 1000 positions of the sort by
     cell, are reached only by a thread's second iteration.  Cells sort by z, then y, then
     x, about 46 points each here: those positions are the upper z layer (z >= 1) of the last
@@ -211,7 +213,9 @@ def test_normals_second_grid_stride_pass(ctx):
     rows = np.concatenate([rng.choice(2 ** 21, 40, replace=False), top,
                            [2 ** 21, n - 1], 2 ** 21 + 1 + rng.choice(998, 48, replace=False)])
     assert len(rows) == 100 and (rows >= 2 ** 21).sum() == 50
-    ctx.voxelize(pts, 0.02)
+    gi = ctx.voxelize(pts, 0.02)
+    pos = _sorted_positions(pts, gi, 0.02)
+    assert (pos[top] >= 2 ** 21).all()  # the ten samples: second-pass positions of the sort by cell
     ctx.compute_normals(RADIUS)
     nrm = ctx.normals(n).astype(np.float64)
     ref = go.normals(pts, RADIUS, rows=rows)
@@ -222,3 +226,58 @@ def test_normals_second_grid_stride_pass(ctx):
     assert np.isfinite(last).all()
     assert np.abs(np.linalg.norm(last[:, :3], axis=1) - 1).max() < 1e-6
     assert (last[:, 2] < -0.9).all()
+
+
+def _sorted_positions(pts, gi, leaf):
+    """Every row's position in the stable sort by search cell (float32 formulas of the library)."""
+    cells, _ = vd.search_cells(pts, gi.min_b[:3], gi.div_b[:3], leaf, RADIUS)
+    assert (cells >= 0).all()
+    pos = np.empty(len(pts), np.int64)
+    pos[np.argsort(cells, kind="stable")] = np.arange(len(pts))
+    return pos
+
+
+def test_batch_normals_second_grid_stride_pass(ctx):
+    """gc.big_cells ahead of a small cloud in one batch: every grid-stride loop of the batch's
+    normals reaches a second iteration.  More than 65536 cells of 16 points and more:
+    vf_normals_kernel's 65536 one-wave workgroups take a second cell each.  Sorted positions from
+    2^21 on in cells of fewer than 16 points: vf_keys_kernel, vf_ranges_kernel and
+    vf_normals_sparse_kernel (8192 x 256 threads) serve them in a second pass.  Both are asserted
+    here first.  Sampled rows against the float64 oracle, the second-pass rows unit normals, and every row bit for bit the per-point walk's that c3h_compute_normals runs."""
+    pts = gc.big_cells()
+    n = len(pts)
+    small = gc.edge_cloud()
+    ctx.set_batch(64)
+    try:
+        _, info = ctx.extract_vosch_frames([pts, small], 0.02, dim=20, row_cap=1, normals_radius=RADIUS)
+        assert list(info["status"]) == [0, 0]
+        nrm = ctx.frame_normals(0)
+    finally:
+        ctx.set_batch(32)
+    cells, dim = vd.search_cells(pts, info["min_b"][0], info["div_b"][0], 0.02, RADIUS)
+    assert (cells >= 0).all()
+    per_cell = np.bincount(cells, minlength=int(dim.prod()))
+    assert (per_cell >= vd.DENSE_MIN).sum() > 65536
+    order = np.argsort(cells, kind="stable")
+    tail = order[2 ** 21:]  # the rows at sorted positions >= 2^21
+    assert len(tail) >= 1000 and (per_cell[cells[tail]] < vd.DENSE_MIN).all()
+    dense_rows = np.flatnonzero(per_cell[cells] >= vd.DENSE_MIN)
+    rng = np.random.default_rng(4)
+    rows = np.concatenate([rng.choice(dense_rows, 50, replace=False), rng.choice(tail, 50, replace=False)])
+    ref = go.normals(pts, RADIUS, rows=rows)
+    ok = np.isfinite(ref[:, 0])
+    assert ok[:50].all() and ok[50:].sum() >= 40 and np.array_equal(np.isfinite(nrm[rows, 0]), ok)
+    np.testing.assert_allclose(nrm[rows][ok].astype(np.float64), ref[ok], atol=1e-5)
+    # every row of the second pass: NaN with fewer than three points in range (float32 distances, as
+    # the library compares them; the strip is thin), else a unit normal, the plane's towards the origin where a dozen points fix it
+    near = pts[pts[:, 1] > 5.37, :3]
+    d = pts[tail, None, :3] - near[None, :, :]
+    cnt = (((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]) < np.float32(RADIUS) * np.float32(RADIUS)).sum(1)
+    last = nrm[tail].astype(np.float64)
+    assert np.array_equal(np.isfinite(last).all(1), cnt >= 3) and (cnt >= 3).sum() >= 1000
+    assert np.isnan(last[cnt < 3]).all()
+    assert np.abs(np.linalg.norm(last[cnt >= 3, :3], axis=1) - 1).max() < 1e-6
+    assert (last[cnt >= 12, 2] < -0.9).sum() >= 0.99 * (cnt >= 12).sum() > 500  # (few points: any direction)
+    ctx.voxelize(pts, 0.02)
+    ctx.compute_normals(RADIUS)
+    assert np.array_equal(nrm.view(np.uint32), ctx.normals(n).view(np.uint32))

@@ -1,8 +1,11 @@
 """Point clouds in, VOSCH / GRSD rows out for a batch (c3h_extract_vosch_frames,
 c3h_run_vosch_point_frames; csrc/vosch_front.hip) against the single-frame route --
 c3h_voxelize + c3h_compute_normals + c3h_extract_vosch / c3h_extract_grsd on a second context,
-which test_gpu_grsd.py and test_gpu_grsd_edges.py pin to the float64 oracle -- never against
-the batched code itself.  Every comparison is of bytes (uint32 views), unconditional: rows,
+which test_gpu_grsd.py and test_gpu_grsd_edges.py pin to the float64 oracle.  Both run the same
+front, the single-frame route as a batch of one: the comparison shows that a frame's results do
+not depend on its batch, and it pins the cell-staged normals of a batch to the per-point walk
+that a table of one frame takes (test_cell_staged_normals_equal_the_per_point_walk does so
+without leaning on that).  Every comparison is of bytes (uint32 views), unconditional: rows,
 info, per-point normals (NaNs in the same rows), per-voxel radii and types, search records.
 The frames: vosch_frames_data.py (test_vosch_frames_cpu.py shows with the oracle alone that they
 hold different grids and subdivision counts, several filled subdivisions, every type, voxels
@@ -45,8 +48,13 @@ def single(rc, pts, leaf, z_limit, radius, dim, normalize, subdiv=vd.SUBDIV, off
     """The single-frame route on the reference context: status, rows, info fields, normals, RSD.
     Computed once per argument set and kept unchanged."""
     key = (id(pts), leaf, z_limit, radius, dim, normalize, subdiv, offset)
-    if key in _REFS:
-        return _REFS[key]
+    if key not in _REFS:
+        _REFS[key] = single_on(rc, pts, leaf, z_limit, radius, dim, normalize, subdiv, offset)
+    return _REFS[key]
+
+
+def single_on(rc, pts, leaf, z_limit, radius, dim, normalize, subdiv=vd.SUBDIV, offset=vd.OFFSET):
+    """The single-frame route on context rc."""
     lib, h = rc.lib, rc.h
     out = {"status": 0, "rows": np.zeros((0, dim), np.float32), "sb": (0, 0, 0)}
     gi = _capi.GridInfo()
@@ -69,7 +77,6 @@ def single(rc, pts, leaf, z_limit, radius, dim, normalize, subdiv=vd.SUBDIV, off
         out["rows"] = rc.features()
         out["normals"] = rc.normals(len(pts))
         out["radii"], out["types"] = rc.rsd()
-    _REFS[key] = out
     return out
 
 
@@ -269,3 +276,74 @@ def test_model_size_is_checked_before_anything_runs(ctx):
                                    offset=vd.OFFSET, normals_radius=vd.RADIUS, d_out=got)
     ctx.synchronize()
     assert (got.cpu().numpy() == -1).all()
+
+
+def test_cell_staged_normals_equal_the_per_point_walk(ctx):
+    """vosch_frames_data.dense_pin_clouds in one batch: the chosen cells hold 16 points and more
+    in frame A (cell-staged kernel, one of them in two passes of 64 queries) and fewer in frame B
+    (per-point walk); the fillers that make the difference are nobody's neighbour among the
+    compared queries, so their normals must agree bit for bit -- a summation-order slip in
+    either kernel would not."""
+    a, b, queries = vd.dense_pin_clouds()
+    ctx.set_batch(64)
+    views, info = run_batch(ctx, [a, b], vd.LEAF, float("inf"), vd.RADIUS, 20, False, 1, subdiv=0, offset=(0, 0, 0))
+    assert list(info["status"]) == [0, 0]
+    vd.check_dense_pin(a, b, queries, (info["min_b"][0], info["div_b"][0]), (info["min_b"][1], info["div_b"][1]))
+    na, nb = ctx.frame_normals(0), ctx.frame_normals(1)
+    assert np.isfinite(nb[queries]).all()
+    assert np.array_equal(u32(na[queries]), u32(nb[queries]))
+
+
+def test_single_frames_and_batches_share_a_context(ctx):
+    """Single-frame calls and batches use the same buffers: interleaved on one context, every
+    result is the one a fresh context gives, and a single-frame c3h_compute_normals takes the
+    batch getters' frames away."""
+    named = vd.batch()
+    clouds = [p for _, p in named]
+    edge = dict(named)["edge"]
+    inf = float("inf")
+    narrow = (edge, vd.LEAF, inf, vd.RADIUS, 137, False)
+    wide = (edge, 0.1, inf, vd.RADIUS, 20, False, 0, (0, 0, 0))  # leaf 0.1: the RSD grid of its own
+    assert 0.1 * np.sqrt(3) / 2 > 4 * vd.RADIUS
+
+    def batch_on(c):
+        c.set_batch(64)
+        views, info = run_batch(c, clouds, vd.LEAF, inf, vd.RADIUS, 137, False, cap)
+        out = []
+        for i, v in enumerate(views):
+            if v is None:
+                out.append(None)
+                continue
+            radii, types = c.frame_rsd(i)
+            out.append(dict(rows=v.cpu().numpy().copy(), normals=c.frame_normals(i), radii=radii, types=types))
+        return out, np.array(info["status"]).copy()
+
+    def fresh(fn, *args):
+        with c3hlac.Context(0) as c:
+            return fn(c, *args)
+
+    def same(got, want):
+        assert got.keys() == want.keys() and got["status"] == 0
+        for k in want:
+            if isinstance(want[k], np.ndarray):
+                assert want[k].size > 0 and np.array_equal(u32(got[k]), u32(want[k])), k
+            else:
+                assert got[k] == want[k], k
+
+    want_narrow, want_wide = fresh(single_on, *narrow), fresh(single_on, *wide)
+    cap = len(want_narrow["rows"])
+    want_batch, want_status = fresh(batch_on)
+    with c3hlac.Context(0) as c:
+        same(single_on(c, *narrow), want_narrow)
+        for _ in range(2):
+            got, status = batch_on(c)
+            assert np.array_equal(status, want_status)
+            for g, w in zip(got, want_batch):
+                assert (g is None) == (w is None)
+                if g is not None:
+                    for k in w:
+                        assert np.array_equal(u32(g[k]), u32(w[k])), k
+            same(single_on(c, *wide), want_wide)
+            same(single_on(c, *narrow), want_narrow)
+            with pytest.raises(_capi.C3HError, match="C3H_ERR_STATE"):
+                c.frame_normals(0)

@@ -3,7 +3,7 @@
 (a) csrc/vosch_frames.h on the host: vosch_frames_check.cpp (its own main) built with
     -fsanitize=address,undefined and run: the prefixes and the frame of an index at every
     boundary (empty frames in the middle and at both ends), each frame's search grid against a
-    literal transcription of nbr_grid(), the composite key's widths, packing, order and
+    literal transcription of the grid arithmetic it replaced, the composite key's widths, packing, order and
     capacity errors, the subdivision counts against grsd_frames' statements.
 
 (b) The oracle alone (pyoracle.voxelize, grsd_oracle) on the frames of vosch_frames_data.py, so
@@ -87,3 +87,12 @@ def test_edge_cloud_fills_subdivisions_with_every_type():
     # EMPTY neighbours (class 5) are counted too: column (i, 5) bins of the upper triangle
     iu = [(i, j) for i in range(6) for j in range(i, 6)][:20]
     assert feat[:, [k for k, (_, j) in enumerate(iu) if j == 5]].sum() > 0
+
+
+def test_dense_pin_clouds_meet_their_conditions():
+    """The clouds of test_gpu_vosch_frames.py::test_cell_staged_normals_equal_the_per_point_walk on
+    the oracle's voxel boxes: same search grid, chosen cells below / at and above the dense-cell
+    threshold, no filler within the radius of a compared query."""
+    a, b, queries = vd.dense_pin_clouds()
+    ga, gb = po.voxelize(a, vd.LEAF)[0], po.voxelize(b, vd.LEAF)[0]
+    vd.check_dense_pin(a, b, queries, (ga.min_b[:3], ga.div_b[:3]), (gb.min_b[:3], gb.div_b[:3]))

@@ -1,7 +1,7 @@
 // vosch_frames_check.cpp -- csrc/vosch_frames.h on the host (its own main; built with
 // -fsanitize=address,undefined by test_vosch_frames_cpu.py): the prefixes and the frame of an
 // index at every boundary (empty frames in the middle and at both ends), each frame's search
-// grid against a literal transcription of nbr_grid() (capi.hip), the composite key widths, its
+// grid against a literal transcription of the single-frame arithmetic it replaced, the composite key widths, its
 // packing and the capacity errors, the subdivision counts against grsd_frames' statements.
 #include <algorithm>
 #include <cmath>
@@ -53,7 +53,7 @@ static void check_prefix(const std::vector<int64_t>& n) {
     }
 }
 
-// nbr_grid() of capi.hip, statement by statement
+// the former nbr_grid() of capi.hip, statement by statement
 static void ref_nbr_grid(const int32_t min_b[3], const int32_t max_b[3], float leaf, float cell, float origin[3], int dim[3],
                          float* inv_cell, bool* too_many) {
   *inv_cell = 1.0f / cell;
@@ -92,6 +92,7 @@ static void check_keys() {
       CHECK(((uint64_t)1 << k.cell_bits) > (uint64_t)mc && (k.cell_bits == 1 || ((uint64_t)1 << (k.cell_bits - 1)) <= (uint64_t)mc));
       CHECK(((uint64_t)1 << k.frame_bits) >= (uint64_t)nf && (k.frame_bits == 1 || ((uint64_t)1 << (k.frame_bits - 1)) < (uint64_t)nf));
       CHECK(k.bits == k.cell_bits + k.frame_bits && k.bits <= 64 && k.wide == (k.bits > 32));
+      if (nf == 1) CHECK(k.frame_bits == 1 && k.bits <= 29 && !k.wide);  // a single frame: 32-bit keys at every grid size
       const uint64_t none = c3h::vf_no_cell(k.cell_bits);
       CHECK(none >= (uint64_t)mc);  // above every real cell index 0 .. mc - 1
       // packing round trip, and the order: frame first, then cell, the no-cell mark last in its frame
@@ -183,7 +184,7 @@ int main() {
     CHECK(c3h::vf_nbr_grid(lo, hi, 0.01f, 0.02f, &g) == c3h::kVfErrCells);
     check_grid(lo, hi, 0.01f, 0.02f);
   }
-  // reach: launch_normals' max(1, (int)ceilf(radius * inv_cell))
+  // reach: max(1, (int)ceilf(radius * inv_cell))
   for (float r : {0.02f, 0.04f, 0.013f, 0.1f, 0.0866025f})
     for (float c : {0.02f, 0.04f, 0.013f, 0.1f, 0.0866025f, 0.005f}) {
       const float inv = 1.0f / c;

@@ -57,3 +57,92 @@ def subdivisions(div_b, subdiv=SUBDIV, offset=OFFSET):
         return (0, 0, 0)
     inv_s = np.float32(1.0 / subdiv)
     return tuple(int(np.ceil(np.float32((int(div_b[a]) - offset[a]) * inv_s))) for a in range(3))
+
+
+# ---- the dense-cell pin (test_gpu_vosch_frames.py::test_cell_staged_normals_equal_the_per_point_walk) ----
+# In a batch a search cell (side = the normals radius r) of DENSE_MIN points and more is served by
+# the cell-staged normals kernel, a cell of fewer by the per-point walk.  Cloud B keeps every cell
+# below that; cloud A is B plus fillers that lift the chosen cells over it without entering any
+# compared query's neighbourhood: the same queries go through the other kernel, with the same
+# neighbours in the same order.
+DENSE_MIN = 16
+PIN_CELLS = [(2 + 3 * i, 2 + 3 * j, 2) for i in range(4) for j in range(2)]  # (cx, cy, cz) of the search grid
+PIN_QUERIES, PIN_CONTEXT, PIN_FILL, PIN_FILL_BIG = 5, 9, 16, 62
+
+
+@functools.lru_cache(maxsize=None)
+def dense_pin_clouds(seed=11):
+    """(A, B, query rows): B = two anchors that pin the voxel box to cells (0, 0, 98) .. (39, 39,
+    105) at LEAF, a sparse noisy plane at z = 1.03, and per chosen cell PIN_QUERIES queries in its
+    low corner (local [0.02, 0.18] r) among PIN_CONTEXT points scattered around that corner;
+    A = B + PIN_FILL fillers per chosen cell (PIN_FILL_BIG in the first: 65 points and more) in
+    the high corner (local [0.87, 0.98] r)."""
+    rng = np.random.default_rng(seed)
+    r = RADIUS
+    origin = np.array([0.0, 0.0, 0.98]) - r  # of the search grid: min_b * leaf - r
+    parts = [np.array([[0.005, 0.005, 0.985], [0.395, 0.395, 1.055]])]
+    plane = np.empty((1500, 3))
+    plane[:, :2] = rng.uniform(0.01, 0.39, (1500, 2))
+    plane[:, 2] = 1.03 + rng.normal(0, 0.0005, 1500)
+    parts.append(plane)
+    n0 = sum(len(p) for p in parts)
+    queries, fill = [], []
+    for k, c in enumerate(PIN_CELLS):
+        corner = origin + np.array(c) * r
+        parts.append(corner + rng.uniform(-0.5 * r, 0.6 * r, (PIN_CONTEXT, 3)))
+        parts.append(corner + rng.uniform(0.02 * r, 0.18 * r, (PIN_QUERIES, 3)))
+        n0 += PIN_CONTEXT
+        queries.extend(range(n0, n0 + PIN_QUERIES))
+        n0 += PIN_QUERIES
+        fill.append(corner + rng.uniform(0.87 * r, 0.98 * r, (PIN_FILL_BIG if k == 0 else PIN_FILL, 3)))
+
+    def cloud(xyz):
+        pts = np.zeros((len(xyz), 4), np.float32)
+        pts[:, :3] = xyz
+        pts[:, 3] = (np.arange(len(xyz), dtype=np.uint32) * 2654435761 >> 8).astype(np.uint32).view(np.float32)
+        pts.setflags(write=False)
+        return pts
+
+    b = np.concatenate(parts)
+    return cloud(np.concatenate([b] + fill)), cloud(b), np.array(queries)
+
+
+def search_cells(pts, min_b, div_b, leaf=LEAF, radius=RADIUS):
+    """The search cell (linear index, -1 outside) of every point, with the float32 formulas of
+    vf_nbr_grid (vosch_frames.h) and cell_of (rsd_dev.h); also the grid's dims."""
+    leaf32, r32 = np.float32(leaf), np.float32(radius)
+    lo = np.asarray(min_b, np.float64) * np.float64(leaf32)
+    hi = (np.asarray(min_b, np.float64) + np.asarray(div_b, np.float64)) * np.float64(leaf32)
+    origin = (lo - np.float64(r32)).astype(np.float32)
+    dim = np.ceil((hi - lo) / np.float64(r32)).astype(np.int64) + 3
+    inv = np.float32(1) / r32
+    t = np.floor((pts[:, :3].astype(np.float32) - origin) * inv)
+    ok = ((t >= 0) & (t < dim.astype(np.float32))).all(1)
+    c = t.astype(np.int64)
+    return np.where(ok, c[:, 0] + dim[0] * (c[:, 1] + dim[1] * c[:, 2]), -1), dim
+
+
+def check_dense_pin(a, b, queries, grid_a, grid_b, radius=RADIUS):
+    """Asserts what the pin rests on; grid_x = (min_b, div_b) of cloud x's voxelization."""
+    assert tuple(grid_a[0]) == tuple(grid_b[0]) and tuple(grid_a[1]) == tuple(grid_b[1])  # same box: same search grid
+    assert np.array_equal(a[:len(b)], b)
+    ca, dim = search_cells(a, *grid_a)
+    cb, _ = search_cells(b, *grid_b)
+    assert (ca >= 0).all() and np.bincount(cb).max() < DENSE_MIN  # B: the per-point walk everywhere
+    chosen = np.unique(cb[queries])
+    want = [c[0] + dim[0] * (c[1] + dim[1] * c[2]) for c in PIN_CELLS]
+    assert sorted(chosen) == sorted(want) and len(chosen) >= 8 and len(queries) >= 32
+    na = np.bincount(ca, minlength=int(dim.prod()))
+    assert (na[chosen] >= DENSE_MIN).all() and na[chosen].max() >= 65  # A: cell-staged, one cell in two passes
+    fillers = a[len(b):, :3].astype(np.float32)
+    assert np.isin(ca[len(b):], chosen).all()
+    q = b[queries, :3].astype(np.float32)
+    d = fillers[:, None, :] - q[None, :, :]
+    d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]  # float32, as pair_d2 adds
+    assert d2.dtype == np.float32 and (d2 >= np.float32(radius) * np.float32(radius)).all()  # no filler is a neighbour
+    dq = q[:, None, :] - b[None, :, :3].astype(np.float32)
+    nb = ((dq[..., 0] * dq[..., 0] + dq[..., 1] * dq[..., 1]) + dq[..., 2] * dq[..., 2]) < np.float32(radius) * np.float32(radius)
+    assert (nb.sum(1) >= 3).all() and nb.sum(1).max() > PIN_QUERIES  # neighbours beyond the query cluster
+    local = (q - ((np.asarray(grid_b[0]) * np.float64(np.float32(LEAF)) - radius).astype(np.float32)
+                  + np.array([[(c % dim[0]), (c // dim[0]) % dim[1], c // (dim[0] * dim[1])] for c in cb[queries]]) * np.float32(radius)))
+    assert (local >= 0).all() and (local <= 0.2 * radius).all()
