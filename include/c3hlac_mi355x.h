@@ -316,7 +316,13 @@ int c3h_search_async(c3h_ctx* ctx, const int32_t range[3], int32_t exist_thresho
  * (c3h_set_score_engine 0 or 2; records and scores byte-identical to c3h_search at engine
  * 2); where the pipeline declines such a batch the lanes run it one frame per launch.  With
  * c3h_set_remove_overlap each frame's records pass through removeOverlap before the frame
- * is complete.  One host call, no host synchronisation. */
+ * is complete.  One host call, no host synchronisation.
+ * What the context holds afterwards (c3h_get_scores, c3h_get_lists, a following c3h_search)
+ * is the frame in slot 0 of its last batch, which a draining call makes the last frame.  The
+ * per-position score arrays are kept for slot 0 of every batch only when the batch runs at
+ * rank 1 through the pipeline (its detections come from the fused argmax, nothing reads the
+ * other slots' arrays); ranks 2 .. 64 and the lanes keep them for every frame, as their
+ * replay needs. */
 int c3h_run_frames(c3h_ctx* ctx, const uint32_t* const* d_grids, int32_t nframes,
                    const int32_t div_b[3], const int32_t min_b[3], float leaf,
                    const c3h_extract_params* p, const int32_t range[3], int32_t exist_threshold,
@@ -547,7 +553,10 @@ int c3h_set_remove_overlap(c3h_ctx* ctx, int32_t enable);
 /* compressed features (setData before the summed-volume table): hist_num x D floats */
 int c3h_get_compressed(c3h_ctx* ctx, float* out, int on_device);
 /* per-position similarity of the last search, modes x M x P doubles (-1 = gated out).
- * n_out receives the element count; pass out=NULL to query it. */
+ * n_out receives the element count; pass out=NULL to query it.  After a batch entry point
+ * (c3h_run_frames and its kin) this is the frame in slot 0 of the context's last batch -- the
+ * last frame of a draining call; no other frame's array can be read back, and at rank 1 the
+ * pipeline does not maintain one. */
 int c3h_get_scores(c3h_ctx* ctx, double* out, int64_t* n_out, int on_device);
 /* SearchObjMulti::removeOverlap on host lists (pure host function, no context). */
 int c3h_remove_overlap(int32_t M, int32_t rank, const int32_t range[3], c3h_det* lists);

@@ -549,6 +549,13 @@ struct SparseSearch {
   // model-0 score is already -1 has -1 for every model (writers always fill all models of
   // a position), so the gate rewrites only positions that passed last time
   int sparse_scores = 0;
+  // a captured batch whose detections come from the fused rank-1 argmax: nothing reads the
+  // score arrays of its slots >= 1 (c3h_get_scores sees slot 0), so for those frames the gate
+  // loads no previous score and writes no -1, and the score role stores no score.  Slot 0 is
+  // kept as ever.  sparse_scores then speaks for slot 0 and sparse_scores_rest for the slots
+  // behind it (a batch that writes every slot again after such batches must dense-fill them)
+  int scores_slot0_only = 0;
+  int sparse_scores_rest = 0;
   // c3h_set_score_engine of the context that runs the tick (read by launch_tick): 1 keeps the
   // tick's score role on the VALU, 0 / 2 see launch_tick
   int score_engine = 0;
@@ -815,8 +822,12 @@ struct c3h_ctx {
   // layout of the score buffers' last search (modes' offsets and sizes, M, frames, buffer):
   // an equal layout lets the gate skip the -1 fill of positions already gated out
   // layout of the last search whose gate was enqueued on `scores` (empty: unknown); a search
-  // of the same layout writes -1 only where that one had not gated the position out already
-  std::vector<int64_t> scores_layout;
+  // of the same layout writes -1 only where that one had not gated the position out already.
+  // Two records: scores_layout vouches for slot 0 (frame 0 of the buffer, the context's view),
+  // scores_layout_rest for the slots behind it.  A pipelined rank-1 batch keeps slot 0 alone
+  // (SparseSearch::scores_slot0_only) and so clears the second; only a search that writes
+  // every slot sets it again
+  std::vector<int64_t> scores_layout, scores_layout_rest;
   std::vector<int64_t> cap_layout;  // a captured (pipelined) search's layout, until its gate runs
   c3h::DevBuf<float> qt;            // D x Opad transposed model basis (fast score path)
   int Opad = 0;

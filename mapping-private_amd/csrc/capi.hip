@@ -339,8 +339,10 @@ int c3h::search_frames(c3h_ctx* ctx, int nf, const int32_t range[3], int32_t thr
     layout.push_back(rm.m[i].offset);
     layout.push_back(rm.m[i].P);
   }
-  const bool same_layout = layout == ctx->scores_layout;
+  const bool same_layout = layout == ctx->scores_layout;  // slot 0
+  const bool same_rest = layout == ctx->scores_layout_rest;  // slots >= 1
   ctx->scores_layout.clear();  // recorded again once this search's gate is enqueued (below)
+  ctx->scores_layout_rest.clear();
   ENSURE(ctx->G, (size_t)nf * H * ctx->D);
   // sparse compress: only the non-empty rows of the extract's list (the rest stay stale
   // and every consumer gates them on exist)
@@ -424,6 +426,7 @@ int c3h::search_frames(c3h_ctx* ctx, int nf, const int32_t range[3], int32_t thr
     q.mpg = std::max(1, 64 / ctx->r);
     q.scores = ctx->scores.p;
     q.sparse_scores = same_layout ? 1 : 0;
+    q.sparse_scores_rest = same_rest ? 1 : 0;
     q.nmodes = rm.n;
     q.score_mfma = mf ? 1 : 0;
     q.skip_empty = ctx->exist_gates_rows ? 1 : 0;
@@ -540,7 +543,8 @@ int c3h::search_frames(c3h_ctx* ctx, int nf, const int32_t range[3], int32_t thr
       Timed t(ctx, 3, nf);
       HIPCHK(c3h::launch_sparse_search(q, sparse_g ? &sc : nullptr, ctx->stream));
     }
-    ctx->scores_layout.swap(layout);  // the gate writes every position of this layout
+    ctx->scores_layout_rest = layout;  // the gate writes every position of this layout, in every slot
+    ctx->scores_layout.swap(layout);
     if (q.prof) {
       int rc = prof_dump(ctx, "score_list_kernel", nparts);
       if (rc != C3H_OK) return rc;
@@ -564,6 +568,7 @@ int c3h::search_frames(c3h_ctx* ctx, int nf, const int32_t range[3], int32_t thr
       Timed t(ctx, 3);
       for (auto& a : launches) HIPCHK(c3h::launch_score(a, ctx->stream));
     }
+    ctx->scores_layout_rest = layout;
     ctx->scores_layout.swap(layout);
     Timed t(ctx, 4);
     HIPCHK(c3h::launch_replay(ctx->scores.p, rm, ctx->M, ctx->rank, range[0], range[1], range[2], clean,

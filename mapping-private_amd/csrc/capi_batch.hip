@@ -152,7 +152,11 @@ int pipe_tick(c3h_ctx* ctx, const c3h_ctx::PipeBatch* fresh) {
       hipError_t e = c3h::launch_remove_overlap_frames(b.ro, ctx->stream);
       if (e != hipSuccess) return hip_fail(ctx, "launch_remove_overlap_frames", e);
     }
-    if (b.age == 2 && b.set) b.set->scores_layout = b.layout;  // this tick enqueued its gate
+    if (b.age == 2 && b.set) {  // this tick enqueued its gate: slot 0 always, the rest when it keeps them
+      b.set->scores_layout = b.layout;
+      if (b.q.scores_slot0_only) b.set->scores_layout_rest.clear();
+      else b.set->scores_layout_rest = b.layout;
+    }
     if (b.age == 1 && b.fix) {  // its tile role ran in this tick: the off-cell fixup before its compress
       hipError_t e = c3h::launch_point_fixup(b.fx, ctx->stream);
       if (e != hipSuccess) return hip_fail(ctx, "launch_point_fixup", e);
@@ -211,6 +215,8 @@ bool pipe_capture_end(const c3h_ctx* ctx, c3h_ctx* c, const int32_t range[3], c3
   if (!c->cap_argmax && !(c->cap_replay && c->rank >= 2 && !c->cap_q.lists && !c->cap_q.partials)) return false;
   fresh->set = c;
   fresh->layout = c->cap_layout;
+  // rank 1: the detections come from the partials, and c3h_get_scores sees slot 0 only
+  fresh->q.scores_slot0_only = c->cap_argmax ? 1 : 0;
   fresh->replay = !c->cap_argmax;
   fresh->rp = c->cap_rp;
   fresh->overlap = overlap_wanted(ctx);

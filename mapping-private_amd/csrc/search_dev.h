@@ -514,6 +514,11 @@ __device__ __forceinline__ int find_mode(const SparseSearch& a, int64_t g) {
   return mi;
 }
 
+// whether frame f's score arrays are kept (SparseSearch::scores_slot0_only)
+__device__ __forceinline__ bool scores_kept(const SparseSearch& a, int64_t f) {
+  return !a.scores_slot0_only || f == 0;
+}
+
 // frame f of a batched search: per-frame pointers at base + f * stride (no struct copy:
 // a by-value SparseSearch with its dynamically indexed mode table would live in scratch)
 __device__ __forceinline__ void gate_body(const SparseSearch& a, int bid, int64_t f) {
@@ -523,6 +528,9 @@ __device__ __forceinline__ void gate_body(const SparseSearch& a, int bid, int64_
   const int32_t* __restrict__ fexist = a.exist + f * a.s_exist;
   double* __restrict__ fscores = a.scores + f * a.s_scores;
   long long* __restrict__ flist = a.list + f * a.s_list;
+  // a frame whose score arrays nobody reads: no previous score is loaded, no -1 written
+  const bool keep = scores_kept(a, f);
+  const bool sparse = f == 0 ? a.sparse_scores != 0 : a.sparse_scores_rest != 0;
   if (bid == 0 && tid == 0) {  // the next search's counters
     fcnt[(a.epoch + 1) & 1] = 0;
     fdone[(a.epoch + 1) & 1] = 0;
@@ -539,7 +547,7 @@ __device__ __forceinline__ void gate_body(const SparseSearch& a, int bid, int64_
     const int xyn = a.xn * a.yn;
     const int h = z * xyn + y * a.xn + x;
     // model 0's score of the previous search of this layout (issued with the exist loads)
-    const double prev = a.sparse_scores ? fscores[md.offset + p] : 0.0;
+    const double prev = keep && sparse ? fscores[md.offset + p] : 0.0;
     int e = 0;  // SearchObj::clipValue<int> on exist_voxel_num (search.cpp:484-535), exact
     for (int dz = 0; dz < md.zr; ++dz)
       for (int dy = 0; dy < md.yr; ++dy)
@@ -550,7 +558,7 @@ __device__ __forceinline__ void gate_body(const SparseSearch& a, int bid, int64_
       pass = pass && x + md.xr <= L[0] && y + md.yr <= L[1] && z + md.zr <= L[2];
     }
     entry = ((int64_t)mi << 40) | p;
-    if (!pass && prev != -1.0)  // (a dense fill without sparse_scores: prev is 0)
+    if (keep && !pass && prev != -1.0)  // (a dense fill without sparse_scores: prev is 0)
       for (int m = 0; m < a.M; ++m) fscores[md.offset + (int64_t)m * md.P + p] = -1.0;
   }
   const unsigned long long m = __ballot(pass);
@@ -732,6 +740,7 @@ __device__ __forceinline__ void score_list_body(const SparseSearch& b, int bx, i
   const float* __restrict__ fG = b.G + fz * b.s_G;
   const int32_t* __restrict__ fexist = b.exist + fz * b.s_exist;
   double* __restrict__ fscores = b.scores + fz * b.s_scores;
+  const bool keep = scores_kept(b, fz);  // else nothing reads this frame's score arrays
   const long long* __restrict__ flist = b.list + fz * b.s_list;
   const uint32_t* fcnt = b.cnt + fz * b.s_cnt;
   uint32_t* fdone = b.done + fz * b.s_cnt;
@@ -895,7 +904,7 @@ __device__ __forceinline__ void score_list_body(const SparseSearch& b, int bx, i
           sc = sqrt((double)q2) / sqrt((double)ffv[pp]);
           const long long en = ent[pp];
           const ModeGeom& md = a.md[(int)(en >> 40)];
-          fscores[md.offset + (int64_t)(m0 + mm) * md.P + (en & ((1ll << 40) - 1))] = sc;
+          if (keep) fscores[md.offset + (int64_t)(m0 + mm) * md.P + (en & ((1ll << 40) - 1))] = sc;
         }
         bsc[e] = sc;
       }
@@ -991,6 +1000,7 @@ __device__ __forceinline__ void score_tick_mfma_body(const SparseSearch& b, int 
   const float* __restrict__ fG = b.G + fz * b.s_G;
   const int32_t* __restrict__ fexist = b.exist + fz * b.s_exist;
   double* __restrict__ fscores = b.scores + fz * b.s_scores;
+  const bool keep = scores_kept(b, fz);  // else nothing reads this frame's score arrays
   const long long* __restrict__ flist = b.list + fz * b.s_list;
   const uint32_t* fcnt = b.cnt + fz * b.s_cnt;
   uint32_t* fdone = b.done + fz * b.s_cnt;
@@ -1125,7 +1135,7 @@ __device__ __forceinline__ void score_tick_mfma_body(const SparseSearch& b, int 
           sc = sqrt((double)q2) / sqrt((double)ffv[pp]);
           const long long en = ent[pp];
           const ModeGeom& md = a.md[(int)(en >> 40)];
-          fscores[md.offset + (int64_t)(m0 + mm) * md.P + (en & ((1ll << 40) - 1))] = sc;
+          if (keep) fscores[md.offset + (int64_t)(m0 + mm) * md.P + (en & ((1ll << 40) - 1))] = sc;
         }
         bsc[e] = sc;
       }
@@ -1207,6 +1217,7 @@ __device__ __forceinline__ void score_tick_wide_body(const SparseSearch& b, int 
   const float* __restrict__ fG = b.G + fz * b.s_G;
   const int32_t* __restrict__ fexist = b.exist + fz * b.s_exist;
   double* __restrict__ fscores = b.scores + fz * b.s_scores;
+  const bool keep = scores_kept(b, fz);  // else nothing reads this frame's score arrays
   const long long* __restrict__ flist = b.list + fz * b.s_list;
   const uint32_t* fcnt = b.cnt + fz * b.s_cnt;
   uint32_t* fdone = b.done + fz * b.s_cnt;
@@ -1352,7 +1363,7 @@ __device__ __forceinline__ void score_tick_wide_body(const SparseSearch& b, int 
             sc = sqrt((double)q2) / sqrt((double)ffv[pp]);
             const long long en = ent[pp];
             const ModeGeom& md = a.md[(int)(en >> 40)];
-            fscores[md.offset + (int64_t)m * md.P + (en & ((1ll << 40) - 1))] = sc;
+            if (keep) fscores[md.offset + (int64_t)m * md.P + (en & ((1ll << 40) - 1))] = sc;
           } else {
             carry[(par ^ 1) * kFP + pp] = q2;
           }

@@ -6,7 +6,7 @@ cd "$(dirname "$0")/../mapping-private_amd"
 NAME=$1; shift
 B=build/variants/$NAME; mkdir -p $B lib/variants
 pids=()
-for f in capi capi_batch voxelize c3hlac search pipeline feat_front colour pcdio pca ingest rsd dist; do
+for f in $(ls csrc/*.hip | xargs -n1 basename | sed 's/\.hip$//'); do
   rm -f $B/$f.o
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function $* -c csrc/$f.hip -o $B/$f.o &
   pids+=($!)
