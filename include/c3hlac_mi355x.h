@@ -480,10 +480,25 @@ int c3h_stream_feature_frames(c3h_ctx* ctx, const float* const* d_feat, const in
  * more than row_cap rows, else the error the single-frame route fails with on that frame (a
  * cloud without a valid point: C3H_ERR_STATE, as c3h_compute_normals).  A frame with a negative
  * status leaves its slot untouched and does not affect the other frames.
- * Frames go in batches of c3h_set_batch.  Per frame, in turn, the library runs c3h_voxelize's
- * voxeliser, the exact centroids, the leaf layout and (dim 137) the C3-HLAC-117 extract, whose
- * columns go straight into columns 20 .. 136; c3h_voxelize's one host synchronisation per frame
- * stays (a batched voxeliser that keeps every centroid would remove it).  Everything else runs
+ * Frames go in batches of c3h_set_batch.  The head of a batch -- every frame's voxel grid
+ * geometry, its exact centroids in leaf-layout order and their voxel indices -- comes from one of
+ * two routes, chosen by c3h_set_vosch_head, with the same bytes everywhere (rows, info, the
+ * getters below, search records):
+ *   1 (the default): the batched voxel head.  One bounds pass over the batch's concatenated
+ *     points, one host synchronisation to size the frames' grids and decide their statuses, one
+ *     stable radix sort of (frame, voxel) keys whose runs are the voxels with their points in
+ *     input order, one thread per run for the centroid, and a second synchronisation for the
+ *     frames' voxel counts: two per batch, whatever the number of frames.  Host clouds are
+ *     staged once, straight into the batch's concatenation.  At dim 137 the C3-HLAC-117 extract
+ *     still runs frame by frame, on a grid buffer of the head's own that holds one frame's
+ *     words at a time, and writes columns 20 .. 136.  After such a call the context holds no
+ *     single-frame grid: until the next c3h_voxelize / c3h_set_grid, c3h_compute_normals,
+ *     c3h_extract, c3h_extract_grsd, c3h_extract_vosch and c3h_get_grid_info return
+ *     C3H_ERR_STATE.  The single-frame voxeliser's own buffers and bookkeeping are not touched.
+ *   0: per frame, in turn, c3h_voxelize's voxeliser, the exact centroids, the leaf layout and
+ *     (dim 137) the extract, with c3h_voxelize's host synchronisations per frame; the context
+ *     then holds the last good frame's grid.
+ * Everything else runs
  * once per batch over the concatenated frames: one keys kernel, one stable radix sort of
  * (frame, cell) keys and one ranges kernel build every frame's radius-search grid, the normals
  * run by occupied cell with the cell's neighbourhood staged in LDS (cells of fewer than 16 points
@@ -502,6 +517,10 @@ int c3h_extract_vosch_frames(c3h_ctx* ctx, const float* const* pts, const int64_
                              int on_device, float leaf, float z_limit, const c3h_vosch_params* p,
                              int32_t dim /* 137 VOSCH | 20 GRSD */, int64_t row_cap, float* d_rows,
                              c3h_frame_info* info);
+/* The head of c3h_extract_vosch_frames and c3h_run_vosch_point_frames (and of the facade's
+ * SearchVOSCH / SearchGRSD::searchBatch through them): 1 = the batched voxel head, 0 = the
+ * per-frame head (see above); any other value: C3H_ERR_ARG.  Nothing else reads it. */
+int c3h_set_vosch_head(c3h_ctx* ctx, int32_t head);
 /* The whole callback of detect_object_vosch_multi.cpp for a batch: the same front end writes
  * into rows the context owns (row_cap = the canvas_b product), then the body of
  * c3h_run_feature_frames searches them with the exist rule C3H_EXIST_VOSCH (dim 137) or

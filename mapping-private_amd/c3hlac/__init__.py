@@ -246,6 +246,12 @@ class Context:
         frame's records through SearchObjMulti::removeOverlap on the device (ranks up to 64)."""
         self._chk(self.lib.c3h_set_remove_overlap(self.h, int(bool(enable))), "set_remove_overlap")
 
+    def set_vosch_head(self, head):
+        """c3h_set_vosch_head: the head of extract_vosch_frames / run_vosch_point_frames -- 1 the
+        batched voxel head (two host synchronisations per batch), 0 c3h_voxelize frame by frame.
+        The same bytes either way."""
+        self._chk(self.lib.c3h_set_vosch_head(self.h, int(head)), "set_vosch_head")
+
     def set_search_precision(self, fp16):
         """c3h_set_search_precision: f16 operands on the matrix cores for the compress of grids
         of >= 65,536 subdivisions (D <= 128) and for the matrix-core projection (any size;

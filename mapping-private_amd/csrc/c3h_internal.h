@@ -197,6 +197,45 @@ struct VoxSortBufs {
 };
 hipError_t launch_vox_sorted(const VoxArgs& a, const int mn[3], const int dv[3], int64_t nv, VoxSortBufs& b,
                              uint32_t* counts, float4* cent, int32_t* offcell, hipStream_t s);
+// ---- the batched voxel head of the VOSCH / GRSD front (voxelize.hip vh_*; vosch_frames.h) ----
+// The frames of a batch over their concatenated points (prefix ppre): what differs per frame
+// sits in a device table.  Point indices of the sort are concatenated ones.
+struct VhFrame {
+  const float4* pts;
+  int32_t mn[3], dv[3];  // min_b, div_b (the keys and the emit; the bounds pass writes them to the host first)
+};
+struct VhTable {
+  int64_t ppre[kVfMaxFrames + 1];
+  int nf, voxel_bits;
+  float inv_leaf, leaf, z_limit;
+  VhFrame fr[kVfMaxFrames];
+};
+// per frame of T: min / max cell, valid points and the beyond flag of its points into rec[f]
+// (vh_rec_init values before the launch)
+hipError_t launch_vh_bounds(const VhTable* d_tab, int64_t ptot, VhRec* rec, hipStream_t s);
+struct VhSortBufs {
+  uint64_t *keys, *keys2;    // ptot; keys2 holds the sorted keys
+  uint32_t *idx, *idx2;      // ptot
+  uint32_t *head, *block_sums;  // ptot, scan_blocks(ptot)
+  int32_t* ord;              // ptot: the run ordinal of every sorted position
+  int64_t* vord;             // kVfMaxFrames + 1: the ordinal prefix of the frames
+  void* tmp;                 // nullptr: size query
+  size_t tmp_bytes;
+};
+// keys, the sort, the runs and the emit: frame f's n_occ centroids (float4, .w the colour bits)
+// and voxel indices at cent / vkeys + vord[f], in leaf-layout order; rec[f].n_occ, n_off
+hipError_t launch_vh_voxels(const VhTable* d_tab, int nf, const VfKey& key, int64_t ptot, VhSortBufs& b, float4* cent,
+                            int32_t* vkeys, VhRec* rec, hipStream_t s);
+// the off-cell records ({voxel index, centroid cell xyz, the same, 0} relative to min_b, as the
+// single-frame voxeliser files them) of every frame, frame f's at offcell + 8 * opre.v[f]
+struct VhOffPre {
+  int64_t v[kVfMaxFrames + 1];
+};
+hipError_t launch_vh_offcell(const VhTable* d_tab, int nf, const int64_t* vord, int64_t vtot, const float4* cent,
+                             const int32_t* vkeys, const VhOffPre& opre, VhRec* rec, int32_t* offcell, hipStream_t s);
+// a frame's colour words into a zero grid through its voxel list (set = 1), and out again (0)
+hipError_t launch_vh_grid_words(const float4* cent, const int32_t* vkeys, int64_t nc, uint32_t* grid, int set,
+                                hipStream_t s);
 int64_t scan_blocks(int64_t n);
 hipError_t launch_leaf_layout(const uint32_t* grid, int64_t nvox, int32_t* leaf,
                               uint32_t* block_sums, int64_t nblocks, hipStream_t s);
@@ -700,7 +739,7 @@ struct c3h_ctx {
   c3h::DevBuf<float4> dsamp;        // downsampled centroids (leaf-layout order)
   int64_t rsd_n = 0;                // centroids with valid radii / types
   // the front (vosch_front.hip): the device table of the batch in flight, the concatenated
-  // points (host input only), sort buffers (the sorted voxeliser borrows them), cell tables,
+  // points (host input only), sort buffers (the sorted voxeliser and the batched voxel head borrow them), cell tables,
   // normals, centroids, voxel keys, radii, types and transitions of its frames
   c3h::DevBuf<c3h::VfTable> vf_tab;
   c3h::DevBuf<float4> vf_pts, vf_normals, vf_cent;
@@ -719,6 +758,20 @@ struct c3h_ctx {
   std::vector<int32_t> vf_status;
   c3h::VfTable* vf_htab = nullptr;  // pinned host copy of the table (its upload is asynchronous)
   hipEvent_t vf_up_ev = nullptr;    // behind the table's last upload: the host copy may change again
+  // the batched voxel head of those calls (c3h_set_vosch_head; voxelize.hip vh_*): buffers of its
+  // own beside the front's sort buffers, so the single-frame voxeliser's state is left alone
+  int vosch_head = 1;               // 0: every frame through c3h_voxelize; 1: the batch at once
+  struct VhHost {                   // pinned: the head's uploads and readbacks
+    c3h::VhTable tab[2];            // the bounds pass's table, the sort's (failed frames dropped)
+    c3h::VhRec init[c3h::kVfMaxFrames], back[c3h::kVfMaxFrames];
+  };
+  VhHost* vh_host = nullptr;
+  c3h::DevBuf<c3h::VhTable> vh_tab;
+  c3h::DevBuf<c3h::VhRec> vh_rec;
+  c3h::DevBuf<uint32_t> vh_head, vh_sums;
+  c3h::DevBuf<int32_t> vh_ord, vh_offcell;
+  c3h::DevBuf<int64_t> vh_vord;
+  c3h::DevBuf<uint32_t> vh_grid;    // dim 137: one frame's words at a time, zero between frames
   // voxeliser state (voxelize.hip): toroidal accumulators, entry / grid-word lists by
   // epoch parity, counters; the grid words the previous frame wrote are cleared by the next
   c3h::DevBuf<ulonglong2> vacc;

@@ -678,6 +678,7 @@ void c3h_destroy(c3h_ctx* ctx) {
   }
   if (ctx->h_small) (void)hipHostFree(ctx->h_small);
   if (ctx->vf_htab) (void)hipHostFree(ctx->vf_htab);
+  if (ctx->vh_host) (void)hipHostFree(ctx->vh_host);
   if (ctx->vf_up_ev) (void)hipEventDestroy(ctx->vf_up_ev);
   if (ctx->h_recs) (void)hipHostFree(ctx->h_recs);
   if (ctx->h_dl) (void)hipHostFree(ctx->h_dl);
@@ -1163,8 +1164,17 @@ bool c3h::extract_params_ok(const c3h_extract_params* p) {
          p->color_mode <= C3H_COLOR_CHLAC;
 }
 
+c3h::VoxelExtras c3h::voxelize_extras(const c3h_ctx* ctx) {
+  VoxelExtras vx;
+  if (!ctx || !ctx->table_valid || ctx->grid_ptr != ctx->grid.p) return vx;
+  vx.offcell = ctx->voffcell.p;
+  vx.n_offcell = ctx->n_offcell;
+  vx.listed = ctx->vargs.lists != nullptr;
+  return vx;
+}
+
 int c3h::extract_frames(c3h_ctx* ctx, const uint32_t* const* grids, int nf, const c3h_extract_params* p,
-                        int32_t subdiv_out[3], int64_t* hist_num_out) {
+                        int32_t subdiv_out[3], int64_t* hist_num_out, const VoxelExtras& vx) {
   if (!ctx || !p) return C3H_ERR_ARG;
   if (!extract_params_ok(p))
     return fail(ctx, C3H_ERR_ARG, "c3h_extract: variant must be 981 or 117, color_mode a C3H_COLOR_* value");
@@ -1220,8 +1230,7 @@ int c3h::extract_frames(c3h_ctx* ctx, const uint32_t* const* grids, int nf, cons
     }
   // voxels whose centroid leaves their cell (voxelize's exact pass) are corrected in the
   // exact 64-bit sums: the extract then runs in the atomic mode
-  const bool offcell = nf == 1 && !ctx->capture && ctx->table_valid && ctx->n_offcell > 0 &&
-                       ctx->grid_ptr == ctx->grid.p;
+  const bool offcell = nf == 1 && !ctx->capture && vx.n_offcell > 0;
   const bool atomic = split[0] || split[1] || split[2] || offcell;
   const bool all_covered = covered[0] && covered[1] && covered[2] && ntiles > 0;
   ENSURE(ctx->feat, (size_t)nf * hist_num * F);
@@ -1378,8 +1387,7 @@ int c3h::extract_frames(c3h_ctx* ctx, const uint32_t* const* grids, int nf, cons
     // the grid of the last c3h_voxelize: its occupied voxels are listed (vox_scatter / the
     // sorted path), so the tiles are stamped from the list instead of the 4 B/voxel stream
     // (sparse frames: 16 B of list work per occupied voxel below the grid's 4 B per voxel)
-    const bool from_list = !ctx->capture && nf == 1 && ctx->table_valid &&
-                           ctx->grid_ptr == ctx->grid.p && ctx->vargs.lists &&
+    const bool from_list = !ctx->capture && nf == 1 && vx.listed &&
                            (int64_t)ctx->vns * 16 < (int64_t)div[0] * div[1] * div[2];
     if (from_list) {
       const c3h::VoxArgs& va = ctx->vargs;
@@ -1410,7 +1418,7 @@ int c3h::extract_frames(c3h_ctx* ctx, const uint32_t* const* grids, int nf, cons
       }
       if (offcell) {
         const int sbv[3] = {l.sbx, l.sby, mode1 ? 1 : sb[2]};
-        HIPCHK(c3h::launch_offcell_delta(ctx->voffcell.p, (int)ctx->n_offcell, l, mode1 ? 1 : 0, p->offset, sbv,
+        HIPCHK(c3h::launch_offcell_delta(vx.offcell, (int)vx.n_offcell, l, mode1 ? 1 : 0, p->offset, sbv,
                                          inv_s, ctx->stream));
       }
       if (atomic)

@@ -3,11 +3,16 @@
 // c3h_extract_vosch and their getters) and for a batch of frames (c3h_extract_vosch_frames,
 // c3h_run_vosch_point_frames and theirs).
 //
-// Per frame, in turn, the host code of capi.hip computes what only it can: the voxel grid
-// (c3h_voxelize, which synchronises the host once per frame), the exact centroids, the leaf
-// layout and, at dim 137, the C3-HLAC-117 rows (extract_frames), whose columns go straight into
-// the frame's output rows.  What a frame leaves for the front is small: its geometry on the
-// host (VfHostFrame), its centroids in leaf order and their voxel keys.  Everything else --
+// The head of a batch gives the front what only a voxeliser can: every frame's voxel grid
+// geometry, its exact centroids in leaf order and their voxel keys and, at dim 137, the
+// C3-HLAC-117 rows (extract_frames), whose columns go straight into the frame's output rows.
+// c3h_set_vosch_head chooses it.  1 (head_batch): the batched voxel head of voxelize.hip (vh_*)
+// -- a bounds pass over the batch's concatenated points, the host's decision per frame
+// (vosch_frames.h), one sort whose runs are the voxels, a thread per run -- with two host
+// synchronisations per batch; the extract still runs per frame, on a grid of the head's own.
+// 0 (front_head): per frame, in turn, c3h_voxelize (which synchronises the host), the exact
+// centroids, the leaf layout and the extract.  What a frame leaves for the front is small: its
+// geometry on the host (VfHostFrame), its centroids in leaf order and their voxel keys.  Everything else --
 // search grids, normals, RSD, GRSD transitions, columns 0 .. 19 -- runs once per batch over a
 // device table of per-frame records.  The single-frame entry points are a batch of one frame in
 // two steps: c3h_compute_normals fills the normals' half of the record and runs that stage,
@@ -37,10 +42,8 @@ struct FrontParams {
 float rsd_max_dist(const c3h_grsd_params* gp, float leaf) {
   return (float)std::max((double)gp->rsd_radius, (double)leaf / 2 * std::sqrt(3.0));
 }
-// A wide RSD radius (large leaves: leaf sqrt(3)/2 > 4 x the normal radius) gets a search grid of
-// its own radius; the normals are already computed, and the RSD's per-bin min/max angles do not
-// depend on the neighbour visiting order
-bool rsd_wide(float max_dist, float cell) { return max_dist > 4 * cell; }
+// A wide RSD radius (c3h::vf_rsd_wide) gets a search grid of its own radius; the normals are
+// already computed, and the RSD's per-bin min/max angles do not depend on the neighbour visiting order
 
 int nbr_grid(c3h_ctx* ctx, float cell, c3h::VfGrid* g) {
   if (c3h::vf_nbr_grid(ctx->info.min_b, ctx->info.max_b, ctx->info.leaf, cell, g) != c3h::kVfOk)
@@ -78,7 +81,7 @@ int frame_grsd(c3h_ctx* ctx, const c3h_grsd_params* gp, int32_t* vkeys, c3h::VfH
   fr->vkeys = vkeys;
   fr->g2 = fr->g;
   const float max_dist = rsd_max_dist(gp, ctx->info.leaf);
-  if (fr->H > 0 && rsd_wide(max_dist, fr->g.cell)) {
+  if (fr->H > 0 && c3h::vf_rsd_wide(max_dist, fr->g.cell)) {
     rc = nbr_grid(ctx, max_dist, &fr->g2);
     if (rc != C3H_OK) return rc;
   }
@@ -162,7 +165,7 @@ void fill_record(c3h_ctx* ctx, c3h::VfTable* ht, int j, const c3h::VfHostFrame& 
 int front_run(c3h_ctx* ctx, c3h::VfTable* ht, const c3h::VfHostFrame* ff, int nb, int stages, const FrontParams& q) {
   const int64_t ptot = ht->ppre[nb], ctot = ht->cpre[nb], c2tot = ht->c2pre[nb], vtot = ht->vpre[nb], htot = ht->hpre[nb];
   if (ptot == 0) return C3H_OK;
-  const bool wide = (stages & kStageGrsd) && vtot > 0 && rsd_wide(q.max_dist, q.radius);
+  const bool wide = (stages & kStageGrsd) && vtot > 0 && c3h::vf_rsd_wide(q.max_dist, q.radius);
   int64_t max_cells = 1;
   for (int j = 0; j < nb; ++j) max_cells = std::max(max_cells, std::max(ff[j].g.ncell, ff[j].g2.ncell));
   c3h::VfKey key{};
@@ -227,7 +230,8 @@ float grsd_norm(const c3h_grsd_params* gp) { return gp->normalize ? (float)(20.0
 
 // The C3 part of extractVOSCH (grsd_colorCHLAC_tools.hpp:832-843) on the grid of the last
 // c3h_voxelize: its C3-HLAC-117 rows (ctx->feat, ctx->exist) into columns 20 .. 136 of rows
-int c3_cols(c3h_ctx* ctx, const c3h_grsd_params* gp, const int32_t thr[3], int32_t color_mode, int64_t H, float* rows) {
+int c3_cols(c3h_ctx* ctx, const c3h_grsd_params* gp, const int32_t thr[3], int32_t color_mode, int64_t H, float* rows,
+            const c3h::VoxelExtras& vx) {
   c3h_extract_params e{};
   e.variant = 117;
   for (int a = 0; a < 3; ++a) {
@@ -239,7 +243,7 @@ int c3_cols(c3h_ctx* ctx, const c3h_grsd_params* gp, const int32_t thr[3], int32
   const uint32_t* g = ctx->grid_ptr;
   int32_t sb2[3];
   int64_t H2 = 0;
-  const int rc = c3h::extract_frames(ctx, &g, 1, &e, sb2, &H2);
+  const int rc = c3h::extract_frames(ctx, &g, 1, &e, sb2, &H2, vx);
   if (rc != C3H_OK) return rc;
   if (H2 != H) return fail(ctx, C3H_ERR_STATE, "extract_vosch: GRSD / C3 subdivisions differ");
   HIPCHK(c3h::launch_vf_c3_cols(ctx->feat.p, ctx->exist.p, H, rows, ctx->stream));
@@ -300,7 +304,211 @@ int front_head(c3h_ctx* ctx, const float* pts, int64_t n, int on_device, float l
     HIPCHK(hipMemcpyAsync(ctx->vf_cent.p + v0, ctx->dsamp.p, (size_t)fr->nc * 16, hipMemcpyDeviceToDevice, ctx->stream));
     fr->cent = ctx->vf_cent.p + v0;
   }
-  if (dim == 137) return c3_cols(ctx, &p->grsd, p->thr, p->color_mode, fr->H, fr->rows);
+  if (dim == 137) return c3_cols(ctx, &p->grsd, p->thr, p->color_mode, fr->H, fr->rows, c3h::voxelize_extras(ctx));
+  return C3H_OK;
+}
+
+static_assert(c3h::vh_status(c3h::kVhGood) == C3H_OK && c3h::vh_status(c3h::kVhArgs) == C3H_ERR_ARG &&
+                  c3h::vh_status(c3h::kVhNoPoint) == C3H_ERR_STATE && c3h::vh_status(c3h::kVhRows) == C3H_ERR_RANGE,
+              "vh_status speaks the header's codes");
+
+const char* head_reason(int reason) {
+  switch (reason) {
+    case c3h::kVhArgs: return "c3h_voxelize: bad arguments";
+    case c3h::kVhPoints: return "c3h_voxelize: at most 16,777,215 points per call";
+    case c3h::kVhBeyond: return "c3h_voxelize: leaf size too small (cell coordinates beyond +-2^20)";
+    case c3h::kVhNoPoint: return "compute_normals: needs the points of a c3h_voxelize";
+    case c3h::kVhVoxels: return "c3h_voxelize: leaf size too small for int32 voxel indices";
+    case c3h::kVhCells: return "normals: more than 2^27 search cells";
+    default: return "vosch frames: a frame has more rows than row_cap";
+  }
+}
+
+// The nb frames of a batch through the batched voxel head (voxelize.hip vh_*): every frame's
+// status, info, VfHostFrame and prefixes as nb front_head calls leave them, with two host
+// synchronisations for the batch -- the bounds of the frames, then their voxel counts.  The
+// centroids and voxel keys of all frames are runs of one sort over the concatenated points; the
+// context's single-frame grid and voxeliser state are not used (vh_* buffers), only, at dim 137,
+// the extract's own buffers.  d_rows: the slot of the batch's first frame.
+int head_batch(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int nb, int on_device, float leaf, float z_limit,
+               const c3h_vosch_params* p, int dim, int64_t row_cap, float* d_rows, const FrontParams& q,
+               c3h::VfTable* ht, c3h::VfHostFrame* ff, c3h_frame_info* info) {
+  if (!ctx->vh_host) HIPCHK(hipHostMalloc(&ctx->vh_host, sizeof(c3h_ctx::VhHost)));
+  c3h_ctx::VhHost* const hh = ctx->vh_host;
+  ENSURE(ctx->vh_tab, 2);
+  ENSURE(ctx->vh_rec, c3h::kVfMaxFrames);
+  ENSURE(ctx->vh_vord, c3h::kVfMaxFrames + 1);
+  // ---- the bounds of every frame whose arguments pass
+  c3h::VhTable& ta = hh->tab[0];
+  memset(&ta, 0, sizeof(ta));
+  ta.nf = nb;
+  ta.leaf = leaf;
+  ta.inv_leaf = 1.0f / leaf;  // c3h_voxelize's
+  ta.z_limit = z_limit;
+  for (int j = 0; j < nb; ++j) {
+    const bool ok = c3h::vh_args_reason(n[j], pts[j] != nullptr) == c3h::kVhGood;
+    ta.ppre[j + 1] = ta.ppre[j] + (ok ? n[j] : 0);
+    hh->init[j] = hh->back[j] = c3h::vh_rec_init();
+  }
+  const int64_t ptot0 = ta.ppre[nb];
+  for (int j = 0; j < nb; ++j) {
+    if (ta.ppre[j + 1] == ta.ppre[j]) continue;
+    if (on_device) {
+      ta.fr[j].pts = reinterpret_cast<const float4*>(pts[j]);
+    } else {  // staged where the front reads it
+      HIPCHK(hipMemcpyAsync(ctx->vf_pts.p + ta.ppre[j], pts[j], (size_t)n[j] * 16, hipMemcpyHostToDevice, ctx->stream));
+      ta.fr[j].pts = ctx->vf_pts.p + ta.ppre[j];
+    }
+  }
+  if (ptot0 > 0) {
+    HIPCHK(hipMemcpyAsync(ctx->vh_rec.p, hh->init, (size_t)nb * sizeof(c3h::VhRec), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->vh_tab.p, &ta, sizeof(ta), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(c3h::launch_vh_bounds(ctx->vh_tab.p, ptot0, ctx->vh_rec.p, ctx->stream));
+    HIPCHK(hipMemcpyAsync(hh->back, ctx->vh_rec.p, (size_t)nb * sizeof(c3h::VhRec), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  // ---- the host's decision per frame; the frames that go on, concatenated again
+  c3h::VhCall call{};
+  call.leaf = leaf;
+  call.radius = p->normals_radius;
+  call.rsd_dist = q.max_dist;
+  call.subdiv = p->grsd.subdiv;
+  for (int a = 0; a < 3; ++a) call.offset[a] = p->grsd.offset[a];
+  call.row_cap = row_cap;
+  c3h::VhTable& tb = hh->tab[1];
+  tb = ta;
+  int reason[c3h::kVfMaxFrames];
+  int64_t max_vox = 1;
+  for (int j = 0; j < nb; ++j) {
+    c3h::VfHostFrame& fr = ff[j];
+    fr = c3h::VfHostFrame{};
+    c3h::VhFrameGeom gm;
+    reason[j] = c3h::vh_frame_decide(n[j], pts[j] != nullptr, hh->back[j], call, &gm);
+    tb.fr[j] = c3h::VhFrame{};
+    if (reason[j] == c3h::kVhGood) {
+      fr.gi.leaf = leaf;
+      fr.gi.inv_leaf = 1.0f / leaf;
+      for (int a = 0; a < 3; ++a) {
+        fr.gi.min_b[a] = gm.min_b[a];
+        fr.gi.max_b[a] = gm.max_b[a];
+        fr.gi.div_b[a] = gm.div_b[a];
+        fr.sb[a] = gm.sb[a];
+        fr.off[a] = p->grsd.subdiv > 0 ? p->grsd.offset[a] : 0;
+        tb.fr[j].mn[a] = gm.min_b[a];
+        tb.fr[j].dv[a] = gm.div_b[a];
+      }
+      fr.gi.n_valid = gm.n_valid;
+      fr.g = gm.g;
+      fr.g2 = gm.g2;
+      fr.pts = ta.fr[j].pts;
+      fr.n = n[j];
+      fr.z_limit = z_limit;
+      fr.H = gm.H;
+      fr.inv_s = gm.inv_s;
+      fr.rows = d_rows + (size_t)j * row_cap * dim;
+      tb.fr[j].pts = fr.pts;
+      max_vox = std::max(max_vox, gm.nvox);
+    } else {
+      ctx->err = head_reason(reason[j]);
+    }
+    tb.ppre[j + 1] = tb.ppre[j] + fr.n;
+  }
+  // ---- keys, the sort, the runs, the emit
+  const int64_t ptot = tb.ppre[nb];
+  if (ptot > 0) {
+    c3h::VfKey key{};
+    if (c3h::vh_key(max_vox, nb, ptot, &key) != c3h::kVfOk)
+      return fail(ctx, C3H_ERR_RANGE, "vosch frames: the batch does not fit the voxel sort key");
+    tb.voxel_bits = key.cell_bits;
+    ENSURE(ctx->vf_keys, ptot);  // (a 64-bit word per key: the front's own sorts find the buffers large enough)
+    ENSURE(ctx->vf_keys2, ptot);
+    ENSURE(ctx->vf_idx, ptot);
+    ENSURE(ctx->vf_idx2, ptot);
+    ENSURE(ctx->vh_head, ptot);
+    ENSURE(ctx->vh_ord, ptot);
+    ENSURE(ctx->vh_sums, c3h::scan_blocks(ptot));
+    c3h::VhSortBufs sb{ctx->vf_keys.p, ctx->vf_keys2.p, ctx->vf_idx.p,  ctx->vf_idx2.p, ctx->vh_head.p,
+                       ctx->vh_sums.p, ctx->vh_ord.p,   ctx->vh_vord.p, nullptr,        0};
+    HIPCHK(c3h::launch_vh_voxels(ctx->vh_tab.p + 1, nb, key, ptot, sb, ctx->vf_cent.p, ctx->vf_vkeys.p, ctx->vh_rec.p,
+                                 ctx->stream));
+    ENSURE(ctx->vf_tmp, std::max<size_t>(sb.tmp_bytes, 1));
+    sb.tmp = ctx->vf_tmp.p;
+    sb.tmp_bytes = ctx->vf_tmp.n;
+    HIPCHK(hipMemcpyAsync(ctx->vh_tab.p + 1, &tb, sizeof(tb), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(c3h::launch_vh_voxels(ctx->vh_tab.p + 1, nb, key, ptot, sb, ctx->vf_cent.p, ctx->vf_vkeys.p, ctx->vh_rec.p,
+                                 ctx->stream));
+    HIPCHK(hipMemcpyAsync(hh->back, ctx->vh_rec.p, (size_t)nb * sizeof(c3h::VhRec), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  // ---- the frames' centroids and voxel keys (runs' ordinals: frame after frame), off-cell records
+  c3h::VhOffPre opre{};
+  int64_t vall = 0;
+  for (int j = 0; j < nb; ++j) {
+    c3h::VfHostFrame& fr = ff[j];
+    opre.v[j + 1] = opre.v[j];
+    if (reason[j] != c3h::kVhGood) continue;
+    const int64_t n_occ = hh->back[j].n_occ;
+    fr.gi.n_occ = n_occ;
+    fr.nc = fr.H > 0 ? n_occ : 0;
+    fr.cent = ctx->vf_cent.p + vall;
+    fr.vkeys = ctx->vf_vkeys.p + vall;
+    fr.layout = nullptr;
+    vall += n_occ;
+    if (dim == 137 && fr.H > 0) opre.v[j + 1] += hh->back[j].n_off;
+  }
+  if (opre.v[nb] > 0) {
+    ENSURE(ctx->vh_offcell, (size_t)opre.v[nb] * 8);
+    HIPCHK(c3h::launch_vh_offcell(ctx->vh_tab.p + 1, nb, ctx->vh_vord.p, vall, ctx->vf_cent.p, ctx->vf_vkeys.p, opre,
+                                  ctx->vh_rec.p, ctx->vh_offcell.p, ctx->stream));
+  }
+  if (dim == 137 && vall > 0) {  // the grid of one frame at a time: zero but for the words of the frame in hand
+    if (ctx->vh_grid.n < (size_t)max_vox) {
+      ENSURE(ctx->vh_grid, max_vox);
+      HIPCHK(hipMemsetAsync(ctx->vh_grid.p, 0, ctx->vh_grid.n * 4, ctx->stream));
+    }
+  }
+  for (int j = 0; j < nb; ++j) {
+    c3h::VfHostFrame& fr = ff[j];
+    int st = c3h::vh_status(reason[j]);
+    if (st == C3H_OK && dim == 137 && fr.H > 0) {
+      // the C3 columns by the single-frame extract on the head's grid: the frame's words in, out again
+      HIPCHK(c3h::launch_vh_grid_words(fr.cent, fr.vkeys, fr.nc, ctx->vh_grid.p, 1, ctx->stream));
+      ctx->info = fr.gi;
+      ctx->have_grid = true;
+      ctx->grid_ptr = ctx->vh_grid.p;
+      c3h::VoxelExtras vx;
+      vx.offcell = ctx->vh_offcell.p + 8 * opre.v[j];
+      vx.n_offcell = opre.v[j + 1] - opre.v[j];
+      st = c3_cols(ctx, &p->grsd, p->thr, p->color_mode, fr.H, fr.rows, vx);
+      ctx->have_grid = false;
+      ctx->have_feat = false;
+      ctx->grid_ptr = nullptr;
+      const hipError_t e = c3h::launch_vh_grid_words(fr.cent, fr.vkeys, fr.nc, ctx->vh_grid.p, 0, ctx->stream);
+      if (e != hipSuccess) {
+        c3h::DevBuf<uint32_t> drop(std::move(ctx->vh_grid));  // not known to be zero any more
+        return c3h::hip_fail(ctx, "launch_vh_grid_words", e);
+      }
+      if (st < 0) {  // no centroid and no row of it goes on (its points are in the sort already: normals only)
+        fr.H = 0;
+        fr.nc = 0;
+        fr.rows = nullptr;
+      }
+    }
+    c3h_frame_info& fi = info[j];
+    memset(&fi, 0, sizeof(fi));
+    fi.status = st;
+    if (st >= 0) {
+      for (int a = 0; a < 3; ++a) {
+        fi.div_b[a] = fr.gi.div_b[a];
+        fi.min_b[a] = fr.gi.min_b[a];
+        fi.subdiv_b[a] = fr.sb[a];
+      }
+      fi.n_valid = fr.gi.n_valid;
+      fi.n_occ = fr.gi.n_occ;
+      fi.n_moved = fr.H > 0 ? (int32_t)hh->back[j].n_off : 0;
+    }
+    push_prefixes(ht, j, fr);
+  }
   return C3H_OK;
 }
 
@@ -312,6 +520,18 @@ int vosch_front(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t
   HIPCHK(hipSetDevice(ctx->device));
   const int B = std::max(1, std::min(ctx->nbatch, c3h::kVfMaxFrames));
   ctx->vf_nframes = 0;
+  if (ctx->vosch_head == 1) {  // the head has no single-frame grid to leave: none is held from here on
+    ctx->have_grid = false;
+    ctx->table_valid = false;
+    ctx->vcent_valid = false;
+    ctx->normals_valid = false;
+    ctx->rsd_n = 0;
+    ctx->grid_ptr = nullptr;
+    ctx->have_feat = false;
+    ctx->feat_listed = false;
+    ctx->g_valid = false;
+    ctx->rows_valid = false;
+  }
   ctx->vf_n.assign(n, n + nframes);
   ctx->vf_status.assign((size_t)nframes, 0);
   ctx->vf_ppre.assign((size_t)nframes + 1, 0);
@@ -336,28 +556,35 @@ int vosch_front(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t
     if (!on_device) ENSURE(ctx->vf_pts, upper);
     ENSURE(ctx->vf_cent, upper);
     ENSURE(ctx->vf_vkeys, upper);
+    if (ctx->vosch_head == 1) {
+      rc = head_batch(ctx, pts + b0, n + b0, nb, on_device, leaf, z_limit, p, dim, row_cap,
+                      d_rows + (size_t)b0 * row_cap * dim, q, ht, ff.data(), info + b0);
+      if (rc != C3H_OK) return rc;
+    }
     for (int j = 0; j < nb; ++j) {
       const int i = b0 + j;
-      c3h::VfHostFrame& fr = ff[(size_t)j];
-      fr = c3h::VfHostFrame{};
-      c3h_frame_info& fi = info[i];
-      memset(&fi, 0, sizeof(fi));
-      const int st = front_head(ctx, pts[i], n[i], on_device, leaf, z_limit, p, dim, row_cap, ht->ppre[j], ht->vpre[j],
-                                d_rows + (size_t)i * row_cap * dim, &fr);
-      fi.status = st;
-      ctx->vf_status[(size_t)i] = st;
-      if (st < 0) fr = c3h::VfHostFrame{};  // no points, cells, centroids or rows in the batch
-      else {
-        for (int a = 0; a < 3; ++a) {
-          fi.div_b[a] = fr.gi.div_b[a];
-          fi.min_b[a] = fr.gi.min_b[a];
-          fi.subdiv_b[a] = fr.sb[a];
+      if (ctx->vosch_head != 1) {
+        c3h::VfHostFrame& fr = ff[(size_t)j];
+        fr = c3h::VfHostFrame{};
+        c3h_frame_info& fi = info[i];
+        memset(&fi, 0, sizeof(fi));
+        const int st = front_head(ctx, pts[i], n[i], on_device, leaf, z_limit, p, dim, row_cap, ht->ppre[j], ht->vpre[j],
+                                  d_rows + (size_t)i * row_cap * dim, &fr);
+        fi.status = st;
+        if (st < 0) fr = c3h::VfHostFrame{};  // no points, cells, centroids or rows in the batch
+        else {
+          for (int a = 0; a < 3; ++a) {
+            fi.div_b[a] = fr.gi.div_b[a];
+            fi.min_b[a] = fr.gi.min_b[a];
+            fi.subdiv_b[a] = fr.sb[a];
+          }
+          fi.n_valid = fr.gi.n_valid;
+          fi.n_occ = fr.gi.n_occ;
+          fi.n_moved = fr.H > 0 ? (int32_t)ctx->n_offcell : 0;
         }
-        fi.n_valid = fr.gi.n_valid;
-        fi.n_occ = fr.gi.n_occ;
-        fi.n_moved = fr.H > 0 ? (int32_t)ctx->n_offcell : 0;
+        push_prefixes(ht, j, fr);
       }
-      push_prefixes(ht, j, fr);
+      ctx->vf_status[(size_t)i] = info[i].status;
       if (nframes <= B) {
         ctx->vf_ppre[(size_t)i + 1] = ht->ppre[j + 1];
         ctx->vf_vpre[(size_t)i + 1] = ht->vpre[j + 1];
@@ -478,7 +705,7 @@ int c3h_extract_vosch(c3h_ctx* ctx, const c3h_grsd_params* p, const int32_t thr[
   int64_t H = 0;
   int rc = grsd_frames(ctx, p, 137, ctx->vf_rows, sb, &H);
   if (rc != C3H_OK) return rc;
-  rc = c3_cols(ctx, p, thr, color_mode, H, ctx->vf_rows.p);
+  rc = c3_cols(ctx, p, thr, color_mode, H, ctx->vf_rows.p, c3h::voxelize_extras(ctx));
   if (rc != C3H_OK) return rc;
   std::swap(ctx->feat, ctx->vf_rows);  // (extract_frames left the 117-wide rows in feat)
   ctx->feat_dim = 137;
@@ -492,6 +719,13 @@ int c3h_extract_vosch(c3h_ctx* ctx, const c3h_grsd_params* p, const int32_t thr[
 }
 
 // ---- a batch of frames ------------------------------------------------------------------------
+
+int c3h_set_vosch_head(c3h_ctx* ctx, int32_t head) {
+  if (!ctx || (head != 0 && head != 1)) return C3H_ERR_ARG;
+  QUIESCE(ctx);
+  ctx->vosch_head = head;
+  return C3H_OK;
+}
 
 int c3h_extract_vosch_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t nframes, int on_device,
                              float leaf, float z_limit, const c3h_vosch_params* p, int32_t dim, int64_t row_cap,

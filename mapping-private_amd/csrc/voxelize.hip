@@ -711,6 +711,66 @@ __global__ __launch_bounds__(kBlock) void voxs_heads_kernel(const uint32_t* __re
     head[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
 }
 
+// One voxel of a sorted voxeliser: the run of equal keys from sorted position i (its points in
+// input order, the sort being stable), summed as the oracle does -- fp32 sequential xyz, integer
+// colour -- into the colour word and the centroid sum * fl(1 / n) (Eigen 3.0: centroid / n ==
+// centroid * (1 / n)).  The single-frame sorted path and the batched head share it.
+struct VoxRun {
+  uint32_t cnt, word;
+  float c[3];
+};
+template <class K, class PointAt>
+__device__ __forceinline__ VoxRun voxs_run(const K* __restrict__ keys, int64_t i, int64_t nv, PointAt point_at) {
+  const K key = keys[i];
+  unsigned long long sr = 0, sg = 0, sb = 0;
+  float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+  uint32_t cnt = 0;
+  for (int64_t j = i; j < nv && keys[j] == key; ++j, ++cnt) {
+    const float4 p = point_at(j);
+    sx += p.x;
+    sy += p.y;
+    sz += p.z;
+    const uint32_t rgb = __float_as_uint(p.w);
+    sr += (rgb >> 16) & 0xffu;
+    sg += (rgb >> 8) & 0xffu;
+    sb += rgb & 0xffu;
+  }
+  VoxRun r;
+  r.cnt = cnt;
+  r.word = pcl_colour_word(sr, sg, sb, cnt);
+  const float rn = __fdiv_rn(1.0f, (float)cnt);
+  r.c[0] = __fmul_rn(sx, rn);
+  r.c[1] = __fmul_rn(sy, rn);
+  r.c[2] = __fmul_rn(sz, rn);
+  return r;
+}
+// the cell of a centroid, floor(c / leaf) per axis (PCL 1.0 getNeighborCentroidIndices; as
+// vox_centroid_kernel), and whether it differs from the voxel's own cell
+__device__ __forceinline__ bool voxs_moved(const float c[3], float leaf, const int own[3], int nb[3]) {
+  bool moved = false;
+#pragma unroll
+  for (int ax = 0; ax < 3; ++ax) {
+    nb[ax] = (int)floorf(__fdiv_rn(c[ax], leaf));
+    moved = moved || nb[ax] != own[ax];
+  }
+  return moved;
+}
+// the cell of linear voxel index v in a grid of dv cells from mn
+__device__ __forceinline__ void voxs_own_cell(uint32_t v, const int mn[3], const int dv[3], int own[3]) {
+  own[0] = mn[0] + (int)(v % (uint32_t)dv[0]);
+  own[1] = mn[1] + (int)(v / (uint32_t)dv[0] % (uint32_t)dv[1]);
+  own[2] = mn[2] + (int)(v / (uint32_t)dv[0] / (uint32_t)dv[1]);
+}
+// the off-cell record of voxel v whose centroid lies in cell nb
+__device__ __forceinline__ void voxs_offcell_record(int32_t* oc, uint32_t v, const int nb[3], const int mn[3]) {
+  oc[0] = (int32_t)v;
+  for (int ax = 0; ax < 3; ++ax) {
+    oc[1 + ax] = nb[ax] - mn[ax];
+    oc[4 + ax] = nb[ax] - mn[ax];
+  }
+  oc[7] = 0;
+}
+
 __global__ __launch_bounds__(kBlock) void voxs_emit_kernel(VoxArgs a, int3 mn, int3 dv, const uint32_t* __restrict__ keys,
                                                            const uint32_t* __restrict__ idx,
                                                            const uint32_t* __restrict__ head,
@@ -719,54 +779,24 @@ __global__ __launch_bounds__(kBlock) void voxs_emit_kernel(VoxArgs a, int3 mn, i
                                                            int32_t* __restrict__ offcell) {
   uint32_t* sl = a.lists + (size_t)a.par * a.lcap;
   uint32_t* tl = a.lists + (size_t)(2 + a.par) * a.lcap;
+  const int mnv[3] = {mn.x, mn.y, mn.z}, dvv[3] = {dv.x, dv.y, dv.z};
   uint32_t nocc = 0;
   for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < nv; i += (int64_t)gridDim.x * kBlock) {
     if (!head[i]) continue;
     const uint32_t key = keys[i];
     const uint32_t q = (uint32_t)ord[i];
-    unsigned long long sr = 0, sg = 0, sb = 0;
-    float sx = 0.0f, sy = 0.0f, sz = 0.0f;
-    uint32_t cnt = 0;
-    for (int64_t j = i; j < nv && keys[j] == key; ++j, ++cnt) {
-      const float4 p = a.pts[idx[j]];
-      sx += p.x;
-      sy += p.y;
-      sz += p.z;
-      const uint32_t rgb = __float_as_uint(p.w);
-      sr += (rgb >> 16) & 0xffu;
-      sg += (rgb >> 8) & 0xffu;
-      sb += rgb & 0xffu;
-    }
-    const uint32_t word = pcl_colour_word(sr, sg, sb, cnt);
-    a.grid[key] = word;
+    const VoxRun r = voxs_run(keys, i, nv, [&](int64_t j) { return a.pts[idx[j]]; });
+    a.grid[key] = r.word;
     sl[q] = key;
     tl[q] = key;
-    a.lcnt[q] = cnt;
-    counts[q] = cnt;
+    a.lcnt[q] = r.cnt;
+    counts[q] = r.cnt;
     ++nocc;
-    const float rn = __fdiv_rn(1.0f, (float)cnt);  // Eigen 3.0: centroid / n == centroid * (1 / n)
-    const float c[3] = {__fmul_rn(sx, rn), __fmul_rn(sy, rn), __fmul_rn(sz, rn)};
-    cent[q] = make_float4(c[0], c[1], c[2], __uint_as_float(word & 0x00ffffffu));
-    const int own[3] = {mn.x + (int)(key % (uint32_t)dv.x), mn.y + (int)(key / (uint32_t)dv.x % (uint32_t)dv.y),
-                        mn.z + (int)(key / (uint32_t)dv.x / (uint32_t)dv.y)};
-    const int mnv[3] = {mn.x, mn.y, mn.z};
-    int nb[3];
-    bool moved = false;
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) {
-      nb[ax] = (int)floorf(__fdiv_rn(c[ax], a.leaf));  // as vox_centroid_kernel
-      moved = moved || nb[ax] != own[ax];
-    }
-    if (moved) {
-      const uint32_t k = atomicAdd(a.cnt + kVcOff, 1u);
-      int32_t* oc = offcell + 8 * (int64_t)k;
-      oc[0] = (int32_t)key;
-      for (int ax = 0; ax < 3; ++ax) {
-        oc[1 + ax] = nb[ax] - mnv[ax];
-        oc[4 + ax] = nb[ax] - mnv[ax];
-      }
-      oc[7] = 0;
-    }
+    cent[q] = make_float4(r.c[0], r.c[1], r.c[2], __uint_as_float(r.word & 0x00ffffffu));
+    int own[3], nb[3];
+    voxs_own_cell(key, mnv, dvv, own);
+    if (voxs_moved(r.c, a.leaf, own, nb))
+      voxs_offcell_record(offcell + 8 * (int64_t)atomicAdd(a.cnt + kVcOff, 1u), key, nb, mnv);
   }
   nocc = wave_reduce(nocc, [](uint32_t u, uint32_t v) { return u + v; });
   if ((threadIdx.x & 63) == 0 && nocc) atomicAdd(a.cnt + kVcSlots + a.par, nocc);
@@ -868,6 +898,191 @@ int grid_for(int64_t n, int cap = 4096) {
   int64_t g = (n + kBlock - 1) / kBlock;
   if (g < 1) g = 1;
   return (int)(g > cap ? cap : g);
+}
+
+// ---- the batched voxel head of the VOSCH / GRSD front ---------------------------------
+// The sorted path above for every frame of a batch at once (c3h_extract_vosch_frames at head 1;
+// host arithmetic: vosch_frames.h).  The frames' points are concatenated by the prefix ppre of a
+// device table.
+//   vh_bounds   per frame the min / max cell, the valid points and the beyond flag: a block takes
+//               chunks of kVhChunk concatenated points, per frame in the chunk (found by the
+//               prefix; one frame but for the chunks on a frame's end) a wave reduction, an LDS
+//               one, then one atomic min / max / add of the block.  The host reads the records.
+//   vh_keys     frame << voxel_bits | linear voxel index of the point's cell from the frame's
+//               min_b, in a 64-bit word; the all-ones index for a dropped point.  Then one stable radix sort of
+//               (key, concatenated point index), vh_heads, the scans: a run's ordinal.
+//   vh_counts   the frames' ordinal prefix: frame f's points sort into [ppre[f], ppre[f + 1]).
+//   vh_emit     one thread per run: voxs_run, the centroid and voxel index at the run's ordinal,
+//               the frame's off-cell count.
+//   vh_offcell  (dim 137) the off-cell records, filed per frame once the host knows the counts.
+// No kernel writes past what the host sized by ptot (keys, idx, head, ord, cent, vkeys: one
+// element per point at most) or by the counts it read back (the off-cell records).
+constexpr int kVhChunk = kBlock * 8;
+
+__global__ __launch_bounds__(kBlock) void vh_bounds_kernel(const VhTable* __restrict__ T, int64_t ptot,
+                                                           VhRec* __restrict__ rec) {
+  __shared__ int32_t red[kBlock / 64][8];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const float inv = T->inv_leaf, z_limit = T->z_limit;
+  const int nf = T->nf;
+  const int64_t nchunks = (ptot + kVhChunk - 1) / kVhChunk;
+  for (int64_t ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+    const int64_t c0 = ch * kVhChunk, c1 = c0 + kVhChunk < ptot ? c0 + kVhChunk : ptot;
+    const int f0 = vf_frame_of(T->ppre, nf, c0), f1 = vf_frame_of(T->ppre, nf, c1 - 1);
+    for (int f = f0; f <= f1; ++f) {  // the same frames in every thread of the block
+      const int64_t p0 = T->ppre[f];
+      const int64_t lo = c0 > p0 ? c0 : p0, hi = c1 < T->ppre[f + 1] ? c1 : T->ppre[f + 1];
+      if (hi <= lo) continue;
+      const float4* __restrict__ pts = T->fr[f].pts;
+      int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN};
+      int nvalid = 0, beyond = 0;
+      for (int64_t i = lo + threadIdx.x; i < hi; i += kBlock) {
+        const float4 p = pts[i - p0];
+        if (!point_valid(p, z_limit)) continue;
+        int c[3];
+        float m;
+        if (!point_cell(inv, p, c, &m)) {
+          beyond = 1;
+          continue;
+        }
+        ++nvalid;
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) {
+          mn[ax] = min(mn[ax], c[ax]);
+          mx[ax] = max(mx[ax], c[ax]);
+        }
+      }
+#pragma unroll
+      for (int ax = 0; ax < 3; ++ax) {
+        mn[ax] = wave_reduce(mn[ax], [](int u, int v) { return min(u, v); });
+        mx[ax] = wave_reduce(mx[ax], [](int u, int v) { return max(u, v); });
+      }
+      nvalid = wave_reduce(nvalid, [](int u, int v) { return u + v; });
+      beyond = wave_reduce(beyond, [](int u, int v) { return u | v; });
+      __syncthreads();  // the previous frame's partials are read
+      if (lane == 0) {
+        for (int ax = 0; ax < 3; ++ax) {
+          red[wid][ax] = mn[ax];
+          red[wid][3 + ax] = mx[ax];
+        }
+        red[wid][6] = nvalid;
+        red[wid][7] = beyond;
+      }
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        for (int w = 1; w < kBlock / 64; ++w) {
+          for (int ax = 0; ax < 3; ++ax) {
+            mn[ax] = min(mn[ax], red[w][ax]);
+            mx[ax] = max(mx[ax], red[w][3 + ax]);
+          }
+          nvalid += red[w][6];
+          beyond |= red[w][7];
+        }
+        VhRec* r = rec + f;
+        if (nvalid > 0) {
+          for (int ax = 0; ax < 3; ++ax) {
+            atomicMin(&r->mn[ax], mn[ax]);
+            atomicMax(&r->mx[ax], mx[ax]);
+          }
+          atomicAdd(&r->n_valid, (unsigned long long)nvalid);
+        }
+        if (beyond) atomicOr(&r->beyond, 1u);
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void vh_keys_kernel(const VhTable* __restrict__ T, int64_t ptot,
+                                                         uint64_t* __restrict__ keys, uint32_t* __restrict__ idx) {
+  const int bits = T->voxel_bits;
+  for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < ptot; i += (int64_t)gridDim.x * kBlock) {
+    const int f = vf_frame_of(T->ppre, T->nf, i);
+    const VhFrame& fr = T->fr[f];
+    const float4 p = fr.pts[i - T->ppre[f]];
+    int c[3];
+    float m;
+    uint64_t v = vf_no_cell(bits);
+    if (point_valid(p, T->z_limit) && point_cell(T->inv_leaf, p, c, &m)) {
+      const uint32_t o0 = (uint32_t)(c[0] - fr.mn[0]), o1 = (uint32_t)(c[1] - fr.mn[1]), o2 = (uint32_t)(c[2] - fr.mn[2]);
+      if (o0 < (uint32_t)fr.dv[0] && o1 < (uint32_t)fr.dv[1] && o2 < (uint32_t)fr.dv[2])  // bounds of the same points
+        v = o0 + (uint32_t)fr.dv[0] * (o1 + (uint32_t)fr.dv[1] * o2);
+    }
+    keys[i] = vf_make_key(f, v, bits);
+    idx[i] = (uint32_t)i;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void vh_heads_kernel(const uint64_t* __restrict__ keys, int bits, int64_t ptot,
+                                                          uint32_t* __restrict__ head) {
+  for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < ptot; i += (int64_t)gridDim.x * kBlock) {
+    const uint64_t k = keys[i];
+    head[i] = (vf_key_cell(k, bits) != vf_no_cell(bits) && (i == 0 || keys[i - 1] != k)) ? 1u : 0u;
+  }
+}
+
+// vord[f]: the runs before frame f's first sorted position; vord[nf]: all of them
+__global__ void vh_counts_kernel(const VhTable* __restrict__ T, int64_t ptot, const uint32_t* __restrict__ head,
+                                 const int32_t* __restrict__ ord, int64_t* __restrict__ vord, VhRec* __restrict__ rec) {
+  const int f = threadIdx.x;
+  if (f > T->nf) return;
+  const int64_t total = (int64_t)(uint32_t)ord[ptot - 1] + head[ptot - 1];
+  auto at = [&](int64_t p) { return p < ptot ? (int64_t)(uint32_t)ord[p] : total; };
+  const int64_t a = at(T->ppre[f]);
+  vord[f] = a;
+  if (f < T->nf) rec[f].n_occ = (uint32_t)(at(T->ppre[f + 1]) - a);
+}
+
+__global__ __launch_bounds__(kBlock) void vh_emit_kernel(const VhTable* __restrict__ T, int64_t ptot,
+                                                         const uint64_t* __restrict__ keys, const uint32_t* __restrict__ idx,
+                                                         const uint32_t* __restrict__ head,
+                                                         const int32_t* __restrict__ ord, float4* __restrict__ cent,
+                                                         int32_t* __restrict__ vkeys, VhRec* __restrict__ rec) {
+  const int bits = T->voxel_bits;
+  const float leaf = T->leaf;
+  for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < ptot; i += (int64_t)gridDim.x * kBlock) {
+    if (!head[i]) continue;
+    const uint64_t key = keys[i];
+    const int f = vf_key_frame(key, bits);
+    if (f < 0 || f >= T->nf) continue;
+    const VhFrame& fr = T->fr[f];
+    const uint32_t v = (uint32_t)vf_key_cell(key, bits);
+    const int64_t p0 = T->ppre[f];
+    const float4* __restrict__ pts = fr.pts;
+    const VoxRun r = voxs_run(keys, i, ptot, [&](int64_t j) { return pts[idx[j] - p0]; });
+    const int64_t q = (int64_t)(uint32_t)ord[i];
+    cent[q] = make_float4(r.c[0], r.c[1], r.c[2], __uint_as_float(r.word & 0x00ffffffu));
+    vkeys[q] = (int32_t)v;
+    int own[3], nb[3];
+    voxs_own_cell(v, fr.mn, fr.dv, own);
+    if (voxs_moved(r.c, leaf, own, nb)) atomicAdd(&rec[f].n_off, 1u);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void vh_offcell_kernel(const VhTable* __restrict__ T, int nf,
+                                                            const int64_t* __restrict__ vord, int64_t vtot,
+                                                            const float4* __restrict__ cent,
+                                                            const int32_t* __restrict__ vkeys, VhOffPre opre,
+                                                            VhRec* __restrict__ rec, int32_t* __restrict__ offcell) {
+  const float leaf = T->leaf;
+  for (int64_t q = blockIdx.x * (int64_t)kBlock + threadIdx.x; q < vtot; q += (int64_t)gridDim.x * kBlock) {
+    const int f = vf_frame_of(vord, nf, q);
+    const VhFrame& fr = T->fr[f];
+    const float4 c4 = cent[q];
+    const float c[3] = {c4.x, c4.y, c4.z};
+    const uint32_t v = (uint32_t)vkeys[q];
+    int own[3], nb[3];
+    voxs_own_cell(v, fr.mn, fr.dv, own);
+    if (!voxs_moved(c, leaf, own, nb)) continue;
+    const int64_t k = (int64_t)atomicAdd(&rec[f].ocur, 1u);
+    if (k < opre.v[f + 1] - opre.v[f]) voxs_offcell_record(offcell + 8 * (opre.v[f] + k), v, nb, fr.mn);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void vh_grid_words_kernel(const float4* __restrict__ cent,
+                                                               const int32_t* __restrict__ vkeys, int64_t nc,
+                                                               uint32_t* __restrict__ grid, int set) {
+  for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < nc; i += (int64_t)gridDim.x * kBlock)
+    grid[vkeys[i]] = set ? (kOcc | (__float_as_uint(cent[i].w) & 0x00ffffffu)) : 0u;
 }
 
 // ---- batched voxeliser (c3h_run_point_frames) ----------------------------------------
@@ -1670,6 +1885,48 @@ hipError_t launch_vox_sorted(const VoxArgs& a, const int mn[3], const int dv[3],
   voxs_emit_kernel<<<grid_for(nv, 8192), kBlock, 0, s>>>(a, m3, d3, b.keys2, b.idx2, b.head, b.ord, nv, counts, cent,
                                                           offcell);
   voxs_parts_kernel<<<(unsigned)((a.nblk + kBlock - 1) / kBlock), kBlock, 0, s>>>(a);
+  return hipGetLastError();
+}
+
+hipError_t launch_vh_bounds(const VhTable* d_tab, int64_t ptot, VhRec* rec, hipStream_t s) {
+  if (ptot <= 0) return hipSuccess;
+  vh_bounds_kernel<<<grid_for((ptot + kVhChunk - 1) / kVhChunk * kBlock, 2048), kBlock, 0, s>>>(d_tab, ptot, rec);
+  return hipGetLastError();
+}
+
+hipError_t launch_vh_voxels(const VhTable* d_tab, int nf, const VfKey& key, int64_t ptot, VhSortBufs& b, float4* cent,
+                            int32_t* vkeys, VhRec* rec, hipStream_t s) {
+  static_assert(kVfMaxFrames + 1 <= 128, "vh_counts_kernel: one thread per prefix entry");
+  if (nf < 1 || nf > kVfMaxFrames) return hipErrorInvalidValue;
+  if (!b.tmp)  // size query
+    return rocprim::radix_sort_pairs(nullptr, b.tmp_bytes, b.keys, b.keys2, b.idx, b.idx2, (size_t)std::max<int64_t>(ptot, 1),
+                                     0, key.bits, s);
+  if (ptot <= 0) return hipSuccess;
+  vh_keys_kernel<<<grid_for(ptot, 8192), kBlock, 0, s>>>(d_tab, ptot, b.keys, b.idx);
+  size_t tb = b.tmp_bytes;
+  hipError_t e = rocprim::radix_sort_pairs(b.tmp, tb, b.keys, b.keys2, b.idx, b.idx2, (size_t)ptot, 0, key.bits, s);
+  if (e != hipSuccess) return e;
+  vh_heads_kernel<<<grid_for(ptot, 8192), kBlock, 0, s>>>(b.keys2, key.cell_bits, ptot, b.head);
+  const int64_t nb = scan_blocks(ptot);
+  scan_count_kernel<false><<<(unsigned)nb, kBlock, 0, s>>>(b.head, ptot, b.block_sums);
+  scan_sums_kernel<<<1, kBlock, 0, s>>>(b.block_sums, nb);
+  scan_write_kernel<false><<<(unsigned)nb, kBlock, 0, s>>>(b.head, ptot, b.block_sums, b.ord);
+  vh_counts_kernel<<<1, 128, 0, s>>>(d_tab, ptot, b.head, b.ord, b.vord, rec);
+  vh_emit_kernel<<<grid_for(ptot, 8192), kBlock, 0, s>>>(d_tab, ptot, b.keys2, b.idx2, b.head, b.ord, cent, vkeys, rec);
+  return hipGetLastError();
+}
+
+hipError_t launch_vh_offcell(const VhTable* d_tab, int nf, const int64_t* vord, int64_t vtot, const float4* cent,
+                             const int32_t* vkeys, const VhOffPre& opre, VhRec* rec, int32_t* offcell, hipStream_t s) {
+  if (vtot <= 0) return hipSuccess;
+  vh_offcell_kernel<<<grid_for(vtot, 8192), kBlock, 0, s>>>(d_tab, nf, vord, vtot, cent, vkeys, opre, rec, offcell);
+  return hipGetLastError();
+}
+
+hipError_t launch_vh_grid_words(const float4* cent, const int32_t* vkeys, int64_t nc, uint32_t* grid, int set,
+                                hipStream_t s) {
+  if (nc <= 0) return hipSuccess;
+  vh_grid_words_kernel<<<grid_for(nc, 8192), kBlock, 0, s>>>(cent, vkeys, nc, grid, set);
   return hipGetLastError();
 }
 

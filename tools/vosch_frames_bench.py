@@ -13,7 +13,12 @@ with removeOverlap ("multi"), D = 100, box 2^3 -- detect_object_vosch_multi.cpp'
 After a warm-up of both routes they alternate --reps times in one process, timed on the host
 clock around a device synchronisation.  Pass: the batched call is shorter than the loop in every
 alternation by more than the loop's own spread (max - min).  --route loop runs the loop alone (a
-library without the batched entry, e.g. the parent commit's through C3HLAC_LIB).  A stage pass
+library without the batched entry, e.g. the parent commit's through C3HLAC_LIB).
+--head 0 | 1 selects the batched call's head (c3h_set_vosch_head: 0 c3h_voxelize per frame, 1 the
+batched voxel head; without --head the library's default runs and the setter is not called, so a
+library without it can be timed).  --head both alternates the loop, the batched call at head 0 and
+the batched call at head 1 in the one process, compares the records of all three and adds
+"head_pass": head 1 is shorter than head 0 in every alternation by more than head 0's own spread.  A stage pass
 drains the device after each of the loop's calls (voxelize | normals with their grid | RSD + GRSD |
 C3 + rows: the granularity of the single-frame entry points, on the host clock); the kernels of
 either route are split further by running this tool under rocprofv3 --kernel-trace --stats.
@@ -43,6 +48,7 @@ def main():
     ap.add_argument("--reps", type=int, default=4)
     ap.add_argument("--searches", default="small,multi")
     ap.add_argument("--route", default="both", choices=["both", "loop"])
+    ap.add_argument("--head", default=None, choices=["0", "1", "both"], help="the batched call's head (c3h_set_vosch_head)")
     args = ap.parse_args()
     import torch
     import c3hlac
@@ -116,9 +122,11 @@ def main():
                                    d_out=d_loop)
             ctx.synchronize()
 
-        def batched():
+        def batched(head=None, out=None):
+            if head is not None:
+                ctx.set_vosch_head(head)
             ctx.run_vosch_point_frames(frames, LEAF, canvas, bench.BOX, thr, dim=DIM, thr=bench.THR, subdiv=SUBDIV,
-                                       normals_radius=RADIUS, rotate=False, d_out=d_batch)
+                                       normals_radius=RADIUS, rotate=False, d_out=d_batch if out is None else out)
             ctx.synchronize()
 
         def timed(fn):
@@ -127,20 +135,38 @@ def main():
             return (time.perf_counter() - t0) * 1e3
 
         loop()
-        t_l, t_b = [], []
+        t_l, t_b, t_h = [], [], {0: [], 1: []}
+        heads = (0, 1) if args.head == "both" else ()
+        one_head = int(args.head) if args.head in ("0", "1") else None
         if args.route == "both":
-            batched()
+            batched(one_head)
             torch.cuda.synchronize(dev)
             same = bool(torch.equal(d_loop, d_batch))
+            for h in heads:  # the warm-up of either head, and its records against the loop's
+                d_head = torch.zeros((nf, rec), dtype=torch.int64, device=dev)
+                torch.cuda.synchronize(dev)
+                batched(h, d_head)
+                torch.cuda.synchronize(dev)
+                same = same and bool(torch.equal(d_loop, d_head))
         for _ in range(args.reps):
             t_l.append(timed(loop))
-            if args.route == "both":
-                t_b.append(timed(batched))
+            if args.route == "both" and not heads:
+                t_b.append(timed(lambda: batched(one_head)))
+            for h in heads:
+                t_h[h].append(timed(lambda: batched(h)))
+        if heads:
+            t_b = t_h[1]
         spread = max(t_l) - min(t_l)
         out = {"setting": args.setting, "search": name, "M": M, "r": r, "rank": rank, "frames": nf,
                "points_per_frame": int(np.mean([len(c) for c in clouds])), "canvas_b": canvas,
                "rows_per_frame": int(np.mean([len(x) for x in rows])), "loop_ms": t_l, "loop_spread_ms": spread,
                "loop_stage_ms_total": stages}
+        if heads:
+            spread0 = max(t_h[0]) - min(t_h[0])
+            out.update({"head": "both", "batched_head0_ms": t_h[0], "batched_head1_ms": t_h[1], "head0_spread_ms": spread0,
+                        "head_pass": all(a - b > spread0 for a, b in zip(t_h[0], t_h[1]))})
+        elif one_head is not None:
+            out["head"] = one_head
         if args.route == "both":
             out.update({"batched_ms": t_b, "records_equal": same,
                         "ratio_loop_over_batched": [a / b for a, b in zip(t_l, t_b)],
