@@ -202,6 +202,15 @@ int c3h_get_feature_info(c3h_ctx* ctx, int32_t subdiv_out[3], int64_t* hist_num,
  * c3h_extract_vosch: extractVOSCH (:832-843): [GRSD-20 | C3-HLAC-117] = 137 floats per
  * subdivision (the C3 part as c3h_extract with variant 117, thr, color_mode), exist by
  * the setVOSCH rule; the next c3h_search uses them (search_setup with F = 137).
+ * c3h_extract_convosch: ConVOSCH, the rotation-variant member (setConVOSCH, search_new.h;
+ * example_GRSD_CCHLAC.cpp writes 20 + 981): [GRSD-20 | C3-HLAC-981] = 1001 floats per
+ * subdivision.  Same arguments and preconditions as c3h_extract_vosch.  Columns 0 .. 19 are
+ * c3h_extract_grsd's, columns 20 .. 1000 c3h_extract's at variant 981 with the same thr,
+ * color_mode, subdiv and offset (zero where exist is 0); exist by the same rule
+ * (C3H_EXIST_VOSCH: f20, f21); the next c3h_search uses them (search_setup with F = 1001).  The
+ * colour columns are always the f32 rows: with c3h_set_search_precision(1) fp16 applies to the
+ * search only.  The reference tree defines ConVOSCH no further than this composition; parity
+ * beyond it is unpinned, as for VOSCH.
  * The PCL algorithms are restated (PCL is not part of the reference tree); radius-search
  * ties are broken by point index. */
 typedef struct {
@@ -216,6 +225,8 @@ int c3h_extract_grsd(c3h_ctx* ctx, const c3h_grsd_params* p, int32_t subdiv_out[
 int c3h_get_rsd(c3h_ctx* ctx, float* radii, int32_t* types, int on_device);
 int c3h_extract_vosch(c3h_ctx* ctx, const c3h_grsd_params* p, const int32_t thr[3], int32_t color_mode,
                       int32_t subdiv_out[3], int64_t* hist_num);
+int c3h_extract_convosch(c3h_ctx* ctx, const c3h_grsd_params* p, const int32_t thr[3], int32_t color_mode,
+                         int32_t subdiv_out[3], int64_t* hist_num);
 /* SearchObj::setData(subdiv_b, feature) (search.cpp:539-658) with features computed
  * elsewhere (VOSCH / ConVOSCH / GRSD extractors, search_new.h:34-76, or stored C3-HLAC
  * rows): subdiv_b[0]*[1]*[2] rows of dim floats, row h = x + y*xn + z*xn*yn.  exist =
@@ -465,11 +476,12 @@ int c3h_stream_feature_frames(c3h_ctx* ctx, const float* const* d_feat, const in
                               const int32_t canvas_b[3], int32_t dim, int32_t exist_rule,
                               const int32_t range[3], int32_t exist_threshold, int32_t rotate,
                               c3h_det* d_out);
-/* Point clouds in, VOSCH / GRSD rows out, for a batch of frames: the per-frame work of
+/* Point clouds in, VOSCH / ConVOSCH / GRSD rows out, for a batch of frames: the per-frame work of
  * color_voxel_recognition_2's detect_object_vosch_multi.cpp ahead of its search -- limitPoint +
  * getVoxelGrid, computeNormal (grsd_colorCHLAC_tools.hpp:63-87), extractVOSCH (:832-843) or
  * extractGRSDSignature21 (:131-296) -- i.e. c3h_voxelize + c3h_compute_normals +
- * c3h_extract_vosch (dim 137) / c3h_extract_grsd (dim 20) for nframes clouds, frame i = pts[i]
+ * c3h_extract_vosch (dim 137) / c3h_extract_convosch (dim 1001) / c3h_extract_grsd (dim 20) for
+ * nframes clouds, frame i = pts[i]
  * (n[i] x 4 floats as c3h_voxelize takes them; device pointers with on_device = 1, which must
  * stay valid until the call's work is done, else host memory).
  * c3h_extract_vosch_frames: frame i's rows start at d_rows + i * row_cap * dim (device), row
@@ -491,12 +503,17 @@ int c3h_stream_feature_frames(c3h_ctx* ctx, const float* const* d_feat, const in
  *     frames' voxel counts: two per batch, whatever the number of frames.  Host clouds are
  *     staged once, straight into the batch's concatenation.  At dim 137 the C3-HLAC-117 extract
  *     still runs frame by frame, on a grid buffer of the head's own that holds one frame's
- *     words at a time, and writes columns 20 .. 136.  After such a call the context holds no
+ *     words at a time, and writes columns 20 .. 136.  At dim 1001 the C3-HLAC-981 columns of the
+ *     whole batch come from one sparse pass over the frames' sorted voxel lists (no dense grid,
+ *     no off-cell records, no per-frame launch; memory proportional to voxels and rows): a sort
+ *     that groups the voxels by row, then exact integer sums per row.  A frame the per-frame
+ *     extract refuses only for its dense tiling (more than 32,767 tile segments on an axis)
+ *     succeeds here; every other status is that of head 0.  After such a call the context holds no
  *     single-frame grid: until the next c3h_voxelize / c3h_set_grid, c3h_compute_normals,
- *     c3h_extract, c3h_extract_grsd, c3h_extract_vosch and c3h_get_grid_info return
+ *     c3h_extract, c3h_extract_grsd, c3h_extract_vosch, c3h_extract_convosch and c3h_get_grid_info return
  *     C3H_ERR_STATE.  The single-frame voxeliser's own buffers and bookkeeping are not touched.
  *   0: per frame, in turn, c3h_voxelize's voxeliser, the exact centroids, the leaf layout and
- *     (dim 137) the extract, with c3h_voxelize's host synchronisations per frame; the context
+ *     (dim 137, 1001) the extract, with c3h_voxelize's host synchronisations per frame; the context
  *     then holds the last good frame's grid.
  * Everything else runs
  * once per batch over the concatenated frames: one keys kernel, one stable radix sort of
@@ -510,12 +527,12 @@ typedef struct {
   c3h_grsd_params grsd;    /* subdiv, offset, rsd_radius, normalize */
   float normals_radius;    /* normals_radius_search (0.02) */
   float viewpoint[3];
-  int32_t thr[3];          /* the C3-HLAC-117 part; ignored at dim 20 */
+  int32_t thr[3];          /* the C3-HLAC part; ignored at dim 20 */
   int32_t color_mode;
 } c3h_vosch_params;
 int c3h_extract_vosch_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t nframes,
                              int on_device, float leaf, float z_limit, const c3h_vosch_params* p,
-                             int32_t dim /* 137 VOSCH | 20 GRSD */, int64_t row_cap, float* d_rows,
+                             int32_t dim /* 137 VOSCH | 1001 ConVOSCH | 20 GRSD */, int64_t row_cap, float* d_rows,
                              c3h_frame_info* info);
 /* The head of c3h_extract_vosch_frames and c3h_run_vosch_point_frames (and of the facade's
  * SearchVOSCH / SearchGRSD::searchBatch through them): 1 = the batched voxel head, 0 = the
@@ -523,8 +540,8 @@ int c3h_extract_vosch_frames(c3h_ctx* ctx, const float* const* pts, const int64_
 int c3h_set_vosch_head(c3h_ctx* ctx, int32_t head);
 /* The whole callback of detect_object_vosch_multi.cpp for a batch: the same front end writes
  * into rows the context owns (row_cap = the canvas_b product), then the body of
- * c3h_run_feature_frames searches them with the exist rule C3H_EXIST_VOSCH (dim 137) or
- * C3H_EXIST_GRSD (dim 20): setVOSCH / setGRSD + search() from fresh lists (search_new.h:34-76),
+ * c3h_run_feature_frames searches them with the exist rule C3H_EXIST_VOSCH (dim 137, 1001) or
+ * C3H_EXIST_GRSD (dim 20): setVOSCH / setConVOSCH / setGRSD + search() from fresh lists (search_new.h:34-76),
  * frame i's M x rank records in d_out + i * M * rank (device).  A failed frame, or one whose
  * counts exceed canvas_b on an axis (C3H_ERR_RANGE), goes in with counts (0, 0, 0): it yields the
  * setRank state and keeps its negative status in info.  c3h_set_rank, c3h_set_batch,

@@ -236,6 +236,19 @@ class Context:
         self.hist_num, self.subdiv, self.variant = int(hn.value), tuple(int(x) for x in sb), 137
         return self.subdiv, self.hist_num
 
+    def extract_convosch(self, thr, subdiv=0, offset=(0, 0, 0), rsd_radius=0.01, normalize=False,
+                         color_mode=COLOR_C3_DOUBLE):
+        """c3h_extract_convosch: [GRSD-20 | C3-HLAC-981] rows of 1001 floats, after voxelize and
+        compute_normals as extract_vosch; the next search uses them (search_setup with F = 1001)."""
+        sb = (C.c_int32 * 3)()
+        hn = C.c_int64()
+        p = self._grsd_params(subdiv, offset, rsd_radius, normalize)
+        t = (C.c_int32 * 3)(*[int(x) for x in thr])
+        self._chk(self.lib.c3h_extract_convosch(self.h, C.byref(p), t, int(color_mode), sb, C.byref(hn)),
+                  "extract_convosch")
+        self.hist_num, self.subdiv, self.variant = int(hn.value), tuple(int(x) for x in sb), 1001
+        return self.subdiv, self.hist_num
+
     def set_score_engine(self, engine):
         """c3h_set_score_engine: 0 automatic, 1 VALU, 2 matrix cores (single-frame searches and
         the pipelined tick's score role; the scores are bit-identical)."""
@@ -411,8 +424,8 @@ class Context:
     def extract_vosch_frames(self, frames, leaf, dim=137, row_cap=None, thr=(0, 0, 0), subdiv=0, offset=(0, 0, 0),
                              rsd_radius=0.01, normalize=False, normals_radius=0.02, viewpoint=(0.0, 0.0, 0.0),
                              color_mode=COLOR_C3_DOUBLE, z_limit=float("inf"), rows=None):
-        """c3h_extract_vosch_frames: voxelize + compute_normals + extract_vosch (dim 137) or
-        extract_grsd (dim 20) for a batch of point clouds (a list as run_point_frames takes it, or
+        """c3h_extract_vosch_frames: voxelize + compute_normals + extract_vosch (dim 137),
+        extract_convosch (dim 1001) or extract_grsd (dim 20) for a batch of point clouds (a list as run_point_frames takes it, or
         a PointFrames).  rows: a contiguous float32 device tensor of len(frames) * row_cap * dim
         elements to write into (None: a new zeroed one; a caller's tensor must be complete on its
         stream before the call, as every device input of this class).  Returns (views, info): views[i] the
@@ -455,7 +468,7 @@ class Context:
                                rotate=True, d_out=None):
         """c3h_run_vosch_point_frames: point clouds in, detections out -- the front end of
         extract_vosch_frames into rows the context owns, then run_feature_frames' search with the
-        setVOSCH (dim 137) / setGRSD (dim 20) exist rule.  d_out = device pointer (int) or tensor of
+        setVOSCH (dim 137) / setConVOSCH (dim 1001) / setGRSD (dim 20) exist rule.  d_out = device pointer (int) or tensor of
         len(frames) * M * rank records.  Returns (modes, info); a frame with a negative status holds
         the setRank state."""
         if not isinstance(frames, PointFrames):

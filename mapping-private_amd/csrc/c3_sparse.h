@@ -1,0 +1,135 @@
+// c3_sparse.h -- host arithmetic of the sparse batched C3-HLAC-981 (c3_sparse.hip): the sort key
+// that groups a batch's voxels by output row, the chunk plan of a group, the subdivision of an
+// acting cell, and the inverse of the 981-bin layout as the table the accumulate phase reads.
+// Plain C++: the kernels (c3_sparse.hip), the launch code (capi_vosch.hip) and the host check
+// (tests/c3_sparse_check.cpp) include it.
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#include "vosch_frames.h"
+
+namespace c3h {
+
+constexpr int kC3sBlock = 256;          // threads of the accumulate workgroup
+constexpr int kC3sSlice = 128;          // voxels staged in LDS at a time
+constexpr int kC3sChunk = 1024;         // voxels of one workgroup's chunk: its sums stay in u32 registers
+constexpr int kC3sBins = 981;
+constexpr int kC3sBinsPerThread = (kC3sBins + kC3sBlock - 1) / kC3sBlock;
+constexpr int kC3sPos = 14;             // staged words per voxel: the centre and its 13 neighbours
+static_assert((uint64_t)kC3sChunk * 65025 < ((uint64_t)1 << 32), "a chunk's largest sum (255 * 255 per voxel) fits u32");
+static_assert(kC3sChunk % kC3sSlice == 0, "a chunk is whole slices");
+
+// ---- the sort key ------------------------------------------------------------------------------
+// key = hpre[frame] + subdivision: the row's ordinal in the batch, so keys order by (frame,
+// subdivision).  The value htot (one past the last row) marks a voxel that feeds no row; it sorts
+// last.  Sorted on c3s_key_bits(htot) bits of a 64-bit word.
+C3H_VF_HD inline uint64_t c3s_none(int64_t htot) { return (uint64_t)htot; }
+C3H_VF_HD inline uint64_t c3s_key(const int64_t* hpre, int frame, int64_t sub) { return (uint64_t)(hpre[frame] + sub); }
+inline int c3s_key_bits(int64_t htot) { return vf_bits((uint64_t)htot); }
+
+// ---- the chunk plan ----------------------------------------------------------------------------
+// A group (the voxels of one row, consecutive after the sort) of L voxels is cut into
+// c3s_chunks(L) chunks of at most kC3sChunk; chunk i holds c3s_chunk_len(L, i) voxels from
+// i * kC3sChunk.  A group of several chunks adds 64-bit partial sums.
+C3H_VF_HD inline int64_t c3s_chunks(int64_t L) { return (L + kC3sChunk - 1) / kC3sChunk; }
+C3H_VF_HD inline int64_t c3s_chunk_len(int64_t L, int64_t i) {
+  const int64_t r = L - i * kC3sChunk;
+  return r < 0 ? 0 : (r > kC3sChunk ? kC3sChunk : r);
+}
+// upper bounds known without reading the device: chunks (every group adds floor(L / chunk) full
+// ones and at most one more) and groups of several chunks (each holds more than a chunk)
+inline int64_t c3s_chunk_cap(int64_t vtot, int64_t htot) { return vtot / kC3sChunk + (vtot < htot ? vtot : htot); }
+inline int64_t c3s_multi_cap(int64_t vtot) { return vtot / (kC3sChunk + 1); }
+
+struct C3sChunk {
+  int64_t row;      // the batch ordinal of the output row
+  uint32_t start;   // first sorted position
+  uint32_t count;   // voxels, 1 .. kC3sChunk
+  int32_t multi;    // the ordinal of its group among those of several chunks, or -1
+  int32_t pad;
+};
+
+// ---- the subdivision of an acting cell ---------------------------------------------------------
+// c3_hlac.cpp:349-356 as offcell_contrib (c3hlac.hip) has it: a = floor(c / leaf) - min_b.  One
+// row: histogram 0 whatever the cell.  Else t = a - offset, skipped below 0; floorf((float)t *
+// inv_s) per axis, dropped from sb on.  Returns the subdivision or -1.
+C3H_VF_HD inline int64_t c3s_subdivision(const int a[3], const int off[3], const int sb[3], float inv_s, int hist1) {
+  if (hist1) return 0;
+  int ijk[3];
+  for (int ax = 0; ax < 3; ++ax) {
+    const int t = a[ax] - off[ax];
+    if (t < 0) return -1;
+    ijk[ax] = (int)floorf((float)t * inv_s);
+    if (ijk[ax] >= sb[ax]) return -1;
+  }
+  return ijk[0] + (int64_t)sb[0] * (ijk[1] + (int64_t)sb[1] * ijk[2]);
+}
+
+// relative coordinates of neighbour k (c3_hlac.cpp:177-202)
+C3H_VF_HD inline void c3s_rel(int k, int rel[3]) {
+  rel[0] = k < 9 ? k / 3 - 1 : (k < 12 ? k - 10 : -1);
+  rel[1] = k < 9 ? k % 3 - 1 : (k < 12 ? -1 : 0);
+  rel[2] = k < 9 ? -1 : 0;
+}
+
+// ---- the bins ------------------------------------------------------------------------------------
+// The closed form of the layout (bin981 / tri6 of c3hlac_dev.h)
+C3H_VF_HD constexpr int c3s_bin981(int k, int c, int n) {
+  return k <= 8 ? 6 + 78 * c + 9 * n + k : 60 + 78 * c + 4 * n + (k - 9);
+}
+C3H_VF_HD constexpr int c3s_tri6(int c, int n) { return 6 * c - c * (c - 1) / 2 + (n - c); }
+
+// A staged voxel word (centre or neighbour; 0 = absent): bytes 0 .. 5 the channel values a[0 .. 5],
+// bits 48 .. 53 the binarised beta[0 .. 5], bit 63 set.  A field of it is (word >> shift) & mask.
+// Every bin is the sum over the group's voxels of field A of the centre times field B of one
+// position (the centre again for the zero-order and auto-product bins).
+enum { kC3sFieldBeta = 6, kC3sFieldOne = 12 };  // fields 0 .. 5: a[c]; 6 .. 11: beta[c]; 12: the constant 1
+C3H_VF_HD constexpr int c3s_field_shift(int f) { return f < 6 ? 8 * f : (f < 12 ? 48 + (f - 6) : 63); }
+C3H_VF_HD constexpr uint32_t c3s_field_mask(int f) { return f < 6 ? 0xffu : 1u; }
+
+struct C3sBin {
+  int pos;     // 0: the centre; 1 + k: neighbour k
+  int fa, fb;  // the centre's field, the position's field
+};
+// the inverse of the layout: what bin i sums
+C3H_VF_HD constexpr C3sBin c3s_bin_desc(int i) {
+  const int type = i >= 495 ? 1 : 0;  // 1: the binarised half
+  const int j = type ? i - 495 : i;
+  const int fo = type ? kC3sFieldBeta : 0;
+  if (j < 6) return C3sBin{0, fo + j, kC3sFieldOne};
+  if (j < 474) {
+    const int c = (j - 6) / 78, r = (j - 6) % 78;
+    const int n = r < 54 ? r / 9 : (r - 54) / 4;
+    const int k = r < 54 ? r % 9 : 9 + (r - 54) % 4;
+    return C3sBin{1 + k, fo + c, fo + n};
+  }
+  if (!type) {  // 474 .. 494: the auto-product triangle a[c] * a[n], c <= n
+    int t = j - 474, c = 0;
+    while (t >= 6 - c) {
+      t -= 6 - c;
+      ++c;
+    }
+    return C3sBin{0, c, c + t};
+  }
+  const int t = j - 474;  // 969 .. 980: the twelve binarised channel pairs
+  if (t < 8) return C3sBin{0, kC3sFieldBeta + t / 4, kC3sFieldBeta + 2 + t % 4};
+  return C3sBin{0, kC3sFieldBeta + 2 + (t - 8) / 2, kC3sFieldBeta + 4 + (t - 8) % 2};
+}
+
+// The table of the accumulate phase, a word per bin:
+// pos | shift A << 4 | shift B << 10 | (mask A is 0xff) << 16 | (mask B is 0xff) << 17 | 1 << 18
+C3H_VF_HD constexpr uint32_t c3s_pack_bin(const C3sBin& b) {
+  return (uint32_t)b.pos | (uint32_t)c3s_field_shift(b.fa) << 4 | (uint32_t)c3s_field_shift(b.fb) << 10 |
+         (c3s_field_mask(b.fa) == 0xffu ? 1u << 16 : 0u) | (c3s_field_mask(b.fb) == 0xffu ? 1u << 17 : 0u) | 1u << 18;
+}
+struct C3sTable {
+  uint32_t v[kC3sBlock * kC3sBinsPerThread];  // 0 past bin 980: both masks 0
+};
+constexpr C3sTable c3s_make_table() {
+  C3sTable t{};
+  for (int i = 0; i < kC3sBins; ++i) t.v[i] = c3s_pack_bin(c3s_bin_desc(i));
+  return t;
+}
+
+}  // namespace c3h

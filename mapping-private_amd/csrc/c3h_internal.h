@@ -15,6 +15,7 @@
 #include "occ_sched.h"
 #include "pc2_layout.h"
 #include "vosch_frames.h"
+#include "c3_sparse.h"
 
 namespace c3h {
 
@@ -492,7 +493,24 @@ hipError_t launch_vf_rsd(const VfTable* d_tab, int64_t vtot, const float4* nrm, 
 hipError_t launch_vf_grsd(const VfTable* d_tab, int64_t vtot, hipStream_t s);
 hipError_t launch_vf_rows(const VfTable* d_tab, int64_t htot, const int32_t* trans, float norm, int dim, hipStream_t s);
 hipError_t launch_vf_vox_keys(const int32_t* layout, int64_t nvox, int64_t nc, int32_t* vkeys, hipStream_t s);
-hipError_t launch_vf_c3_cols(const float* c3, const int32_t* exist, int64_t H, float* rows, hipStream_t s);
+// columns 20 .. 20 + variant - 1 of rows of `stride` floats: the C3-HLAC rows c3, zeros where exist is 0
+hipError_t launch_vf_c3_cols(const float* c3, const int32_t* exist, int64_t H, int variant, int stride, float* rows,
+                             hipStream_t s);
+// The sparse batched C3-HLAC-981 (c3_sparse.hip): columns 20 .. 1000 of every row of the table's
+// frames (rows of dim floats) from their centroids and voxel keys; the table is on the device.
+// Sizes: c3_sparse.h.  tmp == nullptr: size query of the sort into *tmp_bytes.
+struct C3sBufs {
+  uint64_t *keys, *keys2;     // vtot
+  uint32_t *idx, *idx2;       // vtot
+  uint32_t* cnt;              // 2
+  C3sChunk* chunks;           // c3s_chunk_cap(vtot, htot)
+  int64_t* multi_row;         // c3s_multi_cap(vtot)
+  unsigned long long* acc;    // c3s_multi_cap(vtot) x 981
+  void* tmp;
+  size_t* tmp_bytes;
+};
+hipError_t launch_c3_sparse(const VfTable* d_tab, int64_t vtot, int64_t htot, const C3sBufs& b, const uint32_t* lut,
+                            const int32_t thr[3], int dim, hipStream_t s);
 // What the host knows of one frame of the front: the normals' half after its c3h_voxelize, the
 // GRSD half after its head (capi_vosch.hip fills a VfFrame from it)
 struct VfHostFrame {
@@ -772,6 +790,13 @@ struct c3h_ctx {
   c3h::DevBuf<int32_t> vh_ord, vh_offcell;
   c3h::DevBuf<int64_t> vh_vord;
   c3h::DevBuf<uint32_t> vh_grid;    // dim 137: one frame's words at a time, zero between frames
+  // dim 1001 at head 1: the sparse batched C3-HLAC-981 (c3_sparse.hip)
+  c3h::DevBuf<uint64_t> c3s_keys, c3s_keys2;
+  c3h::DevBuf<uint32_t> c3s_idx, c3s_idx2, c3s_cnt;
+  c3h::DevBuf<c3h::C3sChunk> c3s_chunks;
+  c3h::DevBuf<int64_t> c3s_multi_row;
+  c3h::DevBuf<unsigned long long> c3s_acc;
+  c3h::DevBuf<uint8_t> c3s_tmp;
   // voxeliser state (voxelize.hip): toroidal accumulators, entry / grid-word lists by
   // epoch parity, counters; the grid words the previous frame wrote are cleared by the next
   c3h::DevBuf<ulonglong2> vacc;

@@ -304,18 +304,6 @@ struct OffcellArgs {
   unsigned long long* acc64;
 };
 
-__device__ __forceinline__ void channels(uint32_t word, const uint32_t* lut, const int thr[3], int a[6], int beta[6]) {
-  const int v[3] = {(int)((word >> 16) & 0xff), (int)((word >> 8) & 0xff), (int)(word & 0xff)};
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
-    const uint32_t l = lut[v[ch]];
-    a[2 * ch] = (int)(l & 0xff);
-    a[2 * ch + 1] = (int)((l >> 8) & 0xff);
-    beta[2 * ch] = v[ch] > thr[ch] ? 1 : 0;
-    beta[2 * ch + 1] = 1 - beta[2 * ch];
-  }
-}
-
 // sign * (contribution of centre word `w` with subdivision cell `sc` and neighbour base `nb`)
 __device__ void offcell_contrib(const OffcellArgs& o, uint32_t w, const int sc[3], const int nb[3], long long sign) {
   int64_t h = 0;

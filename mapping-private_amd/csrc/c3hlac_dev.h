@@ -20,6 +20,20 @@ __device__ __forceinline__ int bin981(int k, int c, int n) {
 }
 __device__ __forceinline__ int tri6(int c, int n) { return 6 * c - c * (c - 1) / 2 + (n - c); }
 
+// the six channel values of a voxel word (the colour mode's LUT) and their binarisation
+// (shared by the off-cell passes of c3hlac.hip and the sparse pass of c3_sparse.hip)
+__device__ __forceinline__ void channels(uint32_t word, const uint32_t* lut, const int thr[3], int a[6], int beta[6]) {
+  const int v[3] = {(int)((word >> 16) & 0xff), (int)((word >> 8) & 0xff), (int)(word & 0xff)};
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    const uint32_t l = lut[v[ch]];
+    a[2 * ch] = (int)(l & 0xff);
+    a[2 * ch + 1] = (int)((l >> 8) & 0xff);
+    beta[2 * ch] = v[ch] > thr[ch] ? 1 : 0;
+    beta[2 * ch + 1] = 1 - beta[2 * ch];
+  }
+}
+
 // bin of accumulator (type, k, n, c); -1 when that product is not a feature bin
 __device__ __forceinline__ int bin_of(int type, int k, int n, int c) {
   if (k <= 12) return (type ? 495 : 0) + bin981(k, c, n);

@@ -4,8 +4,10 @@
 // c3h_run_vosch_point_frames and theirs).
 //
 // The head of a batch gives the front what only a voxeliser can: every frame's voxel grid
-// geometry, its exact centroids in leaf order and their voxel keys and, at dim 137, the
-// C3-HLAC-117 rows (extract_frames), whose columns go straight into the frame's output rows.
+// geometry, its exact centroids in leaf order and their voxel keys and, at dim 137 (at head 0 also
+// at dim 1001, ConVOSCH), the C3-HLAC rows (extract_frames), whose columns go straight into the
+// frame's output rows.  At dim 1001 the batched head leaves the colour columns to the front: one
+// sparse C3-HLAC-981 pass over the whole batch's voxel lists (c3_sparse.hip), launched by front_run.
 // c3h_set_vosch_head chooses it.  1 (head_batch): the batched voxel head of voxelize.hip (vh_*)
 // -- a bounds pass over the batch's concatenated points, the host's decision per frame
 // (vosch_frames.h), one sort whose runs are the voxels, a thread per run -- with two host
@@ -36,6 +38,9 @@ struct FrontParams {
   float max_dist;  // kStageGrsd: the RSD radius,
   float norm;      //   the factor of the rows
   int dim;         //   and their stride
+  // the batched head at dim 1001: columns 20 .. by the sparse C3-HLAC-981 (c3_sparse.hip)
+  const uint32_t* c3s_lut = nullptr;  // the colour mode's LUT, or nullptr: no such columns
+  int32_t c3s_thr[3] = {0, 0, 0};
 };
 
 // RSD radius: max(rsd_radius_search, voxel_size / 2 * sqrt(3)) (grsd_colorCHLAC_tools.hpp:172)
@@ -222,6 +227,24 @@ int front_run(c3h_ctx* ctx, c3h::VfTable* ht, const c3h::VfHostFrame* ff, int nb
     HIPCHK(c3h::launch_vf_grsd(ctx->vf_tab.p, vtot, ctx->stream));
     HIPCHK(c3h::launch_vf_rows(ctx->vf_tab.p, htot, ctx->vf_trans.p, q.norm, q.dim, ctx->stream));
   }
+  if (q.c3s_lut && htot > 0) {
+    ENSURE(ctx->c3s_keys, vtot);
+    ENSURE(ctx->c3s_keys2, vtot);
+    ENSURE(ctx->c3s_idx, vtot);
+    ENSURE(ctx->c3s_idx2, vtot);
+    ENSURE(ctx->c3s_cnt, 2);
+    ENSURE(ctx->c3s_chunks, c3h::c3s_chunk_cap(vtot, htot));
+    ENSURE(ctx->c3s_multi_row, c3h::c3s_multi_cap(vtot));
+    ENSURE(ctx->c3s_acc, (size_t)c3h::c3s_multi_cap(vtot) * c3h::kC3sBins);
+    size_t sort_bytes = 0;
+    c3h::C3sBufs b{ctx->c3s_keys.p, ctx->c3s_keys2.p, ctx->c3s_idx.p,       ctx->c3s_idx2.p, ctx->c3s_cnt.p,
+                   ctx->c3s_chunks.p, ctx->c3s_multi_row.p, ctx->c3s_acc.p, nullptr,         &sort_bytes};
+    HIPCHK(c3h::launch_c3_sparse(ctx->vf_tab.p, vtot, htot, b, q.c3s_lut, q.c3s_thr, q.dim, ctx->stream));
+    ENSURE(ctx->c3s_tmp, std::max<size_t>(sort_bytes, 1));
+    sort_bytes = ctx->c3s_tmp.n;
+    b.tmp = ctx->c3s_tmp.p;
+    HIPCHK(c3h::launch_c3_sparse(ctx->vf_tab.p, vtot, htot, b, q.c3s_lut, q.c3s_thr, q.dim, ctx->stream));
+  }
   return C3H_OK;
 }
 
@@ -229,11 +252,13 @@ int front_run(c3h_ctx* ctx, c3h::VfTable* ht, const c3h::VfHostFrame* ff, int nb
 float grsd_norm(const c3h_grsd_params* gp) { return gp->normalize ? (float)(20.0 / 26) : 1.0f; }
 
 // The C3 part of extractVOSCH (grsd_colorCHLAC_tools.hpp:832-843) on the grid of the last
-// c3h_voxelize: its C3-HLAC-117 rows (ctx->feat, ctx->exist) into columns 20 .. 136 of rows
-int c3_cols(c3h_ctx* ctx, const c3h_grsd_params* gp, const int32_t thr[3], int32_t color_mode, int64_t H, float* rows,
-            const c3h::VoxelExtras& vx) {
+// c3h_voxelize: its C3-HLAC rows of `variant` columns (ctx->feat, ctx->exist) into columns 20 ..
+// of rows of 20 + variant floats.  117: VOSCH.  981: ConVOSCH, always from the f32 rows (fp16
+// search precision applies to the search only: the extract's f16-row route is not taken here)
+int c3_cols(c3h_ctx* ctx, const c3h_grsd_params* gp, int variant, const int32_t thr[3], int32_t color_mode, int64_t H,
+            float* rows, const c3h::VoxelExtras& vx) {
   c3h_extract_params e{};
-  e.variant = 117;
+  e.variant = variant;
   for (int a = 0; a < 3; ++a) {
     e.thr[a] = thr[a];
     e.offset[a] = gp->offset[a];
@@ -243,10 +268,13 @@ int c3_cols(c3h_ctx* ctx, const c3h_grsd_params* gp, const int32_t thr[3], int32
   const uint32_t* g = ctx->grid_ptr;
   int32_t sb2[3];
   int64_t H2 = 0;
+  const bool prec16 = ctx->prec16;
+  ctx->prec16 = false;
   const int rc = c3h::extract_frames(ctx, &g, 1, &e, sb2, &H2, vx);
+  ctx->prec16 = prec16;
   if (rc != C3H_OK) return rc;
   if (H2 != H) return fail(ctx, C3H_ERR_STATE, "extract_vosch: GRSD / C3 subdivisions differ");
-  HIPCHK(c3h::launch_vf_c3_cols(ctx->feat.p, ctx->exist.p, H, rows, ctx->stream));
+  HIPCHK(c3h::launch_vf_c3_cols(ctx->feat.p, ctx->exist.p, H, variant, 20 + variant, rows, ctx->stream));
   return C3H_OK;
 }
 
@@ -304,7 +332,7 @@ int front_head(c3h_ctx* ctx, const float* pts, int64_t n, int on_device, float l
     HIPCHK(hipMemcpyAsync(ctx->vf_cent.p + v0, ctx->dsamp.p, (size_t)fr->nc * 16, hipMemcpyDeviceToDevice, ctx->stream));
     fr->cent = ctx->vf_cent.p + v0;
   }
-  if (dim == 137) return c3_cols(ctx, &p->grsd, p->thr, p->color_mode, fr->H, fr->rows, c3h::voxelize_extras(ctx));
+  if (dim != 20) return c3_cols(ctx, &p->grsd, dim - 20, p->thr, p->color_mode, fr->H, fr->rows, c3h::voxelize_extras(ctx));
   return C3H_OK;
 }
 
@@ -479,7 +507,7 @@ int head_batch(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int nb, 
       c3h::VoxelExtras vx;
       vx.offcell = ctx->vh_offcell.p + 8 * opre.v[j];
       vx.n_offcell = opre.v[j + 1] - opre.v[j];
-      st = c3_cols(ctx, &p->grsd, p->thr, p->color_mode, fr.H, fr.rows, vx);
+      st = c3_cols(ctx, &p->grsd, 117, p->thr, p->color_mode, fr.H, fr.rows, vx);
       ctx->have_grid = false;
       ctx->have_feat = false;
       ctx->grid_ptr = nullptr;
@@ -489,6 +517,19 @@ int head_batch(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int nb, 
         return c3h::hip_fail(ctx, "launch_vh_grid_words", e);
       }
       if (st < 0) {  // no centroid and no row of it goes on (its points are in the sort already: normals only)
+        fr.H = 0;
+        fr.nc = 0;
+        fr.rows = nullptr;
+      }
+    }
+    if (st == C3H_OK && dim == 1001) {
+      // the colour columns come from the front's sparse pass (front_run); what the per-frame
+      // extract refuses is refused here with its status
+      if (p->color_mode < C3H_COLOR_C3_FLOAT || p->color_mode > C3H_COLOR_CHLAC)
+        st = fail(ctx, C3H_ERR_ARG, "c3h_extract: variant must be 981 or 117, color_mode a C3H_COLOR_* value");
+      else if (fr.H > 0 && (p->thr[0] < 0 || p->thr[1] < 0 || p->thr[2] < 0))
+        st = fail(ctx, C3H_ERR_STATE, "extract_vosch: GRSD / C3 subdivisions differ");
+      if (st < 0) {
         fr.H = 0;
         fr.nc = 0;
         fr.rows = nullptr;
@@ -542,6 +583,10 @@ int vosch_front(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t
   q.max_dist = rsd_max_dist(&p->grsd, leaf);
   q.norm = grsd_norm(&p->grsd);
   q.dim = dim;
+  if (dim == 1001 && ctx->vosch_head == 1 && p->color_mode >= C3H_COLOR_C3_FLOAT && p->color_mode <= C3H_COLOR_CHLAC) {
+    q.c3s_lut = ctx->lut.p + 256 * p->color_mode;
+    for (int a = 0; a < 3; ++a) q.c3s_thr[a] = p->thr[a];
+  }
   std::vector<c3h::VfHostFrame> ff((size_t)B);
   for (int b0 = 0; b0 < nframes; b0 += B) {
     const int nb = std::min(B, nframes - b0);
@@ -600,7 +645,8 @@ int vosch_front(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t
 int front_args(c3h_ctx* ctx, const char* who, const float* const* pts, const int64_t* n, int32_t nframes, float leaf,
                const c3h_vosch_params* p, int32_t dim) {
   if (!ctx || !p || nframes < 0 || (nframes > 0 && (!pts || !n))) return C3H_ERR_ARG;
-  if (dim != 137 && dim != 20) return fail(ctx, C3H_ERR_ARG, std::string(who) + ": dim must be 137 (VOSCH) or 20 (GRSD)");
+  if (dim != 137 && dim != 1001 && dim != 20)
+    return fail(ctx, C3H_ERR_ARG, std::string(who) + ": dim must be 137 (VOSCH), 1001 (ConVOSCH) or 20 (GRSD)");
   if (!(leaf > 0) || !(p->normals_radius > 0)) return fail(ctx, C3H_ERR_ARG, std::string(who) + ": leaf and normals_radius must be > 0");
   return C3H_OK;
 }
@@ -694,21 +740,22 @@ int c3h_get_rsd(c3h_ctx* ctx, float* radii, int32_t* types, int on_device) {
   return (int)std::min<int64_t>(ctx->rsd_n, INT32_MAX);
 }
 
-// extractVOSCH (grsd_colorCHLAC_tools.hpp:832-843): [GRSD-20 | C3-HLAC-117] per subdivision
-int c3h_extract_vosch(c3h_ctx* ctx, const c3h_grsd_params* p, const int32_t thr[3], int32_t color_mode,
-                      int32_t subdiv_out[3], int64_t* hist_num) {
+// extractVOSCH (grsd_colorCHLAC_tools.hpp:832-843): [GRSD-20 | C3-HLAC-117] per subdivision;
+// ConVOSCH (example_GRSD_CCHLAC.cpp): [GRSD-20 | C3-HLAC-981]
+static int extract_vosch_rows(c3h_ctx* ctx, const c3h_grsd_params* p, int variant, const int32_t thr[3], int32_t color_mode,
+                              int32_t subdiv_out[3], int64_t* hist_num) {
   if (!ctx || !p || !thr) return C3H_ERR_ARG;
   QUIESCE(ctx);
   if (!ctx->have_grid || !ctx->table_valid) return fail(ctx, C3H_ERR_STATE, "extract_vosch: no c3h_voxelize grid");
   HIPCHK(hipSetDevice(ctx->device));
   int32_t sb[3];
   int64_t H = 0;
-  int rc = grsd_frames(ctx, p, 137, ctx->vf_rows, sb, &H);
+  int rc = grsd_frames(ctx, p, 20 + variant, ctx->vf_rows, sb, &H);
   if (rc != C3H_OK) return rc;
-  rc = c3_cols(ctx, p, thr, color_mode, H, ctx->vf_rows.p, c3h::voxelize_extras(ctx));
+  rc = c3_cols(ctx, p, variant, thr, color_mode, H, ctx->vf_rows.p, c3h::voxelize_extras(ctx));
   if (rc != C3H_OK) return rc;
-  std::swap(ctx->feat, ctx->vf_rows);  // (extract_frames left the 117-wide rows in feat)
-  ctx->feat_dim = 137;
+  std::swap(ctx->feat, ctx->vf_rows);  // (extract_frames left the C3-HLAC rows in feat)
+  ctx->feat_dim = 20 + variant;
   ctx->feat_sparse = false;
   ctx->g_valid = false;
   ctx->rows_valid = false;
@@ -716,6 +763,16 @@ int c3h_extract_vosch(c3h_ctx* ctx, const c3h_grsd_params* p, const int32_t thr[
   if (subdiv_out) memcpy(subdiv_out, sb, sizeof(sb));
   if (hist_num) *hist_num = H;
   return C3H_OK;
+}
+
+int c3h_extract_vosch(c3h_ctx* ctx, const c3h_grsd_params* p, const int32_t thr[3], int32_t color_mode,
+                      int32_t subdiv_out[3], int64_t* hist_num) {
+  return extract_vosch_rows(ctx, p, 117, thr, color_mode, subdiv_out, hist_num);
+}
+
+int c3h_extract_convosch(c3h_ctx* ctx, const c3h_grsd_params* p, const int32_t thr[3], int32_t color_mode,
+                         int32_t subdiv_out[3], int64_t* hist_num) {
+  return extract_vosch_rows(ctx, p, 981, thr, color_mode, subdiv_out, hist_num);
 }
 
 // ---- a batch of frames ------------------------------------------------------------------------
@@ -783,7 +840,7 @@ int c3h_run_vosch_point_frames(c3h_ctx* ctx, const float* const* pts, const int6
   }
   // the body of c3h_run_feature_frames: failed frames go in with counts (0, 0, 0) and yield the setRank state
   return c3h_run_feature_frames(ctx, feats.data(), nullptr, nframes, sbs.data(), canvas_b, dim,
-                                dim == 137 ? C3H_EXIST_VOSCH : C3H_EXIST_GRSD, range, exist_threshold, rotate, d_out);
+                                dim == 20 ? C3H_EXIST_GRSD : C3H_EXIST_VOSCH, range, exist_threshold, rotate, d_out);
 }
 
 int c3h_get_frame_normals(c3h_ctx* ctx, int32_t frame, float* out, int on_device) {

@@ -272,14 +272,14 @@ __global__ void vf_vox_keys_kernel(const int32_t* __restrict__ layout, int64_t n
   }
 }
 
-// columns 20 .. 136 of a frame's VOSCH rows: its C3-HLAC-117 rows, zeros where exist is 0 (rows
-// of empty subdivisions may be stale)
+// columns 20 .. of a frame's VOSCH (117 of 137) or ConVOSCH (981 of 1001) rows: its C3-HLAC rows,
+// zeros where exist is 0 (rows of empty subdivisions may be stale)
 __global__ void vf_c3_cols_kernel(const float* __restrict__ c3, const int32_t* __restrict__ exist, int64_t H,
-                                  float* __restrict__ rows) {
-  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < H * 117; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t h = e / 117;
-    const int t = (int)(e - h * 117);
-    rows[h * 137 + 20 + t] = exist[h] ? c3[e] : 0.0f;
+                                  int variant, int stride, float* __restrict__ rows) {
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < H * variant; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t h = e / variant;
+    const int t = (int)(e - h * variant);
+    rows[h * stride + 20 + t] = exist[h] ? c3[e] : 0.0f;
   }
 }
 
@@ -371,8 +371,9 @@ hipError_t launch_vf_vox_keys(const int32_t* layout, int64_t nvox, int64_t nc, i
   return hipGetLastError();
 }
 
-hipError_t launch_vf_c3_cols(const float* c3, const int32_t* exist, int64_t H, float* rows, hipStream_t s) {
-  if (H > 0) vf_c3_cols_kernel<<<grid_blocks(H * 117), 256, 0, s>>>(c3, exist, H, rows);
+hipError_t launch_vf_c3_cols(const float* c3, const int32_t* exist, int64_t H, int variant, int stride, float* rows,
+                             hipStream_t s) {
+  if (H > 0) vf_c3_cols_kernel<<<grid_blocks(H * variant), 256, 0, s>>>(c3, exist, H, variant, stride, rows);
   return hipGetLastError();
 }
 

@@ -365,7 +365,8 @@ std::vector<float> getNormals(const VoxelGrid& grid) {
 }
 
 static Vector3i grsd_like(VoxelGrid& grid, std::vector<std::vector<float> >& feature, float voxel_size, int subdiv,
-                          int ox, int oy, int oz, bool normalize, const int* thr) {
+                          int ox, int oy, int oz, bool normalize, const int* thr, int c3 = 117) {
+  // thr == nullptr: GRSD-20; else [GRSD-20 | C3-HLAC-c3]: 117 VOSCH, 981 ConVOSCH
   feature.resize(0);
   if (grid.leaf() != 0.0f && voxel_size != grid.leaf())
     throw Error(C3H_ERR_ARG, "extractGRSDSignature21: voxel_size differs from the grid's leaf size");
@@ -380,15 +381,16 @@ static Vector3i grsd_like(VoxelGrid& grid, std::vector<std::vector<float> >& fea
   int32_t sb[3] = {0, 0, 0};
   int64_t H = 0;
   auto run = [&] {
-    return thr ? c3h_extract_vosch(ctx.get(), &p, thr, 1, sb, &H) : c3h_extract_grsd(ctx.get(), &p, sb, &H);
+    if (!thr) return c3h_extract_grsd(ctx.get(), &p, sb, &H);
+    return c3 == 981 ? c3h_extract_convosch(ctx.get(), &p, thr, 1, sb, &H) : c3h_extract_vosch(ctx.get(), &p, thr, 1, sb, &H);
   };
   int rc = run();
   if (rc == C3H_ERR_STATE) {  // no normals yet: computeNormal with the reference's radius
     computeNormal(grid);
     rc = run();
   }
-  ctx.check(rc, thr ? "c3h_extract_vosch" : "c3h_extract_grsd");
-  const int F = thr ? 137 : 20;
+  ctx.check(rc, !thr ? "c3h_extract_grsd" : c3 == 981 ? "c3h_extract_convosch" : "c3h_extract_vosch");
+  const int F = thr ? 20 + c3 : 20;
   if (H > 0) {
     std::vector<float> flat((size_t)H * F);
     ctx.check(c3h_get_features(ctx.get(), flat.data(), 0), "c3h_get_features");
@@ -407,6 +409,12 @@ Vector3i extractVOSCH(VoxelGrid& grid, std::vector<std::vector<float> >& feature
                       float voxel_size, int subdiv, int ox, int oy, int oz, bool is_normalize) {
   const int thr[3] = {thR, thG, thB};
   return grsd_like(grid, feature, voxel_size, subdiv, ox, oy, oz, is_normalize, thr);
+}
+
+Vector3i extractConVOSCH(VoxelGrid& grid, std::vector<std::vector<float> >& feature, int thR, int thG, int thB,
+                         float voxel_size, int subdiv, int ox, int oy, int oz, bool is_normalize) {
+  const int thr[3] = {thR, thG, thB};
+  return grsd_like(grid, feature, voxel_size, subdiv, ox, oy, oz, is_normalize, thr, 981);
 }
 
 // ------------------------------------------------------------------------- PCA
@@ -848,12 +856,12 @@ void SearchC3HLACMulti::setC3HLAC(int dim, int r, int g, int b, const VoxelGrid&
   set_c3hlac(*this, C3H_VARIANT_981, r, g, b, grid, voxel_size, subdiv);
 }
 
-// setVOSCH / setGRSD (search_new.h:34-76): features on the grid's context, handed to the
+// setVOSCH / setConVOSCH / setGRSD (search_new.h:34-76): features on the grid's context, handed to the
 // search context with their exist rule (setData)
-static void set_external(SearchObj& so, VoxelGrid& grid, double voxel_size, int subdiv, const int* thr) {
+static void set_external(SearchObj& so, VoxelGrid& grid, double voxel_size, int subdiv, const int* thr, int c3 = 117) {
   std::vector<std::vector<float> > f;
-  const Vector3i sb = grsd_like(grid, f, (float)voxel_size, subdiv, 0, 0, 0, false, thr);
-  const int F = thr ? 137 : 20;
+  const Vector3i sb = grsd_like(grid, f, (float)voxel_size, subdiv, 0, 0, 0, false, thr, c3);
+  const int F = thr ? 20 + c3 : 20;
   std::vector<float> flat;
   flat.reserve(f.size() * F);
   for (const auto& row : f) flat.insert(flat.end(), row.begin(), row.end());
@@ -877,6 +885,20 @@ void SearchVOSCHMulti::setVOSCH(int dim, int r, int g, int b, VoxelGrid& grid, d
   ensureSetup(137);
   const int thr[3] = {r, g, b};
   set_external(*this, grid, voxel_size, subdiv, thr);
+}
+
+void SearchConVOSCH::setConVOSCH(int dim, int r, int g, int b, VoxelGrid& grid, double voxel_size, int subdiv) {
+  (void)dim;
+  ensureSetup(1001);
+  const int thr[3] = {r, g, b};
+  set_external(*this, grid, voxel_size, subdiv, thr, 981);
+}
+
+void SearchConVOSCHMulti::setConVOSCH(int dim, int r, int g, int b, VoxelGrid& grid, double voxel_size, int subdiv) {
+  (void)dim;
+  ensureSetup(1001);
+  const int thr[3] = {r, g, b};
+  set_external(*this, grid, voxel_size, subdiv, thr, 981);
 }
 
 void SearchGRSD::setGRSD(int dim, VoxelGrid& grid, double voxel_size, int subdiv) {
@@ -934,6 +956,14 @@ std::vector<c3h_det> SearchVOSCH::searchBatch(int r, int g, int b, const std::ve
                                               const Vector3i& canvas_b, bool rotate, std::vector<c3h_frame_info>* info) {
   const int thr[3] = {r, g, b};
   return searchBatchPoints(137, thr, clouds, n, voxel_size, subdiv, canvas_b, rotate, info);
+}
+
+std::vector<c3h_det> SearchConVOSCH::searchBatch(int r, int g, int b, const std::vector<const float*>& clouds,
+                                                 const std::vector<int64_t>& n, double voxel_size, int subdiv,
+                                                 const Vector3i& canvas_b, bool rotate,
+                                                 std::vector<c3h_frame_info>* info) {
+  const int thr[3] = {r, g, b};
+  return searchBatchPoints(1001, thr, clouds, n, voxel_size, subdiv, canvas_b, rotate, info);
 }
 
 std::vector<c3h_det> SearchGRSD::searchBatch(const std::vector<const float*>& clouds, const std::vector<int64_t>& n,

@@ -299,6 +299,11 @@ Vector3i extractGRSDSignature21(VoxelGrid& grid, std::vector<std::vector<float> 
 Vector3i extractVOSCH(VoxelGrid& grid, std::vector<std::vector<float> >& feature, int thR, int thG, int thB,
                       float voxel_size, int subdivision_size = 0, int offset_x = 0, int offset_y = 0,
                       int offset_z = 0, bool is_normalize = false);
+// ConVOSCH, the rotation-variant member: [GRSD-20 | C3-HLAC-981] = 1001 floats per subdivision
+// (example_GRSD_CCHLAC.cpp; c3h_extract_convosch)
+Vector3i extractConVOSCH(VoxelGrid& grid, std::vector<std::vector<float> >& feature, int thR, int thG, int thB,
+                         float voxel_size, int subdivision_size = 0, int offset_x = 0, int offset_y = 0,
+                         int offset_z = 0, bool is_normalize = false);
 
 // pcl::io::loadPCDFile for x y z rgb clouds (c3h_pcd_read_xyzrgb): 0 on success, -1 when
 // the file cannot be opened or parsed, as PCL returns.
@@ -440,7 +445,7 @@ class SearchObj {
   void ensureSetup(int F);
   void run(bool rotate, bool remove_overlap);
   // c3h_run_vosch_point_frames: clouds in (n[i] x 4 floats x y z rgb, host), per frame the
-  // setVOSCH / setGRSD + search() of this object from fresh lists; returns frame-major
+  // setVOSCH / setConVOSCH / setGRSD + search() of this object from fresh lists; returns frame-major
   // M x rank records, info (may be nullptr) the frames' c3h_frame_info
   std::vector<c3h_det> searchBatchPoints(int dim, const int* thr, const std::vector<const float*>& clouds,
                                          const std::vector<int64_t>& n, double voxel_size, int subdivision_size,
@@ -501,6 +506,25 @@ class SearchVOSCHMulti : public SearchObjMulti {
   using SearchObjMulti::SearchObjMulti;
   void setVOSCH(int dim, int color_threshold_r, int color_threshold_g, int color_threshold_b, VoxelGrid& grid,
                 double voxel_size, int subdivision_size);
+};
+// SearchConVOSCH{,Multi}::setConVOSCH (search_new.h:34-76): as setVOSCH with the 1001-float rows
+// of extractConVOSCH (axes of dimension 1001) and the same exist rule
+class SearchConVOSCH : public SearchObj {
+ public:
+  using SearchObj::SearchObj;
+  void setConVOSCH(int dim, int color_threshold_r, int color_threshold_g, int color_threshold_b, VoxelGrid& grid,
+                   double voxel_size, int subdivision_size);
+  // a batch of clouds through getVoxelGrid + setConVOSCH + search() in one call (c3h_run_vosch_point_frames)
+  std::vector<c3h_det> searchBatch(int color_threshold_r, int color_threshold_g, int color_threshold_b,
+                                   const std::vector<const float*>& clouds, const std::vector<int64_t>& n,
+                                   double voxel_size, int subdivision_size, const Vector3i& canvas_b,
+                                   bool rotate = true, std::vector<c3h_frame_info>* info = nullptr);
+};
+class SearchConVOSCHMulti : public SearchObjMulti {
+ public:
+  using SearchObjMulti::SearchObjMulti;
+  void setConVOSCH(int dim, int color_threshold_r, int color_threshold_g, int color_threshold_b, VoxelGrid& grid,
+                   double voxel_size, int subdivision_size);
 };
 class SearchGRSD : public SearchObj {
  public:

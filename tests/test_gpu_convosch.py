@@ -1,0 +1,434 @@
+"""ConVOSCH ([GRSD-20 | C3-HLAC-981], rows of 1001 floats) from point clouds: one frame
+(c3h_extract_convosch) against the parts it is composed of, and a batch (dim 1001 in
+c3h_extract_vosch_frames / c3h_run_vosch_point_frames) against the single-frame route on a second
+context -- at head 1, whose colour columns come from the sparse batched C3-HLAC-981
+(csrc/c3_sparse.hip), and at head 0, the per-frame extract.  Every comparison of rows, info,
+normals, RSD and search records is of bytes (uint32 views), unconditional.  The clouds:
+vosch_frames_data.py and convosch_data.py, whose conditions test_vosch_frames_cpu.py and
+test_convosch_cpu.py assert with the oracle alone.  ConVOSCH is this composition; parity with the
+reference beyond it is unpinned, as for VOSCH."""
+import ctypes as C
+import json
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import c3hlac
+import convosch_data as cd
+import pyoracle as po
+import vosch_frames_data as vd
+from c3hlac import _capi, synth
+from c3hlac._capi import ptr
+from conftest import ROOT, THR
+from test_gpu_vosch_frames import cap_of, check_frames, u32
+
+pytestmark = pytest.mark.gpu
+ERR_ARG, ERR_STATE, ERR_RANGE = -1, -3, -5
+SENTINEL = np.float32(-12345.5)
+INF = float("inf")
+DIM = 1001
+HEADS = (1, 0)
+
+
+@pytest.fixture(scope="module")
+def hctx():
+    c = c3hlac.Context(0)
+    c.set_batch(64)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def ref_ctx():
+    c = c3hlac.Context(0)
+    yield c
+    c.close()
+
+
+def single_on(rc, pts, leaf, z_limit, radius, dim, normalize, subdiv=vd.SUBDIV, offset=vd.OFFSET, thr=THR):
+    """The single-frame route on context rc (test_gpu_vosch_frames.single_on with dim 1001)."""
+    lib, h = rc.lib, rc.h
+    out = {"status": 0, "rows": np.zeros((0, dim), np.float32), "sb": (0, 0, 0)}
+    gi = _capi.GridInfo()
+    p = rc._grsd_params(subdiv, offset, 0.01, normalize)
+    sb = (C.c_int32 * 3)()
+    hn = C.c_int64()
+    t = (C.c_int32 * 3)(*thr)
+    st = lib.c3h_voxelize(h, ptr(np.ascontiguousarray(pts)), len(pts), 0, float(leaf), float(z_limit), C.byref(gi))
+    if st >= 0:
+        st = lib.c3h_compute_normals(h, float(radius), None)
+    if st >= 0:
+        if dim == 1001:
+            st = lib.c3h_extract_convosch(h, C.byref(p), t, 1, sb, C.byref(hn))
+        elif dim == 137:
+            st = lib.c3h_extract_vosch(h, C.byref(p), t, 1, sb, C.byref(hn))
+        else:
+            st = lib.c3h_extract_grsd(h, C.byref(p), sb, C.byref(hn))
+    out["status"] = min(st, 0)
+    if st >= 0:
+        out["div_b"], out["min_b"] = tuple(gi.div_b), tuple(gi.min_b)
+        out["n_valid"], out["n_occ"], out["sb"] = int(gi.n_valid), int(gi.n_occ), tuple(sb)
+        rc.hist_num, rc.variant = int(hn.value), dim
+        out["rows"] = rc.features()
+        out["normals"] = rc.normals(len(pts))
+        out["radii"], out["types"] = rc.rsd()
+    return out
+
+
+_REFS = {}
+
+
+def single(rc, pts, leaf, z_limit, radius, dim, normalize, subdiv=vd.SUBDIV, offset=vd.OFFSET, thr=THR):
+    """Computed once per argument set and kept unchanged."""
+    key = (id(pts), leaf, z_limit, radius, dim, normalize, subdiv, offset, thr)
+    if key not in _REFS:
+        _REFS[key] = single_on(rc, pts, leaf, z_limit, radius, dim, normalize, subdiv, offset, thr)
+    return _REFS[key]
+
+
+def run_batch(ctx, clouds, leaf, z_limit, radius, dim, normalize, row_cap, rows=None, subdiv=vd.SUBDIV,
+              offset=vd.OFFSET, thr=THR):
+    return ctx.extract_vosch_frames(clouds, leaf, dim=dim, row_cap=row_cap, thr=thr, subdiv=subdiv, offset=offset,
+                                    normalize=normalize, normals_radius=radius, z_limit=z_limit, rows=rows)
+
+
+# ---- 1. one frame against the pinned parts ------------------------------------------------------
+def test_one_frame_is_grsd_and_c3hlac_981(ctx):
+    pts = synth.kinect_scene(150_000, grid=48, leaf=0.02, seed=77)
+    ctx.voxelize(pts, 0.02)
+    ctx.compute_normals(0.04)
+    ctx.extract_grsd(6)
+    grsd = ctx.features().copy()
+    sb, H = ctx.extract(981, THR, 6)
+    c3, ex = ctx.features().copy(), ctx.exist().copy()
+    sbv, Hv = ctx.extract_convosch(THR, 6)
+    assert sbv == sb and Hv == H and H > 1
+    v = ctx.features()
+    assert v.shape == (H, DIM)
+    assert np.array_equal(u32(v[:, :20]), u32(grsd))
+    assert (ex > 0).sum() > 1 and (ex == 0).any()
+    assert np.array_equal(u32(v[:, 20:][ex > 0]), u32(c3[ex > 0]))
+    assert (u32(v[:, 20:][ex == 0]) == 0).all()
+    assert np.array_equal(ctx.exist(), ex)  # the setConVOSCH rule on f20, f21 = the C3 rule
+    axis_t, var, axis_q = synth.random_bases(DIM, 30, 2, 5, seed=78)
+    fmax = v.max(0) * np.float32(0.9)
+    ctx.search_setup(axis_t, var, axis_q, feature_max=fmax)
+    ctx.set_rank(1)
+    ctx.search((2, 2, 2), 20, rotate=False)
+    _, _, scd = po.search(sb, v, ex, synth.whiten(axis_t, var), axis_q, (2, 2, 2), 1, 20, rotate=False,
+                          dbl=True, fmax=fmax, want_scores=True)
+    sc = ctx.scores()
+    ok = scd > 0
+    assert ok.any()
+    np.testing.assert_allclose(sc[ok], scd[ok], rtol=1e-5)
+
+
+# ---- 2. a batch equals the single frames --------------------------------------------------------
+@pytest.mark.parametrize("z_limit", vd.Z_LIMITS, ids=["plain", "z1"])
+@pytest.mark.parametrize("normalize", [False, True])
+def test_batch_equals_single_frames(hctx, ref_ctx, normalize, z_limit):
+    names = [n for n, _ in vd.batch()]
+    clouds = [p for _, p in vd.batch()]
+    refs = [single(ref_ctx, p, vd.LEAF, z_limit, vd.RADIUS, DIM, normalize) for p in clouds]
+    assert sum(len(r["rows"]) > 1 for r in refs) >= 3
+    hctx.set_batch(64)
+    for head in HEADS:
+        hctx.set_vosch_head(head)
+        views, info = run_batch(hctx, clouds, vd.LEAF, z_limit, vd.RADIUS, DIM, normalize, cap_of(refs))
+        check_frames(hctx, refs, views, info)
+        if z_limit == vd.Z_LIMITS[0]:
+            assert info["n_moved"][names.index("edge")] == 1
+
+
+def test_fine_leaf_with_off_cell_centroids(hctx, ref_ctx):
+    clouds = [p for _, p in vd.fine_batch()]
+    refs = [single(ref_ctx, p, vd.FINE_LEAF, INF, vd.RADIUS, DIM, False) for p in clouds]
+    for head in HEADS:
+        hctx.set_vosch_head(head)
+        views, info = run_batch(hctx, clouds, vd.FINE_LEAF, INF, vd.RADIUS, DIM, False, cap_of(refs))
+        check_frames(hctx, refs, views, info)
+        assert info["n_moved"][0] == 14 and info["n_occ"][0] == 945
+
+
+# ---- 3. exactness and chunks --------------------------------------------------------------------
+def test_sums_beyond_32_bits_and_groups_of_many_chunks(hctx, ref_ctx):
+    """The white plane and the dense cube in one head-1 batch, at the plane's subdivision 0 (one row
+    each: 90,000 voxels in 88 chunks with sums above 2^32, and 1,728 voxels in two chunks) and at the
+    cube's subdivision 10 (900 rows of 100 voxels, and 8 rows of 1,000 .. 8 voxels)."""
+    hctx.set_batch(64)
+    hctx.set_vosch_head(1)
+    clouds = [cd.white_plane(), cd.dense_cube()]
+    for subdiv in (cd.PLANE_SUBDIV, cd.CUBE_SUBDIV):
+        want = []
+        for pts in clouds:
+            ref_ctx.voxelize(pts, cd.LEAF)
+            sb, H = ref_ctx.extract(981, cd.THR_MID, subdiv)
+            want.append((tuple(sb), H, ref_ctx.features().copy(), ref_ctx.exist().copy()))
+        cap = max(w[1] for w in want)
+        views, info = run_batch(hctx, clouds, cd.LEAF, INF, vd.RADIUS, DIM, False, cap, subdiv=subdiv, offset=(0, 0, 0),
+                                thr=cd.THR_MID)
+        views20, info20 = run_batch(hctx, clouds, cd.LEAF, INF, vd.RADIUS, 20, False, cap, subdiv=subdiv, offset=(0, 0, 0))
+        assert list(info["status"]) == [0, 0] and list(info20["status"]) == [0, 0]
+        for k, (sb, H, c3, ex) in enumerate(want):
+            got = views[k].cpu().numpy()
+            # (one histogram: c3h_extract reports counts (0, 0, 0), the GRSD front (1, 1, 1))
+            assert tuple(info["subdiv_b"][k]) == (sb if subdiv else (1, 1, 1)) and got.shape == (H, DIM) and (ex > 0).any()
+            assert np.array_equal(u32(got[:, 20:][ex > 0]), u32(c3[ex > 0]))
+            assert (u32(got[:, 20:][ex == 0]) == 0).all()
+            assert np.array_equal(u32(got[:, :20]), u32(views20[k].cpu().numpy()))
+        if subdiv == cd.PLANE_SUBDIV:
+            assert want[0][1] == 1 and float(views[0].cpu().numpy()[0, 20 + 474]) * 65025 > 2.0 ** 32
+        else:
+            assert want[1][3].tolist() == cd.CUBE_EXIST and (views[1].cpu().numpy()[0, 20:] != 0).all()
+
+
+# ---- 4. batch mechanics -------------------------------------------------------------------------
+def test_batch_sizes_order_row_cap_and_empty_frames(hctx, ref_ctx):
+    import torch
+    named = vd.batch()
+    names = [n for n, _ in named]
+    clouds = [p for _, p in named]
+    refs = [single(ref_ctx, p, vd.LEAF, INF, vd.RADIUS, DIM, False) for p in clouds]
+    cap = cap_of(refs)
+    hctx.set_vosch_head(1)
+    for B in (1, 3, 64):
+        hctx.set_batch(B)
+        views, info = run_batch(hctx, clouds, vd.LEAF, INF, vd.RADIUS, DIM, False, cap)
+        check_frames(hctx, refs, views, info, getters=B >= len(clouds))
+    hctx.set_batch(64)
+    order = np.random.default_rng(3).permutation(len(clouds))
+    views, info = run_batch(hctx, [clouds[i] for i in order], vd.LEAF, INF, vd.RADIUS, DIM, False, cap)
+    check_frames(hctx, [refs[i] for i in order], views, info)
+    views, info = run_batch(hctx, clouds * 8, vd.LEAF, INF, vd.RADIUS, DIM, False, cap)  # 64 frames, one batch
+    check_frames(hctx, refs * 8, views, info, getters=False)
+    # row_cap one below the edge cloud's count: that frame alone fails, its slot keeps the sentinel
+    e = names.index("edge")
+    small = len(refs[e]["rows"]) - 1
+    assert small >= max(len(r["rows"]) for k, r in enumerate(refs) if k != e)
+    rows = torch.full((len(clouds) * small * DIM,), float(SENTINEL), dtype=torch.float32, device="cuda:0")
+    torch.cuda.synchronize()
+    views, info = run_batch(hctx, clouds, vd.LEAF, INF, vd.RADIUS, DIM, False, small, rows=rows)
+    assert info["status"][e] == ERR_RANGE and views[e] is None
+    slots = rows.view(len(clouds), small * DIM)
+    assert (slots[e] == float(SENTINEL)).all()
+    cut = [dict(r, status=ERR_RANGE) if k == e else r for k, r in enumerate(refs)]
+    check_frames(hctx, cut, views, info, getters=False)
+    for k in (e - 1, e + 1):
+        h = len(refs[k]["rows"])
+        assert (slots[k, h * DIM:] == float(SENTINEL)).all()
+    # empty frames between full ones
+    d = dict(named)
+    empty = [d["no_point"], np.full((5, 4), np.nan, np.float32)]
+    mixed = [empty[0], d["noisy_sphere_green"], empty[1], empty[0], d["edge"], d["noiseless_cone_red"], empty[0]]
+    mrefs = [single(ref_ctx, p, vd.LEAF, INF, vd.RADIUS, DIM, False) for p in mixed]
+    assert [r["status"] for r in mrefs] == [ERR_STATE, 0, ERR_STATE, ERR_STATE, 0, 0, ERR_STATE]
+    views, info = run_batch(hctx, mixed, vd.LEAF, INF, vd.RADIUS, DIM, False, cap)
+    check_frames(hctx, mrefs, views, info)
+
+
+# ---- 5. search records --------------------------------------------------------------------------
+@pytest.mark.parametrize("rank,overlap", [(1, False), (4, True)])
+def test_search_records(hctx, ref_ctx, rank, overlap):
+    import torch
+    dev = torch.device("cuda", 0)
+    clouds = [p for _, p in vd.batch()]
+    refs = [single(ref_ctx, p, vd.LEAF, INF, vd.RADIUS, DIM, False) for p in clouds]
+    M = 2
+    axis_t, var, axis_q = synth.random_bases(DIM, 30, M, 5, seed=78)
+    hctx.search_setup(axis_t, var, axis_q)
+    hctx.set_rank(rank)
+    hctx.set_remove_overlap(overlap)
+    hctx.set_batch(64)
+    e = [n for n, _ in vd.batch()].index("edge")
+    full = tuple(max(r["sb"][a] for r in refs) for a in range(3))
+    small = tuple(max(r["sb"][a] for k, r in enumerate(refs) if k != e) for a in range(3))
+    assert any(refs[e]["sb"][a] > small[a] for a in range(3))
+    box, thr = (2, 2, 2), 5
+    nf = len(clouds)
+    feats = [torch.from_numpy(np.ascontiguousarray(r["rows"])).to(dev) for r in refs]
+    try:
+        for canvas in (full, small):
+            cut = canvas is small
+            sbs = [(0, 0, 0) if (cut and k == e) else r["sb"] for k, r in enumerate(refs)]
+            fs = [f[:0] if (cut and k == e) else f for k, f in enumerate(feats)]
+            want = torch.zeros((nf, M * rank * 3), dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            nm_ref = hctx.run_feature_frames(fs, sbs, canvas, rule=1, ranges=box, exist_threshold=thr, rotate=True,
+                                             d_out=want)
+            hctx.synchronize()
+            want = want.cpu().numpy()
+            assert want.view(c3hlac.DET_DTYPE)["score"].max() > 0
+            for head in HEADS:
+                hctx.set_vosch_head(head)
+                got = torch.full((nf, M * rank * 3), -1, dtype=torch.int64, device=dev)
+                torch.cuda.synchronize()
+                nm, info = hctx.run_vosch_point_frames(clouds, vd.LEAF, canvas, box, thr, dim=DIM, thr=THR,
+                                                       subdiv=vd.SUBDIV, offset=vd.OFFSET, normals_radius=vd.RADIUS,
+                                                       d_out=got)
+                hctx.synchronize()
+                assert nm == nm_ref and np.array_equal(got.cpu().numpy(), want), (head, cut)
+                st = [ERR_RANGE if (cut and k == e) else r["status"] for k, r in enumerate(refs)]
+                assert [int(s) for s in info["status"]] == st
+    finally:
+        hctx.set_rank(1)
+        hctx.set_remove_overlap(False)
+
+
+# ---- 6. argument checks -------------------------------------------------------------------------
+def test_argument_checks(hctx, ref_ctx):
+    import torch
+    clouds = [p for _, p in vd.batch()]
+    with pytest.raises(_capi.C3HError, match="C3H_ERR_ARG"):
+        run_batch(hctx, clouds[:2], vd.LEAF, INF, vd.RADIUS, 1000, False, 8)
+    axis_t, var, axis_q = synth.random_bases(137, 30, 2, 5, seed=79)
+    hctx.search_setup(axis_t, var, axis_q)
+    hctx.set_rank(1)
+    got = torch.full((2, 2 * 3), -1, dtype=torch.int64, device="cuda:0")
+    torch.cuda.synchronize()
+    with pytest.raises(_capi.C3HError, match="C3H_ERR_ARG"):
+        hctx.run_vosch_point_frames(clouds[:2], vd.LEAF, (4, 4, 4), (2, 2, 2), 5, dim=DIM, thr=THR, subdiv=vd.SUBDIV,
+                                    offset=vd.OFFSET, normals_radius=vd.RADIUS, d_out=got)
+    hctx.synchronize()
+    assert (got.cpu().numpy() == -1).all()  # refused before anything is enqueued
+    # a negative threshold: C3H_ERR_STATE on every frame that has rows, at either head
+    refs = [single(ref_ctx, p, vd.LEAF, INF, vd.RADIUS, DIM, False) for p in clouds]
+    want = [r["status"] if len(r["rows"]) == 0 else ERR_STATE for r in refs]
+    assert ERR_STATE in want and 0 in want
+    neg = (THR[0], -1, THR[2])
+    status = {}
+    for head in HEADS:
+        hctx.set_vosch_head(head)
+        rows = torch.full((len(clouds) * cap_of(refs) * DIM,), float(SENTINEL), dtype=torch.float32, device="cuda:0")
+        torch.cuda.synchronize()
+        views, info = run_batch(hctx, clouds, vd.LEAF, INF, vd.RADIUS, DIM, False, cap_of(refs), rows=rows, thr=neg)
+        status[head] = [int(s) for s in info["status"]]
+        assert (rows == float(SENTINEL)).all()  # no frame has a row to write
+    assert status[1] == status[0] == want
+
+
+# ---- 7. shared state ----------------------------------------------------------------------------
+def test_single_frames_and_batches_share_a_context():
+    named = vd.batch()
+    clouds = [p for _, p in named]
+    edge = dict(named)["edge"]
+    con = (edge, vd.LEAF, INF, vd.RADIUS, DIM, False)
+    vos = (edge, vd.LEAF, INF, vd.RADIUS, 137, False)
+
+    def batch_on(c, dim):
+        c.set_batch(64)
+        c.set_vosch_head(1)
+        views, info = run_batch(c, clouds, vd.LEAF, INF, vd.RADIUS, dim, False, cap)
+        out = []
+        for i, v in enumerate(views):
+            if v is None:
+                out.append(None)
+                continue
+            radii, types = c.frame_rsd(i)
+            out.append(dict(rows=v.cpu().numpy().copy(), normals=c.frame_normals(i), radii=radii, types=types))
+        return out, np.array(info["status"]).copy()
+
+    def fresh(fn, *args):
+        with c3hlac.Context(0) as c:
+            return fn(c, *args)
+
+    def same(got, want):
+        assert got.keys() == want.keys() and got["status"] == 0
+        for k in want:
+            if isinstance(want[k], np.ndarray):
+                assert want[k].size > 0 and np.array_equal(u32(got[k]), u32(want[k])), k
+            else:
+                assert got[k] == want[k], k
+
+    def same_batch(got, want):
+        assert np.array_equal(got[1], want[1])
+        for g, w in zip(got[0], want[0]):
+            assert (g is None) == (w is None)
+            if g is not None:
+                for k in w:
+                    assert np.array_equal(u32(g[k]), u32(w[k])), k
+
+    want_con, want_vos = fresh(single_on, *con), fresh(single_on, *vos)
+    cap = len(want_con["rows"])
+    want_b1001, want_b137 = fresh(batch_on, DIM), fresh(batch_on, 137)
+    with c3hlac.Context(0) as c:
+        for _ in range(2):
+            same(single_on(c, *con), want_con)
+            same_batch(batch_on(c, DIM), want_b1001)
+            p = c._grsd_params(vd.SUBDIV, vd.OFFSET, 0.01, False)
+            sb, hn = (C.c_int32 * 3)(), C.c_int64()
+            t = (C.c_int32 * 3)(*THR)
+            assert c.lib.c3h_extract_convosch(c.h, C.byref(p), t, 1, sb, C.byref(hn)) == ERR_STATE
+            assert c.lib.c3h_extract_vosch(c.h, C.byref(p), t, 1, sb, C.byref(hn)) == ERR_STATE
+            with pytest.raises(_capi.C3HError, match="C3H_ERR_STATE"):
+                c.compute_normals(vd.RADIUS)
+            same_batch(batch_on(c, 137), want_b137)
+            same(single_on(c, *vos), want_vos)
+            same_batch(batch_on(c, DIM), want_b1001)
+            same(single_on(c, *con), want_con)
+
+
+# ---- 8. the facade --------------------------------------------------------------------------------
+def _lcg(seed, n):
+    s = np.uint64(seed)
+    out = np.empty(n, np.float32)
+    for i in range(n):
+        s = (s * np.uint64(1664525) + np.uint64(1013904223)) & np.uint64(0xFFFFFFFF)
+        out[i] = np.float32(int((s >> np.uint64(8)) & np.uint64(0xFFFF)) / 65536.0) - np.float32(0.5)
+    return out
+
+
+def test_facade_search_convosch(hctx, tmp_path):
+    import torch
+    pkg = ROOT / "mapping-private_amd"
+    assert shutil.which("g++") and (pkg / "lib" / "libc3hlac_host.so").exists()
+    exe = tmp_path / "convosch_demo"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", str(ROOT / "include"), "-I", str(pkg / "host"),
+                    str(ROOT / "tests" / "cpp" / "convosch_demo.cpp"), "-L", str(pkg / "lib"), "-lc3hlac_host",
+                    "-lc3hlac_mi355x", "-Wl,-rpath," + str(pkg / "lib"), "-o", str(exe)], check=True, capture_output=True,
+                   text=True)
+    d = dict(vd.batch())
+    clouds = [np.ascontiguousarray(d[k]) for k in ("noisy_sphere_green", "noiseless_cone_red", "bowl1_0000")]
+    files = []
+    for i, p in enumerate(clouds):
+        files.append(tmp_path / ("cloud%d.bin" % i))
+        p.tofile(files[-1])
+    D, rdim, box, thr = 16, 4, (2, 2, 2), 5
+    # the C-ABI records through the binding: the demo's LCG scene axis and the model file it wrote
+    hctx.set_vosch_head(1)
+    hctx.set_batch(64)
+    hctx.set_rank(1)
+    hctx.set_remove_overlap(False)
+    singles = []
+    canvas = (8, 8, 8)
+    r = subprocess.run([str(exe), str(tmp_path), repr(vd.LEAF), str(vd.SUBDIV)] + [str(c) for c in canvas] +
+                       [str(f) for f in files], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    j = json.loads(r.stdout)
+    a, v, _ = c3hlac.pca_read(tmp_path / "m0")
+    q = c3hlac.read_axis(a, v, D, rdim, multiple_similarity=True)
+    axis = _lcg(3, D * DIM).reshape(D, DIM)
+    var = np.arange(1, D + 1, dtype=np.float32)
+    hctx.search_setup(axis, var, np.stack([q]))
+    for p in clouds:
+        hctx.voxelize(p, vd.LEAF)
+        hctx.compute_normals(0.02)
+        sb, _ = hctx.extract_convosch(THR, vd.SUBDIV)
+        assert all(sb[k] <= canvas[k] for k in range(3))
+        hctx.set_features(hctx.features(), sb, None, rule=1)  # setData with the setConVOSCH rule, as the facade
+        hctx.clean_max()  # fresh lists per cloud, as the demo's cleanData
+        det, _ = hctx.search(box, thr, rotate=True)
+        e = det[0, 0]
+        singles.append([float(e["score"]), int(e["x"]), int(e["y"]), int(e["z"]), int(e["mode"])])
+    assert max(s[0] for s in singles) > 0
+    assert j["single"] == singles
+    got = torch.full((len(clouds), 3), -1, dtype=torch.int64, device="cuda:0")
+    torch.cuda.synchronize()
+    nm, info = hctx.run_vosch_point_frames(clouds, vd.LEAF, canvas, box, thr, dim=DIM, thr=THR, subdiv=vd.SUBDIV,
+                                           normals_radius=0.02, d_out=got)
+    hctx.synchronize()
+    rec = got.cpu().numpy().view(c3hlac.DET_DTYPE).reshape(len(clouds))
+    want = [[float(e["score"]), int(e["x"]), int(e["y"]), int(e["z"]), int(e["mode"])] for e in rec]
+    assert j["batch"] == want and j["status"] == [int(s) for s in info["status"]] == [0, 0, 0]
+    assert max(w[0] for w in want) > 0

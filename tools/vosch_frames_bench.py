@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Point clouds in, detections out (c3h_run_vosch_point_frames) against what a caller of the
 same library did before it, per frame: c3h_voxelize -> c3h_compute_normals -> c3h_extract_vosch
--> a device copy of the rows, then one c3h_run_feature_frames over the frames' rows.
+(--dim 137) or c3h_extract_convosch (--dim 1001) -> a device copy of the rows, then one
+c3h_run_feature_frames over the frames' rows.
 
   A  resident synth.kinect_scene(300_000, grid=256, leaf=0.01) clouds (--scenes distinct ones,
      cycled to --frames), leaf 0.01, normals 0.02, RSD 0.01, subdivision 10;
@@ -22,7 +23,9 @@ the batched call at head 1 in the one process, compares the records of all three
 drains the device after each of the loop's calls (voxelize | normals with their grid | RSD + GRSD |
 C3 + rows: the granularity of the single-frame entry points, on the host clock); the kernels of
 either route are split further by running this tool under rocprofv3 --kernel-trace --stats.
-Prints one JSON line per setting and search."""
+Prints one JSON line per setting and search; "row_buffer_bytes" is what the tool itself allocates
+for the loop's rows (the batched call's rows are the context's: frames x canvas rows x dim floats,
+"context_row_bytes")."""
 import argparse
 import json
 import sys
@@ -36,7 +39,7 @@ import numpy as np  # noqa: E402
 
 import bench  # noqa: E402
 
-DIM, LEAF, RADIUS, SUBDIV = 137, 0.01, 0.02, 10
+LEAF, RADIUS, SUBDIV = 0.01, 0.02, 10
 SEARCHES = {"small": (10, 20, 1), "multi": (63, 70, 63)}  # M, r, rank
 
 
@@ -49,7 +52,9 @@ def main():
     ap.add_argument("--searches", default="small,multi")
     ap.add_argument("--route", default="both", choices=["both", "loop"])
     ap.add_argument("--head", default=None, choices=["0", "1", "both"], help="the batched call's head (c3h_set_vosch_head)")
+    ap.add_argument("--dim", type=int, default=137, choices=[137, 1001], help="137 VOSCH | 1001 ConVOSCH")
     args = ap.parse_args()
+    DIM = args.dim
     import torch
     import c3hlac
     from c3hlac import synth
@@ -59,6 +64,7 @@ def main():
     ctx = c3hlac.Context(0)
     ctx.set_batch(64)
     ctx.set_pipeline(True)
+    extract_rows = ctx.extract_vosch if DIM == 137 else ctx.extract_convosch
     if args.setting == "A":
         base = [synth.kinect_scene(300_000, grid=256, leaf=LEAF, seed=synth.BASE_SEED + k) for k in range(args.scenes)]
     else:
@@ -81,7 +87,7 @@ def main():
     for c in clouds:
         ctx.voxelize(c, LEAF)
         ctx.compute_normals(RADIUS)
-        sbs.append(ctx.extract_vosch(bench.THR, SUBDIV)[0])
+        sbs.append(extract_rows(bench.THR, SUBDIV)[0])
     canvas = tuple(max(s[a] for s in sbs) for a in range(3))
     rows = [torch.zeros((s[0] * s[1] * s[2], DIM), dtype=torch.float32, device=dev) for s in sbs]
     torch.cuda.synchronize(dev)
@@ -91,7 +97,7 @@ def main():
         for c in clouds:  # every stage drained before the next starts
             t = [time.perf_counter()]
             for call in (lambda: ctx.voxelize(c, LEAF), lambda: ctx.compute_normals(RADIUS),
-                         lambda: ctx.extract_grsd(SUBDIV), lambda: ctx.extract_vosch(bench.THR, SUBDIV)):
+                         lambda: ctx.extract_grsd(SUBDIV), lambda: extract_rows(bench.THR, SUBDIV)):
                 call()
                 ctx.synchronize()
                 t.append(time.perf_counter())
@@ -116,7 +122,7 @@ def main():
             for c, out in zip(clouds, rows):
                 ctx.voxelize(c, LEAF)
                 ctx.compute_normals(RADIUS)
-                ctx.extract_vosch(bench.THR, SUBDIV)
+                extract_rows(bench.THR, SUBDIV)
                 ctx._chk(ctx.lib.c3h_get_features(ctx.h, c3hlac.ptr(out), 1), "get_features")  # the device copy
             ctx.run_feature_frames(rows, sbs, canvas, rule=1, ranges=bench.BOX, exist_threshold=thr, rotate=False,
                                    d_out=d_loop)
@@ -157,9 +163,11 @@ def main():
         if heads:
             t_b = t_h[1]
         spread = max(t_l) - min(t_l)
-        out = {"setting": args.setting, "search": name, "M": M, "r": r, "rank": rank, "frames": nf,
+        out = {"setting": args.setting, "search": name, "dim": DIM, "M": M, "r": r, "rank": rank, "frames": nf,
                "points_per_frame": int(np.mean([len(c) for c in clouds])), "canvas_b": canvas,
-               "rows_per_frame": int(np.mean([len(x) for x in rows])), "loop_ms": t_l, "loop_spread_ms": spread,
+               "rows_per_frame": int(np.mean([len(x) for x in rows])),
+               "row_buffer_bytes": int(sum(x.numel() * 4 for x in rows)),
+               "context_row_bytes": int(nf * canvas[0] * canvas[1] * canvas[2] * DIM * 4), "loop_ms": t_l, "loop_spread_ms": spread,
                "loop_stage_ms_total": stages}
         if heads:
             spread0 = max(t_h[0]) - min(t_h[0])
