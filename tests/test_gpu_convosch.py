@@ -5,8 +5,9 @@ context -- at head 1, whose colour columns come from the sparse batched C3-HLAC-
 (csrc/c3_sparse.hip), and at head 0, the per-frame extract.  Every comparison of rows, info,
 normals, RSD and search records is of bytes (uint32 views), unconditional.  The clouds:
 vosch_frames_data.py and convosch_data.py, whose conditions test_vosch_frames_cpu.py and
-test_convosch_cpu.py assert with the oracle alone.  ConVOSCH is this composition; parity with the
-reference beyond it is unpinned, as for VOSCH."""
+test_convosch_cpu.py assert with the oracle alone.  ConVOSCH is this composition; the colour
+columns of head 1, head 0 and the single-frame route are pinned to the oracle, bit for bit, in
+test_gpu_c3_sparse.py."""
 import ctypes as C
 import json
 import shutil
