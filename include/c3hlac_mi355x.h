@@ -308,7 +308,10 @@ int c3h_clean_max(c3h_ctx* ctx);
  * (search.cpp:972-992) first.  A scheduled mode whose box does not fit the subdivisions is
  * skipped (searchPart's loops are empty); when none fits the search finds no candidate and
  * hands out the lists as they stand (a pending cleanMax applied), on the batch entry points
- * the setRank state.  Returns the number of scheduled modes (>0) or an error. */
+ * the setRank state.  Returns the number of scheduled modes (>0) or an error.  A D above 160
+ * runs the generic kernels, which stage 16 box rows of D + 1 floats in LDS: a D beyond what a
+ * workgroup of the device gets (160 KB on gfx950: D of about 2,500) is C3H_ERR_RANGE, before
+ * anything is launched. */
 int c3h_search(c3h_ctx* ctx, const int32_t range[3], int32_t exist_threshold,
                int32_t rotate, int32_t remove_overlap, c3h_det* out);
 /* Asynchronous variant for device-resident pipelines: no host sync; copies the M x rank

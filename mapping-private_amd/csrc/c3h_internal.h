@@ -560,6 +560,10 @@ struct ScoreLaunch {
 hipError_t launch_score(const ScoreLaunch& a, hipStream_t s);
 bool score_fast_ok(int D, int r);  // the sparse list path applies
 int64_t score_blocks(const ScoreLaunch& a);
+// generic path (launch_score): positions per workgroup on the current device, 64 or 16;
+// 0 = the request exceeds the device's LDS per workgroup at any of them (no launch)
+int score_generic_sp(int D, int r);
+size_t score_lds_limit();
 
 // sparse search (fast path): gate every position of every mode, project the list
 struct ModeGeom {

@@ -319,6 +319,13 @@ int c3h::search_frames(c3h_ctx* ctx, int nf, const int32_t range[3], int32_t thr
                     c3h::score_tick_wide_ok(ctx->D, ctx->M, ctx->r);
   const bool fast = valu_fast || mf || wide;  // the sparse (gate list) search
   if (nf > 1 && !fast) return fail(ctx, C3H_ERR_STATE, "search: batched frames need the fast path");
+  // the generic kernel stages whole box rows in LDS: a D beyond the device's LDS is refused
+  // before anything launches
+  if (!fast && !ctx->capture && c3h::score_generic_sp(ctx->D, ctx->r) == 0)
+    return fail(ctx, C3H_ERR_RANGE,
+                "c3h_search: D = " + std::to_string(ctx->D) + " with r = " + std::to_string(ctx->r) +
+                    " exceeds the generic score kernel's LDS (" + std::to_string(c3h::score_lds_limit()) +
+                    " bytes per workgroup on this device)");
   int modes[6];
   const int nm = mode_schedule(range[0], range[1], range[2], rotate, modes);
   c3h::ReplayModes rm{};
@@ -1643,7 +1650,9 @@ int c3h::search_setup_dev(c3h_ctx* ctx, const float* axis_p, const float* var, i
   // still read them
   HIPCHK(hipStreamSynchronize(ctx->stream));
   const int Dpad = (D + 7) / 8 * 8;
-  std::vector<float> pt((size_t)F * Dpad, 0.0f);
+  // + 8 zeros: compress_kernel's waves read 16 columns of a row from a multiple of 16 below D,
+  // which in the last row ends up to 8 floats past F * Dpad (D = 164: columns 160..175 of 168)
+  std::vector<float> pt((size_t)F * Dpad + 8, 0.0f);
   for (int d = 0; d < D; ++d) {
     // setSceneAxis with whitening: row d scaled by 1/sqrt(var(d)) (search.cpp:701-712)
     const float w = var ? (float)(1 / std::sqrt((double)var[d])) : 1.0f;

@@ -154,7 +154,9 @@ __global__ __launch_bounds__(kBlock) void score_kernel(ScoreLaunch a, int64_t P)
   }
   constexpr int kRowsPerPass = kBlock / SP;
   const int pp = tid & (SP - 1);
-  const int i0 = __builtin_amdgcn_readfirstlane(tid / SP);
+  // one SP-lane group per basis row: at SP = 64 the group is the wave (a uniform row, the
+  // basis through the scalar path); at SP = 16 a wave holds four groups, each on its own row
+  const int i0 = SP >= 64 ? __builtin_amdgcn_readfirstlane(tid / SP) : tid / SP;
   for (int m = 0; m < a.M; ++m) {
     const float* __restrict__ Q = a.axis_q + (int64_t)m * a.r * a.D;
     for (int i = i0; i < a.r; i += kRowsPerPass) {
@@ -1176,21 +1178,55 @@ bool score_tick_wide_ok(int D, int M, int r) {
          (int64_t)M * r <= INT32_MAX / 64 && score_tick_wide_tpp(D, M, r) >= 1;
 }
 
+// LDS a workgroup of the current device may ask for (read from the device, 0 if that fails).
+// The generic kernel's requests pass 64 KB inside its own ranges (D = 256, r = 20: 71,424 B;
+// the uncompressed 981-float row at r = 70: 67,456 B), so the first call per device also
+// raises the dynamic-LDS attribute of both instantiations to that limit.
+size_t score_lds_limit() {
+  static thread_local size_t c_lim = 0;
+  static thread_local int c_dev = -1;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev != c_dev) {
+    int lim = 0;
+    if (hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || lim < 0) lim = 0;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&score_kernel<64>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&score_kernel<16>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+    (void)hipGetLastError();  // a runtime that refuses the attribute still grants what it grants
+    c_lim = (size_t)lim;
+    c_dev = dev;
+  }
+  return c_lim;
+}
+
+// positions per workgroup of the generic kernel: 64 up to D = 256, 16 above or where 64 do
+// not fit the device's LDS; 0 when not even 16 fit (D of about 2,500 and beyond: refused)
+int score_generic_sp(int D, int r) {
+  const size_t lim = score_lds_limit();
+  if (D <= 256 && score_lds_bytes(D, r, 64) <= lim) return 64;
+  return score_lds_bytes(D, r, 16) <= lim ? 16 : 0;
+}
+
 int64_t score_blocks(const ScoreLaunch& a) {
   const int64_t P = (int64_t)a.xe * a.ye * a.ze;
   if (score_fast_ok(a.D, a.r)) return (P + kFP - 1) / kFP;
-  return a.D <= 256 ? (P + 63) / 64 : (P + 15) / 16;
+  const int sp = std::max(score_generic_sp(a.D, a.r), 1);
+  return (P + sp - 1) / sp;
 }
 
 hipError_t launch_score(const ScoreLaunch& a, hipStream_t s) {
   const int64_t P = (int64_t)a.xe * a.ye * a.ze;
   if (P <= 0) return hipSuccess;
-  if (score_fast_ok(a.D, a.r)) {
-    return hipErrorInvalidValue;  // the fast path is the sparse search (launch_sparse_search)
-  } else if (a.D <= 256) {
+  if (score_fast_ok(a.D, a.r)) return hipErrorInvalidValue;  // the fast path is the sparse search (launch_sparse_search)
+  const int sp = score_generic_sp(a.D, a.r);
+  if (sp == 64) {
     score_kernel<64><<<(unsigned)((P + 63) / 64), kBlock, score_lds_bytes(a.D, a.r, 64), s>>>(a, P);
-  } else {
+  } else if (sp == 16) {
     score_kernel<16><<<(unsigned)((P + 15) / 16), kBlock, score_lds_bytes(a.D, a.r, 16), s>>>(a, P);
+  } else {
+    return hipErrorInvalidValue;  // beyond the device's LDS (search_frames refuses it first)
   }
   return hipGetLastError();
 }
