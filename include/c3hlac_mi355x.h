@@ -537,6 +537,38 @@ int c3h_extract_vosch_frames(c3h_ctx* ctx, const float* const* pts, const int64_
                              int on_device, float leaf, float z_limit, const c3h_vosch_params* p,
                              int32_t dim /* 137 VOSCH | 1001 ConVOSCH | 20 GRSD */, int64_t row_cap, float* d_rows,
                              c3h_frame_info* info);
+/* Point clouds in, C3-HLAC rows out: limitPoint + getVoxelGrid + extractC3HLACSignature981 / 117
+ * for nframes clouds, i.e. c3h_voxelize + c3h_extract per frame, without the normals, RSD and
+ * GRSD stages of the call above (none runs, none of their buffers is allocated).  pts and n as
+ * c3h_extract_vosch_frames takes them.  p->variant is 981 or 117; thr, subdiv, offset and
+ * color_mode as for c3h_extract.  Frame i's rows start at d_rows + i * row_cap * variant
+ * (device), row h = x + y * xn + z * xn * yn in the frame's own counts, its exist_voxel_num
+ * values (the setC3HLAC rule) at d_exist + i * row_cap (device, may be NULL): byte for byte what
+ * c3h_get_features / c3h_get_exist return after c3h_voxelize + c3h_extract on that frame, voxels
+ * whose centroid lies in another cell included (the acting-cell rule, c3_hlac.cpp:349-377).  A
+ * row without a voxel is all zero bits with exist 0.  Rows are f32 whatever
+ * c3h_set_search_precision says.
+ * Frames go in batches of c3h_set_batch through the batched voxel head, always
+ * (c3h_set_vosch_head is not read), and the rows of a batch come from one sparse pass over the
+ * frames' sorted voxel lists (no dense grid): two host synchronisations per batch, none per
+ * frame.  The sums are exact integers (u32 per chunk of 1,024 voxels, 64-bit across chunks) and
+ * every bin takes one conversion and one multiply, as the dense extract does; at variant 117 the
+ * 13 neighbours of a voxel are summed per field before the products.
+ * info[i] (host, may be NULL) carries div_b, min_b, n_valid, n_occ, subdiv_b ((1, 1, 1) for one
+ * histogram: the row count is always the product), n_moved (0 where the frame has no row) and
+ * the status: 0 for a good frame and for the reference's silent-empty cases (an offset at or
+ * past the grid, a negative threshold: subdiv_b (0, 0, 0), no rows, the slot untouched);
+ * C3H_ERR_ARG for n < 0 or a null pointer with n > 0; C3H_ERR_RANGE for n >= 2^24, a cell beyond
+ * +-2^20, a div_b product above INT32_MAX or more rows than row_cap; C3H_ERR_STATE for a cloud
+ * without a valid point.  A frame with a negative status leaves its slot untouched and does not
+ * affect the others.  For the whole call, before anything is enqueued: C3H_ERR_ARG for a bad
+ * variant or color_mode, leaf <= 0 or row_cap < 1; C3H_ERR_RANGE for a batch of 2^32 points or
+ * more.  Afterwards the context holds no single-frame grid, as after a head-1
+ * c3h_extract_vosch_frames call; the single-frame voxeliser's buffers are not touched. */
+int c3h_extract_c3_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t nframes,
+                          int on_device, float leaf, float z_limit, const c3h_extract_params* p,
+                          int64_t row_cap, float* d_rows, int32_t* d_exist /* may be NULL */,
+                          c3h_frame_info* info /* may be NULL */);
 /* The head of c3h_extract_vosch_frames and c3h_run_vosch_point_frames (and of the facade's
  * SearchVOSCH / SearchGRSD::searchBatch through them): 1 = the batched voxel head, 0 = the
  * per-frame head (see above); any other value: C3H_ERR_ARG.  Nothing else reads it. */

@@ -462,6 +462,51 @@ class Context:
             views.append(flat[i * row_cap * dim:(i * row_cap + h) * dim].view(h, dim) if fi["status"][i] >= 0 else None)
         return views, fi
 
+    def extract_c3_frames(self, frames, leaf, variant, thr, row_cap, subdiv=0, offset=(0, 0, 0),
+                          color_mode=COLOR_C3_DOUBLE, z_limit=float("inf"), rows=None, exist=None):
+        """c3h_extract_c3_frames: voxelize + extract (variant 981 or 117) for a batch of point clouds
+        (a list as run_point_frames takes it, or a PointFrames), without normals, RSD or GRSD.
+        rows: a contiguous float32 device tensor of len(frames) * row_cap * variant elements to
+        write into, exist: a contiguous int32 one of len(frames) * row_cap (None: new zeroed ones; a
+        caller's tensor must be complete on its stream before the call).  Returns (views,
+        exist_views, info): views[i] the (rows of frame i, variant) view of its slot, exist_views[i]
+        the (rows of frame i,) view of its exist values (both None for a frame with a negative
+        status), info the structured array of extract_vosch_frames."""
+        import torch
+        if not isinstance(frames, PointFrames):
+            frames = self.prepare_point_frames(frames)
+        nf = len(frames)
+        row_cap, variant = int(row_cap), int(variant)
+        dev = "cuda:%d" % self.device
+        fresh = rows is None or exist is None
+        if rows is None:
+            rows = torch.zeros(max(nf * row_cap * variant, 1), dtype=torch.float32, device=dev)
+        if exist is None:
+            exist = torch.zeros(max(nf * row_cap, 1), dtype=torch.int32, device=dev)
+        for name, t, dt, need in (("rows", rows, torch.float32, nf * row_cap * variant),
+                                  ("exist", exist, torch.int32, nf * row_cap)):
+            if not hasattr(t, "data_ptr") or t.dtype != dt or not t.is_contiguous() or t.numel() < need or \
+                    t.device.type != "cuda" or (t.device.index or 0) != self.device:
+                raise ValueError("extract_c3_frames: %s must be a contiguous %s tensor of >= %d elements on %s"
+                                 % (name, dt, need, dev))
+        if fresh:  # (the fills run on torch's stream, the library on the context's: the fills first)
+            torch.cuda.current_stream(rows.device).synchronize()
+        p = self._extract_params(variant, thr, subdiv, offset, color_mode)
+        info = (_capi.FrameInfo * max(nf, 1))()
+        self._chk(self.lib.c3h_extract_c3_frames(self.h, ptr(frames.ptrs), ptr(frames.ns), nf, int(frames.on_device),
+                                                 float(leaf), float(z_limit), C.byref(p), row_cap, ptr(rows), ptr(exist),
+                                                 info), "extract_c3_frames")
+        self.synchronize()
+        fi = self._frame_info(info, nf)
+        flat, eflat = rows.view(-1), exist.view(-1)
+        views, eviews = [], []
+        for i in range(nf):
+            ok = fi["status"][i] >= 0
+            h = int(np.prod(fi["subdiv_b"][i].astype(np.int64)))
+            views.append(flat[i * row_cap * variant:(i * row_cap + h) * variant].view(h, variant) if ok else None)
+            eviews.append(eflat[i * row_cap:i * row_cap + h] if ok else None)
+        return views, eviews, fi
+
     def run_vosch_point_frames(self, frames, leaf, canvas_b, ranges, exist_threshold, dim=137, thr=(0, 0, 0), subdiv=0,
                                offset=(0, 0, 0), rsd_radius=0.01, normalize=False, normals_radius=0.02,
                                viewpoint=(0.0, 0.0, 0.0), color_mode=COLOR_C3_DOUBLE, z_limit=float("inf"),

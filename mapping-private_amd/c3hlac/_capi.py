@@ -134,6 +134,8 @@ _SIGS = {
                                        C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "c3h_extract_vosch_frames": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int, C.c_float, C.c_float, _P, C.c_int32,
                                            C.c_int64, _P, _P]),
+    "c3h_extract_c3_frames": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int, C.c_float, C.c_float, _P, C.c_int64, _P, _P,
+                                        _P]),
     "c3h_run_vosch_point_frames": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int, C.c_float, C.c_float, _P, C.c_int32,
                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P,
                                              _P]),

@@ -1,8 +1,8 @@
-// c3_sparse.h -- host arithmetic of the sparse batched C3-HLAC-981 (c3_sparse.hip): the sort key
-// that groups a batch's voxels by output row, the chunk plan of a group, the subdivision of an
-// acting cell, and the inverse of the 981-bin layout as the table the accumulate phase reads.
-// Plain C++: the kernels (c3_sparse.hip), the launch code (capi_vosch.hip) and the host check
-// (tests/c3_sparse_check.cpp) include it.
+// c3_sparse.h -- host arithmetic of the sparse batched C3-HLAC-981 / 117 (c3_sparse.hip): the sort
+// key that groups a batch's voxels by output row, the chunk plan of a group, the subdivision of an
+// acting cell, and the inverses of the 981-bin and 117-bin layouts as the tables the accumulate
+// phases read.  Plain C++: the kernels (c3_sparse.hip), the launch code (capi_vosch.hip) and the
+// host checks (tests/c3_sparse_check.cpp, tests/c3_rows_check.cpp) include it.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -129,6 +129,77 @@ struct C3sTable {
 constexpr C3sTable c3s_make_table() {
   C3sTable t{};
   for (int i = 0; i < kC3sBins; ++i) t.v[i] = c3s_pack_bin(c3s_bin_desc(i));
+  return t;
+}
+
+// ---- the 117 bins (the rotation-invariant variant) -------------------------------------------------
+// fold117's layout (c3hlac_dev.h): every first-order bin sums its 13 neighbour positions, so with
+// N[n] = sum over the 13 neighbours of a[n] and B[n] = the same of beta[n], every one of the 117 bins
+// is the sum over the group's voxels of field X times field Y of one record per voxel:
+//   field 0: the constant 1;  1 .. 6: a[c];  7 .. 12: beta[c];  13 .. 18: N[n];  19 .. 24: B[n]
+// (w117_bin_channels' numbering).  a <= 255, N <= 13 * 255 = 3,315, beta <= 1, B <= 13.
+constexpr int kC3s117Bins = 117;
+constexpr int kC3s117Fields = 25;
+constexpr int kC3s117Words = 6;   // 32-bit words of a voxel's record
+constexpr int kC3s117Slice = 64;  // voxels a wave stages at a time: a lane per voxel in the fold
+constexpr int kC3s117Waves = kC3sBlock / 64;  // a chunk per wave
+static_assert(kC3s117Bins <= 128, "two bins per lane of one wave");
+static_assert((uint64_t)13 * kC3sChunk * 65025 < ((uint64_t)1 << 32),
+              "a chunk's largest 117 sum (13 neighbours x 255 x 255 per voxel) fits u32");
+static_assert(kC3sChunk % kC3s117Slice == 0, "a chunk is whole slices");
+
+// The record: word 0: a[0 .. 3] as bytes; word 1: a[4], a[5] as bytes, beta[0 .. 5] in bits 16 .. 21,
+// bit 31 set (the constant 1); words 2 .. 4: N[0 .. 5], 16 bits each; word 5: B[0 .. 5], 4 bits each
+C3H_VF_HD constexpr int c3s117_field_word(int f) {
+  return f == 0 ? 1 : f < 7 ? (f - 1) / 4 : f < 13 ? 1 : f < 19 ? 2 + (f - 13) / 2 : 5;
+}
+C3H_VF_HD constexpr int c3s117_field_shift(int f) {
+  return f == 0 ? 31 : f < 7 ? 8 * ((f - 1) % 4) : f < 13 ? 16 + (f - 7) : f < 19 ? 16 * ((f - 13) % 2) : 4 * (f - 19);
+}
+C3H_VF_HD constexpr int c3s117_field_bits(int f) { return f == 0 ? 1 : f < 7 ? 8 : f < 13 ? 1 : f < 19 ? 16 : 4; }
+
+struct C3s117Bin {
+  int fx, fy;  // the two fields whose product the bin sums
+};
+// the inverse of fold117's layout: what bin i sums
+C3H_VF_HD constexpr C3s117Bin c3s117_bin_desc(int i) {
+  if (i < 6) return C3s117Bin{0, 1 + i};                            // zero order
+  if (i < 42) return C3s117Bin{1 + (i - 6) / 6, 13 + (i - 6) % 6};  // a[c] * N[n]
+  if (i < 63) {                                                     // the auto-product triangle a[c] * a[n], c <= n
+    int t = i - 42, c = 0;
+    while (t >= 6 - c) {
+      t -= 6 - c;
+      ++c;
+    }
+    return C3s117Bin{1 + c, 1 + c + t};
+  }
+  if (i < 69) return C3s117Bin{0, 7 + (i - 63)};                      // binarised zero order
+  if (i < 105) return C3s117Bin{7 + (i - 69) / 6, 19 + (i - 69) % 6};  // beta[c] * B[n]
+  const int t = i - 105;                                              // the twelve binarised channel pairs
+  if (t < 8) return C3s117Bin{7 + t / 4, 7 + 2 + t % 4};
+  return C3s117Bin{7 + 2 + (t - 8) / 2, 7 + 4 + (t - 8) % 2};
+}
+// the 117 bin that fold117 adds 981-bin j into
+C3H_VF_HD constexpr int c3s117_of_981(int j) {
+  const int type = j >= 495 ? 1 : 0, r = type ? j - 495 : j;
+  if (r < 6) return (type ? 63 : 0) + r;
+  if (r < 474) return (type ? 69 : 6) + 6 * ((r - 6) / 78) + ((r - 6) % 78 < 54 ? (r - 6) % 78 / 9 : ((r - 6) % 78 - 54) / 4);
+  return (type ? 105 : 42) + (r - 474);
+}
+
+// The table of the 117 accumulate phase, a word per bin:
+// word X | shift X << 3 | bits X << 8 | word Y << 13 | shift Y << 16 | bits Y << 21 | 1 << 26
+C3H_VF_HD constexpr uint32_t c3s117_pack_bin(const C3s117Bin& b) {
+  return (uint32_t)c3s117_field_word(b.fx) | (uint32_t)c3s117_field_shift(b.fx) << 3 | (uint32_t)c3s117_field_bits(b.fx) << 8 |
+         (uint32_t)c3s117_field_word(b.fy) << 13 | (uint32_t)c3s117_field_shift(b.fy) << 16 |
+         (uint32_t)c3s117_field_bits(b.fy) << 21 | 1u << 26;
+}
+struct C3s117Table {
+  uint32_t v[128];  // 0 past bin 116: both fields of 0 bits
+};
+constexpr C3s117Table c3s117_make_table() {
+  C3s117Table t{};
+  for (int i = 0; i < kC3s117Bins; ++i) t.v[i] = c3s117_pack_bin(c3s117_bin_desc(i));
   return t;
 }
 

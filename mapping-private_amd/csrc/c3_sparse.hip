@@ -1,5 +1,6 @@
-// c3_sparse.hip -- C3-HLAC-981 of a whole batch of frames from their sorted voxel lists, with no
-// dense grid: columns 20 .. 1000 of the ConVOSCH rows of the batched voxel head (capi_vosch.hip).
+// c3_sparse.hip -- C3-HLAC-981 / 117 of a whole batch of frames from their sorted voxel lists, with
+// no dense grid: columns 20 .. 1000 of the ConVOSCH rows of the batched voxel head, and the rows and
+// exist values of c3h_extract_c3_frames at either variant (capi_vosch.hip).
 //
 // Every voxel is a centre at its acting cell a = floor(centroid / leaf) - min_b (voxs_moved's
 // arithmetic), which gives its subdivision and the base of its 13 neighbours -- the semantics of
@@ -11,7 +12,7 @@
 //   (rocPRIM)   one stable radix sort of (key, voxel ordinal): a row's voxels become consecutive
 //   c3s_plan    thread = sorted position; a group's head finds the group's end, takes its chunks
 //               (at most kC3sChunk voxels each) and, with several chunks, a slot of 64-bit sums
-//   c3s_fill    zeros in columns 20 .. of every row of every good frame, a workgroup per row
+//   c3s_fill    zeros in the columns of every row of every good frame, a workgroup (117: a wave) per row
 //   c3s_accum   workgroup = chunk, per slice of kC3sSlice voxels two phases.  Stage: thread =
 //               (voxel, position), its lookup, the centre or neighbour word unpacked to channel bytes
 //               and beta bits into LDS (0 = absent).  Accumulate: thread = 4 of the 981 bins, each
@@ -22,6 +23,8 @@
 //               A group of one chunk writes (float)sum * norm981 into its row; others add their
 //               sums to the group's 64-bit slot (integer adds: exact and order-free)
 //   c3s_final   workgroup = group of several chunks: its slot into its row
+//   c3s117_accum  variant 117 in place of c3s_accum: wave = chunk; the 13 neighbours of a voxel are
+//               summed per field before the products (its own comment, below)
 //
 // The numbers of groups and chunks stay on the device: the launches take the host's upper bounds
 // (c3s_chunk_cap, c3s_multi_cap) and loop up to the device's counters.
@@ -37,6 +40,7 @@ namespace c3h {
 namespace {
 
 __device__ const C3sTable kC3sTab = c3s_make_table();
+__device__ const C3s117Table kC3s117Tab = c3s117_make_table();
 
 int c3s_blocks(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192)); }
 
@@ -142,19 +146,26 @@ __global__ __launch_bounds__(256) void c3s_plan_kernel(const uint64_t* __restric
   }
 }
 
-// a workgroup per row: 981 consecutive floats
-__global__ __launch_bounds__(256) void c3s_fill_kernel(const VfTable* __restrict__ T, int64_t htot, int dim) {
-  for (int64_t h = blockIdx.x; h < htot; h += gridDim.x) {
+// kPer rows per workgroup, 256 / kPer threads each (1: a workgroup per row of 981; 4: a wave per
+// row of 117, whose 30 quads leave most of a workgroup idle): w consecutive floats from column
+// col0, and the row's exist value
+template <int kPer>
+__global__ __launch_bounds__(256) void c3s_fill_kernel(const VfTable* __restrict__ T, int64_t htot, int w, int stride,
+                                                       int col0) {
+  constexpr int kN = 256 / kPer;
+  const int t = kPer == 1 ? (int)threadIdx.x : (int)threadIdx.x % kN;
+  const int sub = kPer == 1 ? 0 : (int)threadIdx.x / kN;  // (1: the row stays uniform over the workgroup, in scalar registers)
+  for (int64_t h = (int64_t)blockIdx.x * kPer + sub; h < htot; h += (int64_t)gridDim.x * kPer) {
     const int f = vf_frame_of(T->hpre, T->nf, h);
-    float* __restrict__ out = T->fr[f].rows + (h - T->hpre[f]) * dim + 20;
-    const int w = dim - 20;
+    float* __restrict__ out = T->fr[f].rows + (h - T->hpre[f]) * stride + col0;
+    if (t == 0 && T->fr[f].exist) T->fr[f].exist[h - T->hpre[f]] = 0;
     const int head = (int)((16 - ((uintptr_t)out & 15)) & 15) >> 2;  // floats up to a 16-byte boundary (rows are 4-byte aligned)
     const int quads = head < w ? (w - head) >> 2 : 0;
     float4* __restrict__ body = reinterpret_cast<float4*>(out + head);
-    for (int t = threadIdx.x; t < quads; t += 256) body[t] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (int q = t; q < quads; q += kN) body[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     const int tail = head + 4 * quads;
-    if ((int)threadIdx.x < head && (int)threadIdx.x < w) out[threadIdx.x] = 0.0f;
-    if (tail + (int)threadIdx.x < w) out[tail + threadIdx.x] = 0.0f;
+    if (t < head && t < w) out[t] = 0.0f;
+    if (tail + t < w) out[tail + t] = 0.0f;
   }
 }
 
@@ -176,8 +187,8 @@ __global__ __launch_bounds__(kC3sBlock) void c3s_accum_kernel(const VfTable* __r
                                                               const uint32_t* __restrict__ order,
                                                               const C3sChunk* __restrict__ chunks,
                                                               const uint32_t* __restrict__ cnt, int64_t chunk_cap,
-                                                              const uint32_t* __restrict__ lut, C3sThr thr, int dim,
-                                                              unsigned long long* __restrict__ acc) {
+                                                              const uint32_t* __restrict__ lut, C3sThr thr, int stride,
+                                                              int col0, unsigned long long* __restrict__ acc) {
   __shared__ uint64_t s_w[kC3sSlice * kC3sPos];
   __shared__ uint32_t s_ex[2];
   const int tid = threadIdx.x;
@@ -263,8 +274,10 @@ __global__ __launch_bounds__(kC3sBlock) void c3s_accum_kernel(const VfTable* __r
       __syncthreads();  // s_ex of the chunk before is read
       if (tid < 2) s_ex[tid] = sum[0];
       __syncthreads();
-      const bool ex = exist_from((float)s_ex[0], (float)s_ex[1]) != 0;
-      float* out = fr.rows + (ch.row - T->hpre[f]) * dim + 20;
+      const int32_t exv = exist_from((float)s_ex[0], (float)s_ex[1]);
+      const bool ex = exv != 0;
+      if (tid == 0 && fr.exist) fr.exist[ch.row - T->hpre[f]] = exv;
+      float* out = fr.rows + (ch.row - T->hpre[f]) * stride + col0;
 #pragma unroll
       for (int i = 0; i < kC3sBinsPerThread; ++i) {
         const int bin = tid + kC3sBlock * i;
@@ -274,24 +287,152 @@ __global__ __launch_bounds__(kC3sBlock) void c3s_accum_kernel(const VfTable* __r
   }
 }
 
+template <int kBins>
 __global__ __launch_bounds__(256) void c3s_final_kernel(const VfTable* __restrict__ T, const uint32_t* __restrict__ cnt,
                                                         int64_t multi_cap, const int64_t* __restrict__ multi_row,
-                                                        const unsigned long long* __restrict__ acc, int dim) {
+                                                        const unsigned long long* __restrict__ acc, int stride, int col0) {
   const int64_t nm = std::min<int64_t>((int64_t)cnt[1], multi_cap);
   for (int64_t m = blockIdx.x; m < nm; m += gridDim.x) {
-    const unsigned long long* hist = acc + m * kC3sBins;
+    const unsigned long long* hist = acc + m * kBins;
     const int64_t row = multi_row[m];
     const int f = vf_frame_of(T->hpre, T->nf, row);
-    float* out = T->fr[f].rows + (row - T->hpre[f]) * dim + 20;
-    const bool ex = exist_from((float)hist[0], (float)hist[1]) != 0;
-    for (int i = threadIdx.x; i < kC3sBins; i += 256) out[i] = ex ? (float)hist[i] * norm981(i) : 0.0f;
+    float* out = T->fr[f].rows + (row - T->hpre[f]) * stride + col0;
+    const int32_t exv = exist_from((float)hist[0], (float)hist[1]);
+    const bool ex = exv != 0;
+    if (threadIdx.x == 0 && T->fr[f].exist) T->fr[f].exist[row - T->hpre[f]] = exv;
+    for (int i = threadIdx.x; i < kBins; i += 256)
+      out[i] = ex ? (float)hist[i] * (kBins == kC3sBins ? norm981(i) : norm117(i)) : 0.0f;
+  }
+}
+
+// ---- the 117 bins: a chunk per wave ----------------------------------------------------------------
+// Per slice of kC3s117Slice voxels three wave-local phases.  Stage: lane = (voxel, position), as
+// above.  Fold: lane = voxel, its 13 neighbour words summed per field into the voxel's record
+// (c3_sparse.h): the factor 13 leaves the accumulate phase.  Accumulate: lane = bins lane and
+// lane + 64, each the product of two fields of the record; the lanes walk the records together.
+// Nothing is shared between the waves of a workgroup, so no workgroup barrier is met: a wave's
+// LDS writes are ordered before its own later reads by wave_lds_fence.
+__global__ __launch_bounds__(kC3sBlock) void c3s117_accum_kernel(const VfTable* __restrict__ T,
+                                                                 const uint32_t* __restrict__ order,
+                                                                 const C3sChunk* __restrict__ chunks,
+                                                                 const uint32_t* __restrict__ cnt, int64_t chunk_cap,
+                                                                 const uint32_t* __restrict__ lut, C3sThr thr, int stride,
+                                                                 int col0, unsigned long long* __restrict__ acc) {
+  __shared__ uint64_t s_w[kC3s117Waves][kC3s117Slice * kC3sPos];
+  __shared__ uint32_t s_r[kC3s117Waves][kC3s117Slice * kC3s117Words];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint64_t* const sw = s_w[wave];
+  uint32_t* const sr = s_r[wave];
+  int wx[2], sx[2], wy[2], sy[2];
+  uint32_t mx[2], my[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const uint32_t d = kC3s117Tab.v[lane + 64 * i];
+    wx[i] = (int)(d & 7u);
+    sx[i] = (int)(d >> 3 & 31u);
+    mx[i] = (1u << (d >> 8 & 31u)) - 1u;
+    wy[i] = (int)(d >> 13 & 7u);
+    sy[i] = (int)(d >> 16 & 31u);
+    my[i] = (1u << (d >> 21 & 31u)) - 1u;
+  }
+  const int64_t nchunks = std::min<int64_t>((int64_t)cnt[0], chunk_cap);
+  for (int64_t ci = (int64_t)blockIdx.x * kC3s117Waves + wave; ci < nchunks; ci += (int64_t)gridDim.x * kC3s117Waves) {
+    const C3sChunk ch = chunks[ci];
+    const int f = vf_frame_of(T->hpre, T->nf, ch.row);
+    const VfFrame& fr = T->fr[f];
+    const GrsdArgs& ga = fr.ga;
+    const int32_t* __restrict__ vk = fr.vkeys;
+    const int64_t nc = ga.nc, v0 = T->vpre[f];
+    uint32_t sum[2] = {0u, 0u};
+    for (uint32_t s0 = 0; s0 < ch.count; s0 += kC3s117Slice) {
+      const int m = (int)std::min<uint32_t>(kC3s117Slice, ch.count - s0);
+      wave_lds_fence();  // the phases of the slice before have read sw and sr
+      __builtin_amdgcn_wave_barrier();
+      for (int e = lane; e < m * kC3sPos; e += 64) {
+        const int j = e / kC3sPos, p = e - j * kC3sPos;
+        const int64_t v = (int64_t)order[ch.start + s0 + j] - v0;
+        uint64_t w = 0;
+        if (v >= 0 && v < nc) {  // (else a position of another frame: not reached)
+          const float4 c = ga.cent[v];
+          if (p == 0) {
+            w = c3s_stage_word(__float_as_uint(c.w) & 0x00ffffffu, lut, thr.v);
+          } else {
+            int a[3], rel[3];
+            c3s_acting(ga, c, a);
+            c3s_rel(p - 1, rel);
+            const int q0 = a[0] + rel[0], q1 = a[1] + rel[1], q2 = a[2] + rel[2];
+            if (q0 >= 0 && q0 < ga.div_b[0] && q1 >= 0 && q1 < ga.div_b[1] && q2 >= 0 && q2 < ga.div_b[2]) {
+              const int64_t lin = q0 + (int64_t)ga.div_b[0] * (q1 + (int64_t)ga.div_b[1] * q2);
+              const int64_t own = vk[v], off = lin - own;  // (the bounds of c3s_accum_kernel's search)
+              int64_t lo = off < 0 ? (v + off > 0 ? v + off : 0) : v, hi = off < 0 ? v : (v + off + 1 < nc ? v + off + 1 : nc);
+              while (lo < hi) {
+                const int64_t mid = (lo + hi) >> 1;
+                if (vk[mid] < lin) lo = mid + 1;
+                else hi = mid;
+              }
+              if (lo < nc && vk[lo] == lin) w = c3s_stage_word(__float_as_uint(ga.cent[lo].w) & 0x00ffffffu, lut, thr.v);
+            }
+          }
+        }
+        sw[e] = w;
+      }
+      wave_lds_fence();
+      __builtin_amdgcn_wave_barrier();
+      if (lane < m) {
+        const uint64_t* w = sw + lane * kC3sPos;
+        // the centre's staged word is words 0 and 1 of the record as it stands
+        uint32_t n[6] = {0u, 0u, 0u, 0u, 0u, 0u}, b = 0u;
+#pragma unroll
+        for (int p = 1; p < kC3sPos; ++p) {
+          const uint64_t x = w[p];
+#pragma unroll
+          for (int c = 0; c < 6; ++c) n[c] += (uint32_t)(x >> (8 * c)) & 0xffu;
+          // beta bits 48 .. 53 spread to 4-bit fields: 13 ones at most per field
+          const uint32_t be = (uint32_t)(x >> 48) & 0x3fu;
+#pragma unroll
+          for (int c = 0; c < 6; ++c) b += (be >> c & 1u) << (4 * c);
+        }
+        uint32_t* r = sr + lane * kC3s117Words;
+        r[0] = (uint32_t)w[0];
+        r[1] = (uint32_t)(w[0] >> 32);
+        r[2] = n[0] | n[1] << 16;
+        r[3] = n[2] | n[3] << 16;
+        r[4] = n[4] | n[5] << 16;
+        r[5] = b;
+      }
+      wave_lds_fence();
+      __builtin_amdgcn_wave_barrier();
+      for (int j = 0; j < m; ++j) {
+        const uint32_t* r = sr + j * kC3s117Words;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) sum[i] += ((r[wx[i]] >> sx[i]) & mx[i]) * ((r[wy[i]] >> sy[i]) & my[i]);
+      }
+    }
+    if (ch.multi >= 0) {
+      unsigned long long* slot = acc + (int64_t)ch.multi * kC3s117Bins;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int bin = lane + 64 * i;
+        if (bin < kC3s117Bins && sum[i]) atomicAdd(&slot[bin], (unsigned long long)sum[i]);
+      }
+    } else {
+      const int32_t exv = exist_from((float)__shfl(sum[0], 0, 64), (float)__shfl(sum[0], 1, 64));
+      const bool ex = exv != 0;
+      if (lane == 0 && fr.exist) fr.exist[ch.row - T->hpre[f]] = exv;
+      float* out = fr.rows + (ch.row - T->hpre[f]) * stride + col0;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int bin = lane + 64 * i;
+        if (bin < kC3s117Bins) out[bin] = ex ? (float)sum[i] * norm117(bin) : 0.0f;
+      }
+    }
   }
 }
 
 }  // namespace
 
 hipError_t launch_c3_sparse(const VfTable* d_tab, int64_t vtot, int64_t htot, const C3sBufs& b, const uint32_t* lut,
-                            const int32_t thr[3], int dim, hipStream_t s) {
+                            const int32_t thr[3], int variant, int stride, int col0, hipStream_t s) {
   const size_t n = (size_t)std::max<int64_t>(vtot, 1);
   const int bits = c3s_key_bits(htot);
   if (!b.tmp) {  // size query
@@ -300,13 +441,17 @@ hipError_t launch_c3_sparse(const VfTable* d_tab, int64_t vtot, int64_t htot, co
     *b.tmp_bytes = bytes;
     return e;
   }
+  if (variant != kC3sBins && variant != kC3s117Bins) return hipErrorInvalidValue;
   if (htot <= 0) return hipSuccess;
-  c3s_fill_kernel<<<(int)std::min<int64_t>(htot, 16384), 256, 0, s>>>(d_tab, htot, dim);
+  if (variant == kC3s117Bins)  // (4,096 workgroups: 16,384 rows a sweep, as at 981)
+    c3s_fill_kernel<4><<<(int)std::min<int64_t>((htot + 3) / 4, 4096), 256, 0, s>>>(d_tab, htot, variant, stride, col0);
+  else
+    c3s_fill_kernel<1><<<(int)std::min<int64_t>(htot, 16384), 256, 0, s>>>(d_tab, htot, variant, stride, col0);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || vtot <= 0) return e;
   const int64_t chunk_cap = c3s_chunk_cap(vtot, htot), multi_cap = c3s_multi_cap(vtot);
   e = hipMemsetAsync(b.cnt, 0, 2 * sizeof(uint32_t), s);
-  if (e == hipSuccess && multi_cap > 0) e = hipMemsetAsync(b.acc, 0, (size_t)multi_cap * kC3sBins * 8, s);
+  if (e == hipSuccess && multi_cap > 0) e = hipMemsetAsync(b.acc, 0, (size_t)multi_cap * variant * 8, s);
   if (e != hipSuccess) return e;
   c3s_keys_kernel<<<c3s_blocks(vtot), 256, 0, s>>>(d_tab, vtot, htot, b.keys, b.idx);
   e = hipGetLastError();
@@ -319,11 +464,20 @@ hipError_t launch_c3_sparse(const VfTable* d_tab, int64_t vtot, int64_t htot, co
   if (e != hipSuccess) return e;
   C3sThr t;
   for (int a = 0; a < 3; ++a) t.v[a] = thr[a];
-  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(chunk_cap, 4096));
-  c3s_accum_kernel<<<blocks, kC3sBlock, 0, s>>>(d_tab, b.idx2, b.chunks, b.cnt, chunk_cap, lut, t, dim, b.acc);
+  if (variant == kC3s117Bins) {
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((chunk_cap + kC3s117Waves - 1) / kC3s117Waves, 4096));
+    c3s117_accum_kernel<<<blocks, kC3sBlock, 0, s>>>(d_tab, b.idx2, b.chunks, b.cnt, chunk_cap, lut, t, stride, col0, b.acc);
+  } else {
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(chunk_cap, 4096));
+    c3s_accum_kernel<<<blocks, kC3sBlock, 0, s>>>(d_tab, b.idx2, b.chunks, b.cnt, chunk_cap, lut, t, stride, col0, b.acc);
+  }
   e = hipGetLastError();
   if (e != hipSuccess || multi_cap == 0) return e;
-  c3s_final_kernel<<<(int)std::min<int64_t>(multi_cap, 4096), 256, 0, s>>>(d_tab, b.cnt, multi_cap, b.multi_row, b.acc, dim);
+  const int fblocks = (int)std::min<int64_t>(multi_cap, 4096);
+  if (variant == kC3s117Bins)
+    c3s_final_kernel<kC3s117Bins><<<fblocks, 256, 0, s>>>(d_tab, b.cnt, multi_cap, b.multi_row, b.acc, stride, col0);
+  else
+    c3s_final_kernel<kC3sBins><<<fblocks, 256, 0, s>>>(d_tab, b.cnt, multi_cap, b.multi_row, b.acc, stride, col0);
   return hipGetLastError();
 }
 

@@ -462,6 +462,7 @@ struct VfFrame {
   const int32_t* vkeys;  // linear voxel index of the frame's ga.nc occupied voxels, ascending (leaf order)
   const int32_t* layout; // or, while the frame's leaf layout is at hand (a single frame), the layout itself
   float* rows;           // the frame's output rows (H x dim)
+  int32_t* exist;        // or nullptr: the frame's exist_voxel_num values (H), written by the sparse C3-HLAC pass
 };
 struct VfTable {
   int64_t ppre[kVfMaxFrames + 1];   // points
@@ -496,21 +497,23 @@ hipError_t launch_vf_vox_keys(const int32_t* layout, int64_t nvox, int64_t nc, i
 // columns 20 .. 20 + variant - 1 of rows of `stride` floats: the C3-HLAC rows c3, zeros where exist is 0
 hipError_t launch_vf_c3_cols(const float* c3, const int32_t* exist, int64_t H, int variant, int stride, float* rows,
                              hipStream_t s);
-// The sparse batched C3-HLAC-981 (c3_sparse.hip): columns 20 .. 1000 of every row of the table's
-// frames (rows of dim floats) from their centroids and voxel keys; the table is on the device.
-// Sizes: c3_sparse.h.  tmp == nullptr: size query of the sort into *tmp_bytes.
+// The sparse batched C3-HLAC (c3_sparse.hip): columns col0 .. col0 + variant - 1 (variant 981 or
+// 117) of every row of the table's frames (rows of `stride` floats) from their centroids and voxel
+// keys, and where a frame's exist pointer is set its exist_voxel_num values; the table is on the
+// device.  ConVOSCH rows: variant 981, stride 1001, col0 20.  Sizes: c3_sparse.h.  tmp == nullptr:
+// size query of the sort into *tmp_bytes.
 struct C3sBufs {
   uint64_t *keys, *keys2;     // vtot
   uint32_t *idx, *idx2;       // vtot
   uint32_t* cnt;              // 2
   C3sChunk* chunks;           // c3s_chunk_cap(vtot, htot)
   int64_t* multi_row;         // c3s_multi_cap(vtot)
-  unsigned long long* acc;    // c3s_multi_cap(vtot) x 981
+  unsigned long long* acc;    // c3s_multi_cap(vtot) x variant
   void* tmp;
   size_t* tmp_bytes;
 };
 hipError_t launch_c3_sparse(const VfTable* d_tab, int64_t vtot, int64_t htot, const C3sBufs& b, const uint32_t* lut,
-                            const int32_t thr[3], int dim, hipStream_t s);
+                            const int32_t thr[3], int variant, int stride, int col0, hipStream_t s);
 // What the host knows of one frame of the front: the normals' half after its c3h_voxelize, the
 // GRSD half after its head (capi_vosch.hip fills a VfFrame from it)
 struct VfHostFrame {
@@ -526,6 +529,7 @@ struct VfHostFrame {
   int32_t* vkeys;        // their linear voxel indices (a batch),
   const int32_t* layout; //   or the leaf layout they came from (a single frame)
   float* rows;           // H rows of the call's dim
+  int32_t* exist;        // H exist values (c3h_extract_c3_frames), or nullptr
 };
 
 // sensor_msgs/PointCloud2 bytes -> n x float4 (x, y, z, rgb bits) (ingest.hip)

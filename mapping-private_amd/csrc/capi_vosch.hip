@@ -1,7 +1,8 @@
 // capi_vosch.hip -- normals, RSD, GRSD and VOSCH rows of point clouds: the host side of the
 // front (vosch_front.hip) for one frame (c3h_compute_normals, c3h_extract_grsd,
 // c3h_extract_vosch and their getters) and for a batch of frames (c3h_extract_vosch_frames,
-// c3h_run_vosch_point_frames and theirs).
+// c3h_run_vosch_point_frames and theirs), and c3h_extract_c3_frames: the batched voxel head and the
+// sparse C3-HLAC pass without the front (c3_rows_front).
 //
 // The head of a batch gives the front what only a voxeliser can: every frame's voxel grid
 // geometry, its exact centroids in leaf order and their voxel keys and, at dim 137 (at head 0 also
@@ -125,10 +126,12 @@ void push_prefixes(c3h::VfTable* ht, int j, const c3h::VfHostFrame& fr) {
   ht->hpre[j + 1] = ht->hpre[j] + fr.H;
 }
 
-// frame j's record of the table, from its prefixes and the front's buffers (both final)
-void fill_record(c3h_ctx* ctx, c3h::VfTable* ht, int j, const c3h::VfHostFrame& fr) {
+// frame j's record of the table, from its prefixes and the front's buffers (both final).
+// grids == false (c3_rows_front): no search grid, RSD type or transition buffer exists; those
+// fields stay zero
+void fill_record(c3h_ctx* ctx, c3h::VfTable* ht, int j, const c3h::VfHostFrame& fr, bool grids = true) {
   c3h::VfFrame& t = ht->fr[j];
-  for (int which = 0; which < 2; ++which) {
+  for (int which = 0; grids && which < 2; ++which) {
     const c3h::VfGrid& vg = which ? fr.g2 : fr.g;
     c3h::NbrGrid& g = which ? t.g2 : t.g;
     g.pts = fr.pts;
@@ -147,8 +150,8 @@ void fill_record(c3h_ctx* ctx, c3h::VfTable* ht, int j, const c3h::VfHostFrame& 
   c3h::GrsdArgs& ga = t.ga;
   ga.cent = fr.cent;
   ga.nc = fr.nc;
-  ga.types = ctx->vf_types.p + ht->vpre[j];
-  ga.trans = ctx->vf_trans.p + ht->hpre[j] * 36;
+  ga.types = grids ? ctx->vf_types.p + ht->vpre[j] : nullptr;
+  ga.trans = grids ? ctx->vf_trans.p + ht->hpre[j] * 36 : nullptr;
   for (int a = 0; a < 3; ++a) {
     ga.div_b[a] = fr.gi.div_b[a];
     ga.min_b[a] = fr.gi.min_b[a];
@@ -162,6 +165,30 @@ void fill_record(c3h_ctx* ctx, c3h::VfTable* ht, int j, const c3h::VfHostFrame& 
   t.vkeys = fr.vkeys;
   t.layout = fr.layout;
   t.rows = fr.rows;
+  t.exist = fr.exist;
+}
+
+// The sparse C3-HLAC pass (c3_sparse.hip) over the uploaded table: columns col0 .. col0 + variant - 1
+// of every row, rows of `stride` floats
+int c3_sparse_run(c3h_ctx* ctx, int64_t vtot, int64_t htot, const uint32_t* lut, const int32_t thr[3], int variant,
+                  int stride, int col0) {
+  ENSURE(ctx->c3s_keys, vtot);
+  ENSURE(ctx->c3s_keys2, vtot);
+  ENSURE(ctx->c3s_idx, vtot);
+  ENSURE(ctx->c3s_idx2, vtot);
+  ENSURE(ctx->c3s_cnt, 2);
+  ENSURE(ctx->c3s_chunks, c3h::c3s_chunk_cap(vtot, htot));
+  ENSURE(ctx->c3s_multi_row, c3h::c3s_multi_cap(vtot));
+  ENSURE(ctx->c3s_acc, (size_t)c3h::c3s_multi_cap(vtot) * variant);
+  size_t sort_bytes = 0;
+  c3h::C3sBufs b{ctx->c3s_keys.p, ctx->c3s_keys2.p, ctx->c3s_idx.p,       ctx->c3s_idx2.p, ctx->c3s_cnt.p,
+                 ctx->c3s_chunks.p, ctx->c3s_multi_row.p, ctx->c3s_acc.p, nullptr,         &sort_bytes};
+  HIPCHK(c3h::launch_c3_sparse(ctx->vf_tab.p, vtot, htot, b, lut, thr, variant, stride, col0, ctx->stream));
+  ENSURE(ctx->c3s_tmp, std::max<size_t>(sort_bytes, 1));
+  sort_bytes = ctx->c3s_tmp.n;
+  b.tmp = ctx->c3s_tmp.p;
+  HIPCHK(c3h::launch_c3_sparse(ctx->vf_tab.p, vtot, htot, b, lut, thr, variant, stride, col0, ctx->stream));
+  return C3H_OK;
 }
 
 // The front over the nb frames of the host table, whose prefixes are pushed: the buffers of the
@@ -227,24 +254,7 @@ int front_run(c3h_ctx* ctx, c3h::VfTable* ht, const c3h::VfHostFrame* ff, int nb
     HIPCHK(c3h::launch_vf_grsd(ctx->vf_tab.p, vtot, ctx->stream));
     HIPCHK(c3h::launch_vf_rows(ctx->vf_tab.p, htot, ctx->vf_trans.p, q.norm, q.dim, ctx->stream));
   }
-  if (q.c3s_lut && htot > 0) {
-    ENSURE(ctx->c3s_keys, vtot);
-    ENSURE(ctx->c3s_keys2, vtot);
-    ENSURE(ctx->c3s_idx, vtot);
-    ENSURE(ctx->c3s_idx2, vtot);
-    ENSURE(ctx->c3s_cnt, 2);
-    ENSURE(ctx->c3s_chunks, c3h::c3s_chunk_cap(vtot, htot));
-    ENSURE(ctx->c3s_multi_row, c3h::c3s_multi_cap(vtot));
-    ENSURE(ctx->c3s_acc, (size_t)c3h::c3s_multi_cap(vtot) * c3h::kC3sBins);
-    size_t sort_bytes = 0;
-    c3h::C3sBufs b{ctx->c3s_keys.p, ctx->c3s_keys2.p, ctx->c3s_idx.p,       ctx->c3s_idx2.p, ctx->c3s_cnt.p,
-                   ctx->c3s_chunks.p, ctx->c3s_multi_row.p, ctx->c3s_acc.p, nullptr,         &sort_bytes};
-    HIPCHK(c3h::launch_c3_sparse(ctx->vf_tab.p, vtot, htot, b, q.c3s_lut, q.c3s_thr, q.dim, ctx->stream));
-    ENSURE(ctx->c3s_tmp, std::max<size_t>(sort_bytes, 1));
-    sort_bytes = ctx->c3s_tmp.n;
-    b.tmp = ctx->c3s_tmp.p;
-    HIPCHK(c3h::launch_c3_sparse(ctx->vf_tab.p, vtot, htot, b, q.c3s_lut, q.c3s_thr, q.dim, ctx->stream));
-  }
+  if (q.c3s_lut && htot > 0) return c3_sparse_run(ctx, vtot, htot, q.c3s_lut, q.c3s_thr, c3h::kC3sBins, q.dim, 20);
   return C3H_OK;
 }
 
@@ -357,10 +367,12 @@ const char* head_reason(int reason) {
 // synchronisations for the batch -- the bounds of the frames, then their voxel counts.  The
 // centroids and voxel keys of all frames are runs of one sort over the concatenated points; the
 // context's single-frame grid and voxeliser state are not used (vh_* buffers), only, at dim 137,
-// the extract's own buffers.  d_rows: the slot of the batch's first frame.
+// the extract's own buffers.  d_rows: the slot of the batch's first frame.  c3_only
+// (c3_rows_front): dim is the C3-HLAC variant, the rows' stride; no search grid is sized or
+// checked, and negative thresholds make every frame the reference's silent-empty case.
 int head_batch(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int nb, int on_device, float leaf, float z_limit,
                const c3h_vosch_params* p, int dim, int64_t row_cap, float* d_rows, const FrontParams& q,
-               c3h::VfTable* ht, c3h::VfHostFrame* ff, c3h_frame_info* info) {
+               c3h::VfTable* ht, c3h::VfHostFrame* ff, c3h_frame_info* info, bool c3_only = false) {
   if (!ctx->vh_host) HIPCHK(hipHostMalloc(&ctx->vh_host, sizeof(c3h_ctx::VhHost)));
   c3h_ctx::VhHost* const hh = ctx->vh_host;
   ENSURE(ctx->vh_tab, 2);
@@ -401,8 +413,10 @@ int head_batch(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int nb, 
   call.radius = p->normals_radius;
   call.rsd_dist = q.max_dist;
   call.subdiv = p->grsd.subdiv;
+  if (c3_only && (p->thr[0] < 0 || p->thr[1] < 0 || p->thr[2] < 0)) call.subdiv = -1;  // computeFeature (c3_hlac.cpp:398-401)
   for (int a = 0; a < 3; ++a) call.offset[a] = p->grsd.offset[a];
   call.row_cap = row_cap;
+  call.no_grids = c3_only ? 1 : 0;
   c3h::VhTable& tb = hh->tab[1];
   tb = ta;
   int reason[c3h::kVfMaxFrames];
@@ -642,6 +656,75 @@ int vosch_front(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t
   return C3H_OK;
 }
 
+// c3h_extract_c3_frames: the batched voxel head, then the sparse C3-HLAC pass alone -- frame i's
+// rows at d_rows + i * row_cap * variant, its exist values at d_exist + i * row_cap.  No search
+// grid, normal, RSD or GRSD buffer is touched.
+int c3_rows_front(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t nframes, int on_device, float leaf,
+                  float z_limit, const c3h_extract_params* e, int64_t row_cap, float* d_rows, int32_t* d_exist,
+                  c3h_frame_info* info) {
+  HIPCHK(hipSetDevice(ctx->device));
+  const int B = std::max(1, std::min(ctx->nbatch, c3h::kVfMaxFrames));
+  for (int b0 = 0; b0 < nframes; b0 += B) {
+    int64_t upper = 0;
+    for (int j = b0; j < std::min(nframes, b0 + B); ++j) upper += std::max<int64_t>(n[j], 0);
+    if (upper > c3h::kVfMaxPoints) return fail(ctx, C3H_ERR_RANGE, "c3 frames: a batch holds 2^32 points or more");
+  }
+  ctx->vf_nframes = 0;  // the head has no single-frame grid to leave: none is held from here on
+  ctx->have_grid = false;
+  ctx->table_valid = false;
+  ctx->vcent_valid = false;
+  ctx->normals_valid = false;
+  ctx->rsd_n = 0;
+  ctx->grid_ptr = nullptr;
+  ctx->have_feat = false;
+  ctx->feat_listed = false;
+  ctx->g_valid = false;
+  ctx->rows_valid = false;
+  const int variant = e->variant;
+  c3h_vosch_params p{};
+  p.grsd.subdiv = e->subdiv;
+  p.normals_radius = leaf;  // (unread: the head sizes no search grid)
+  p.color_mode = e->color_mode;
+  for (int a = 0; a < 3; ++a) {
+    p.grsd.offset[a] = e->offset[a];
+    p.thr[a] = e->thr[a];
+  }
+  FrontParams q{};
+  q.dim = variant;
+  const uint32_t* lut = ctx->lut.p + 256 * e->color_mode;
+  std::vector<c3h::VfHostFrame> ff((size_t)B);
+  for (int b0 = 0; b0 < nframes; b0 += B) {
+    const int nb = std::min(B, nframes - b0);
+    int64_t upper = 0;
+    for (int j = 0; j < nb; ++j) upper += std::max<int64_t>(n[b0 + j], 0);
+    // the previous batch's launches read the buffers that may grow now
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    c3h::VfTable* ht = nullptr;
+    int rc = front_begin(ctx, nb, &ht);
+    if (rc != C3H_OK) return rc;
+    if (!on_device) ENSURE(ctx->vf_pts, upper);
+    ENSURE(ctx->vf_cent, upper);
+    ENSURE(ctx->vf_vkeys, upper);
+    rc = head_batch(ctx, pts + b0, n + b0, nb, on_device, leaf, z_limit, &p, variant, row_cap,
+                    d_rows + (size_t)b0 * row_cap * variant, q, ht, ff.data(), info + b0, true);
+    if (rc != C3H_OK) return rc;
+    const int64_t vtot = ht->vpre[nb], htot = ht->hpre[nb];
+    if (htot == 0) continue;
+    ENSURE(ctx->vf_tab, 1);
+    for (int j = 0; j < nb; ++j) {
+      if (d_exist && ff[(size_t)j].H > 0) ff[(size_t)j].exist = d_exist + (size_t)(b0 + j) * row_cap;
+      fill_record(ctx, ht, j, ff[(size_t)j], false);
+    }
+    HIPCHK(hipMemcpyAsync(ctx->vf_tab.p, ht, offsetof(c3h::VfTable, fr) + (size_t)nb * sizeof(c3h::VfFrame),
+                          hipMemcpyHostToDevice, ctx->stream));
+    if (!ctx->vf_up_ev) HIPCHK(hipEventCreateWithFlags(&ctx->vf_up_ev, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(ctx->vf_up_ev, ctx->stream));
+    rc = c3_sparse_run(ctx, vtot, htot, lut, p.thr, variant, variant, 0);
+    if (rc != C3H_OK) return rc;
+  }
+  return C3H_OK;
+}
+
 int front_args(c3h_ctx* ctx, const char* who, const float* const* pts, const int64_t* n, int32_t nframes, float leaf,
                const c3h_vosch_params* p, int32_t dim) {
   if (!ctx || !p || nframes < 0 || (nframes > 0 && (!pts || !n))) return C3H_ERR_ARG;
@@ -798,6 +881,23 @@ int c3h_extract_vosch_frames(c3h_ctx* ctx, const float* const* pts, const int64_
     info = own.data();
   }
   return vosch_front(ctx, pts, n, nframes, on_device, leaf, z_limit, p, dim, row_cap, d_rows, info);
+}
+
+int c3h_extract_c3_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t nframes, int on_device,
+                          float leaf, float z_limit, const c3h_extract_params* p, int64_t row_cap, float* d_rows,
+                          int32_t* d_exist, c3h_frame_info* info) {
+  if (!ctx || !p || nframes < 0 || (nframes > 0 && (!pts || !n))) return C3H_ERR_ARG;
+  if ((p->variant != 981 && p->variant != 117) || p->color_mode < C3H_COLOR_C3_FLOAT || p->color_mode > C3H_COLOR_CHLAC)
+    return fail(ctx, C3H_ERR_ARG, "c3h_extract_c3_frames: variant must be 981 or 117, color_mode a C3H_COLOR_* value");
+  if (!(leaf > 0)) return fail(ctx, C3H_ERR_ARG, "c3h_extract_c3_frames: leaf must be > 0");
+  if (row_cap < 1 || (nframes > 0 && !d_rows)) return fail(ctx, C3H_ERR_ARG, "c3h_extract_c3_frames: row_cap / d_rows");
+  QUIESCE(ctx);
+  std::vector<c3h_frame_info> own;
+  if (!info) {
+    own.resize((size_t)std::max(nframes, 1));
+    info = own.data();
+  }
+  return c3_rows_front(ctx, pts, n, nframes, on_device, leaf, z_limit, p, row_cap, d_rows, d_exist, info);
 }
 
 int c3h_run_vosch_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t nframes, int on_device,

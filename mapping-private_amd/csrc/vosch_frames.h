@@ -176,7 +176,7 @@ enum VhReason {
   kVhBeyond,     // a valid point's cell beyond +-2^20           C3H_ERR_RANGE
   kVhNoPoint,    // no valid point                               C3H_ERR_STATE
   kVhVoxels,     // div_b product above INT32_MAX                C3H_ERR_RANGE
-  kVhCells,      // more than 2^27 search cells (either grid)    C3H_ERR_RANGE
+  kVhCells,      // more than 2^27 search cells (either grid; not where VhCall::no_grids)  C3H_ERR_RANGE
   kVhRows        // more rows than row_cap                       C3H_ERR_RANGE
 };
 // the C3H_ERR_* value of a reason (capi_vosch.hip asserts that they are the header's)
@@ -199,6 +199,8 @@ struct VhCall {          // what every frame of a call shares
   float rsd_dist;        // the RSD radius (the cell of g2 where vf_rsd_wide holds)
   int32_t subdiv, offset[3];
   int64_t row_cap;
+  int32_t no_grids;      // 1: a call without normals or RSD (c3h_extract_c3_frames): no search grid is
+                         //    sized and kVhCells never holds; g and g2 stay zero
 };
 struct VhFrameGeom {     // the host's share of a good frame
   int32_t min_b[3], max_b[3], div_b[3];
@@ -225,11 +227,11 @@ inline int vh_frame_decide(int64_t n, bool has_pointer, const VhRec& rec, const 
     out->nvox *= out->div_b[a];  // (each factor < 2^21: no overflow)
   }
   if (out->nvox > kVhMaxVoxels) return kVhVoxels;
-  if (vf_nbr_grid(out->min_b, out->max_b, q.leaf, q.radius, &out->g) != kVfOk) return kVhCells;
+  if (!q.no_grids && vf_nbr_grid(out->min_b, out->max_b, q.leaf, q.radius, &out->g) != kVfOk) return kVhCells;
   out->g2 = out->g;
   out->H = vf_subdivisions(out->div_b, q.subdiv, q.offset, out->sb, &out->inv_s);
   if (out->H > q.row_cap) return kVhRows;
-  if (out->H > 0 && vf_rsd_wide(q.rsd_dist, q.radius) &&
+  if (!q.no_grids && out->H > 0 && vf_rsd_wide(q.rsd_dist, q.radius) &&
       vf_nbr_grid(out->min_b, out->max_b, q.leaf, q.rsd_dist, &out->g2) != kVfOk)
     return kVhCells;
   return kVhGood;

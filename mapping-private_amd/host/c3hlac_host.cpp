@@ -63,6 +63,106 @@ Vector3i extract(VoxelGrid& grid, int variant, std::vector<std::vector<float> >&
   return v3(sb);
 }
 
+// An upper bound of a cloud's row count, from the box of its finite points alone: the device
+// decides the cells (and drops z >= z_limit), so every axis gets two cells of slack and the
+// offsets are left out
+int64_t rows_bound(const std::vector<PointXYZRGB>& cloud, float leaf, int subdiv) {
+  if (subdiv <= 0) return 1;
+  double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+  bool any = false;
+  for (const PointXYZRGB& q : cloud) {
+    if (!std::isfinite(q.x) || !std::isfinite(q.y) || !std::isfinite(q.z)) continue;
+    const double v[3] = {q.x, q.y, q.z};
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = any ? std::min(lo[a], v[a]) : v[a];
+      hi[a] = any ? std::max(hi[a], v[a]) : v[a];
+    }
+    any = true;
+  }
+  int64_t rows = 1;
+  for (int a = 0; a < 3; ++a) {
+    const double div = std::min(std::floor(hi[a] / leaf) - std::floor(lo[a] / leaf) + 3, 4194304.0);
+    rows *= (int64_t)std::ceil(div / subdiv) + 1;
+  }
+  return rows;
+}
+
+// the batch form of extract(): c3h_extract_c3_frames over host clouds
+std::vector<Vector3i> extract_batch(const Context& ctx, int variant, const std::vector<std::vector<PointXYZRGB> >& clouds,
+                                    std::vector<std::vector<std::vector<float> > >& feature, int thr_r, int thr_g,
+                                    int thr_b, float voxel_size, int subdiv, int ox, int oy, int oz, int color_mode,
+                                    float z_limit, std::vector<c3h_frame_info>* info_out) {
+  const int nf = (int)clouds.size();
+  feature.assign((size_t)nf, std::vector<std::vector<float> >());
+  std::vector<Vector3i> sbs((size_t)nf);
+  if (info_out) info_out->assign((size_t)nf, c3h_frame_info{});
+  if (nf == 0) return sbs;
+  if (!(voxel_size > 0)) throw Error(C3H_ERR_ARG, "extractC3HLACSignature: voxel_size must be > 0");
+  c3h_extract_params p;
+  p.variant = variant;
+  p.thr[0] = thr_r;
+  p.thr[1] = thr_g;
+  p.thr[2] = thr_b;
+  p.subdiv = subdiv;
+  p.offset[0] = ox;
+  p.offset[1] = oy;
+  p.offset[2] = oz;
+  p.color_mode = color_mode;
+  std::vector<const float*> ptrs((size_t)nf);
+  std::vector<int64_t> n((size_t)nf);
+  int64_t row_cap = 1;
+  for (int i = 0; i < nf; ++i) {
+    ptrs[(size_t)i] = clouds[(size_t)i].empty() ? nullptr : &clouds[(size_t)i][0].x;
+    n[(size_t)i] = (int64_t)clouds[(size_t)i].size();
+    row_cap = std::max(row_cap, rows_bound(clouds[(size_t)i], voxel_size, subdiv));
+  }
+  // the rows land in device memory; the HIP calls come from the runtime the kernel library has loaded
+  typedef int (*malloc_fn)(void**, size_t);
+  typedef int (*free_fn)(void*);
+  typedef int (*memcpy_fn)(void*, const void*, size_t, int);
+  const malloc_fn hipMalloc = (malloc_fn)dlsym(RTLD_DEFAULT, "hipMalloc");
+  const free_fn hipFree = (free_fn)dlsym(RTLD_DEFAULT, "hipFree");
+  const memcpy_fn hipMemcpy = (memcpy_fn)dlsym(RTLD_DEFAULT, "hipMemcpy");
+  const int hipSuccess = 0, hipMemcpyDeviceToHost = 2;
+  if (!hipMalloc || !hipFree || !hipMemcpy) throw Error(C3H_ERR_HIP, "extractC3HLACSignature: no HIP runtime loaded");
+  void* d_rows = nullptr;
+  if (hipMalloc(&d_rows, (size_t)nf * row_cap * variant * sizeof(float)) != hipSuccess)
+    throw Error(C3H_ERR_NOMEM, "extractC3HLACSignature: hipMalloc");
+  std::vector<c3h_frame_info> info((size_t)nf);
+  int rs = c3h_extract_c3_frames(ctx.get(), ptrs.data(), n.data(), nf, 0, voxel_size, z_limit, &p, row_cap, (float*)d_rows,
+                                 nullptr, info.data());
+  if (rs >= 0) rs = c3h_synchronize(ctx.get());
+  std::vector<float> flat;
+  for (int i = 0; rs >= 0 && i < nf; ++i) {
+    const c3h_frame_info& fi = info[(size_t)i];
+    if (fi.status < 0) {
+      rs = fi.status;
+      break;
+    }
+    const int64_t H = (int64_t)fi.subdiv_b[0] * fi.subdiv_b[1] * fi.subdiv_b[2];
+    // getSubdivNum() as the single-cloud function reports it: setVoxelFilter's counts
+    if (subdiv > 0 && fi.div_b[0] > ox && fi.div_b[1] > oy && fi.div_b[2] > oz) {
+      const float inv_s = 1.0 / subdiv;
+      const int off[3] = {ox, oy, oz};
+      for (int a = 0; a < 3; ++a) sbs[(size_t)i][a] = (int)std::ceil((float)((fi.div_b[a] - off[a]) * inv_s));
+    }
+    if (H <= 0) continue;
+    flat.resize((size_t)H * variant);
+    if (hipMemcpy(flat.data(), (const float*)d_rows + (size_t)i * row_cap * variant, flat.size() * sizeof(float),
+                  hipMemcpyDeviceToHost) != hipSuccess) {
+      rs = C3H_ERR_HIP;
+      break;
+    }
+    feature[(size_t)i].resize((size_t)H);
+    for (int64_t h = 0; h < H; ++h)
+      feature[(size_t)i][(size_t)h].assign(flat.begin() + h * variant, flat.begin() + (h + 1) * variant);
+  }
+  (void)hipFree(d_rows);
+  if (info_out) *info_out = info;
+  ctx.check(rs, "c3h_extract_c3_frames");
+  return sbs;
+}
+
 // Param::readParam (param.cpp:200-222): first "key value" pair whose key matches.
 template <typename T>
 bool read_param(const char* filename, const char* key, T& val) {
@@ -329,6 +429,21 @@ void extractC3HLACSignature117(VoxelGrid& grid, std::vector<float>& feature, int
   std::vector<std::vector<float> > tmp;
   extract(grid, C3H_VARIANT_117, tmp, r, g, b, voxel_size, 0, 0, 0, 0, color_mode);
   feature = tmp.empty() ? std::vector<float>() : tmp[0];
+}
+
+std::vector<Vector3i> extractC3HLACSignature981(const Context& ctx, const std::vector<std::vector<PointXYZRGB> >& clouds,
+                                                std::vector<std::vector<std::vector<float> > >& feature, int r, int g,
+                                                int b, float voxel_size, int subdiv, int ox, int oy, int oz,
+                                                int color_mode, float z_limit, std::vector<c3h_frame_info>* info) {
+  return extract_batch(ctx, C3H_VARIANT_981, clouds, feature, r, g, b, voxel_size, subdiv, ox, oy, oz, color_mode, z_limit,
+                       info);
+}
+std::vector<Vector3i> extractC3HLACSignature117(const Context& ctx, const std::vector<std::vector<PointXYZRGB> >& clouds,
+                                                std::vector<std::vector<std::vector<float> > >& feature, int r, int g,
+                                                int b, float voxel_size, int subdiv, int ox, int oy, int oz,
+                                                int color_mode, float z_limit, std::vector<c3h_frame_info>* info) {
+  return extract_batch(ctx, C3H_VARIANT_117, clouds, feature, r, g, b, voxel_size, subdiv, ox, oy, oz, color_mode, z_limit,
+                       info);
 }
 
 // extractColorCHLACSignature981/117 (color_chlac/include/color_chlac/grsd_colorCHLAC_tools.hpp:

@@ -125,6 +125,28 @@ void extractC3HLACSignature117(VoxelGrid& grid, std::vector<float>& feature, int
                                int color_threshold_g, int color_threshold_b, float voxel_size,
                                int color_mode = C3H_COLOR_C3_DOUBLE);
 
+// The batch form over several clouds: limitPoint + getVoxelGrid + extractC3HLACSignature981/117 of
+// every cloud in one c3h_extract_c3_frames call (the batched voxel head and the sparse C3-HLAC
+// pass: no per-cloud host synchronisation, no dense grid).  feature[i] and the returned counts [i]
+// are what the single-cloud function leaves for cloud i (feature[i] empty in the silent-empty
+// cases); info, where given, receives c3h_frame_info per cloud.  A cloud the call refuses (no
+// valid point, cells beyond +-2^20, ...) throws Error with its status.  Afterwards `ctx` holds no
+// single-frame grid.
+std::vector<Vector3i> extractC3HLACSignature981(const Context& ctx, const std::vector<std::vector<PointXYZRGB> >& clouds,
+                                                std::vector<std::vector<std::vector<float> > >& feature,
+                                                int color_threshold_r, int color_threshold_g, int color_threshold_b,
+                                                float voxel_size, int subdivision_size = 0, int offset_x = 0,
+                                                int offset_y = 0, int offset_z = 0, int color_mode = C3H_COLOR_C3_DOUBLE,
+                                                float z_limit = std::numeric_limits<float>::infinity(),
+                                                std::vector<c3h_frame_info>* info = nullptr);
+std::vector<Vector3i> extractC3HLACSignature117(const Context& ctx, const std::vector<std::vector<PointXYZRGB> >& clouds,
+                                                std::vector<std::vector<std::vector<float> > >& feature,
+                                                int color_threshold_r, int color_threshold_g, int color_threshold_b,
+                                                float voxel_size, int subdivision_size = 0, int offset_x = 0,
+                                                int offset_y = 0, int offset_z = 0, int color_mode = C3H_COLOR_C3_DOUBLE,
+                                                float z_limit = std::numeric_limits<float>::infinity(),
+                                                std::vector<c3h_frame_info>* info = nullptr);
+
 // ---- the pcl::Feature-style estimators (c3_hlac/include/c3_hlac/c3_hlac.h:42-220) -----
 const int DIM_C3HLAC_981_1_3 = 495;
 const int DIM_C3HLAC_981_BIN_1_3 = 486;
