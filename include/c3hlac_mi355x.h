@@ -569,6 +569,33 @@ int c3h_extract_c3_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* 
                           int on_device, float leaf, float z_limit, const c3h_extract_params* p,
                           int64_t row_cap, float* d_rows, int32_t* d_exist /* may be NULL */,
                           c3h_frame_info* info /* may be NULL */);
+/* The same rows in the learning layout (extract_c3_hlac_scene's writeFeature, pca_scene / pca_models'
+ * addData): only the rows with exist_voxel_num > 0 of all good frames, ordered by frame, then by
+ * row ordinal h.  Arguments, statuses and per-frame rules as above, but there is no row_cap per
+ * frame (a frame of any row count is good) and no row of zeros is written.  Packed row k sits at
+ * d_rows + k * variant and equals, as bytes, the row c3h_extract_c3_frames writes for that
+ * (frame, h); d_ids[k] (device, may be NULL) carries the frame's index in the call, h and the
+ * exist value.  frame_first[i] .. frame_first[i + 1] (host, nframes + 1, may be NULL) is frame i's
+ * range, empty for a failed frame, a silent-empty frame or a frame without a voxel in a row;
+ * *n_packed (host) is the total.  Order and bytes do not depend on c3h_set_batch or on the run: a
+ * row's position is the number of group heads in front of it in the sorted keys, counted per
+ * plan tile, scanned over the tiles by one workgroup and completed inside the tile from wave
+ * ballots (no atomic's return value, no workgroup waits on another).
+ * If *n_packed > packed_cap the call returns C3H_ERR_RANGE with the number needed in *n_packed;
+ * rows and ids below packed_cap are written as usual and nothing at or past it is touched.
+ * d_rows == NULL with packed_cap == 0 is the count query: the head, keys, sort, plan and pack run,
+ * no accumulate launch does, the call returns 0 with the count.  Three host synchronisations per
+ * batch: the head's two and the one that brings the batch's count (the wait between batches). */
+typedef struct {
+  int32_t frame; /* the frame's index in the call */
+  int32_t exist; /* exist_voxel_num of the row, >= 1 */
+  int64_t row;   /* h = x + y * xn + z * xn * yn in the frame's own counts */
+} c3h_packed_row; /* 16 bytes */
+int c3h_extract_c3_frames_packed(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t nframes,
+                                 int on_device, float leaf, float z_limit, const c3h_extract_params* p,
+                                 int64_t packed_cap, float* d_rows, c3h_packed_row* d_ids /* may be NULL */,
+                                 int64_t* n_packed, int64_t* frame_first /* may be NULL */,
+                                 c3h_frame_info* info /* may be NULL */);
 /* The head of c3h_extract_vosch_frames and c3h_run_vosch_point_frames (and of the facade's
  * SearchVOSCH / SearchGRSD::searchBatch through them): 1 = the batched voxel head, 0 = the
  * per-frame head (see above); any other value: C3H_ERR_ARG.  Nothing else reads it. */
@@ -682,6 +709,21 @@ int c3h_pca_set_compress(c3h_pca* pca, const float* axis, const float* var, int3
  * (pca.cpp:54-57).  Rows on the device (on_device = 1) or the host. */
 int c3h_pca_add_data(c3h_pca* pca, const float* rows, int64_t n, int64_t ld, int32_t F, int32_t rotate24,
                      int on_device);
+/* Point clouds in, addData out: the packed rows of c3h_extract_c3_frames_packed (same arguments,
+ * frame statuses and info) go straight into the accumulator -- learn_env.sh steps 2-3 and
+ * learn_obj.sh steps 1-2 in one call per set of clouds.  Per batch of c3h_set_batch frames the
+ * packed pass runs up to its plan, the count is read, a buffer of the context is sized to it
+ * (memory follows the rows that exist), the accumulate launches fill it and the rows are added as
+ * by c3h_pca_add_data (F = ld = p->variant, on the device): set_compress applies, rotate24 as
+ * there.  The object's stream waits for the context's rows and the context's next batch waits
+ * until they are read, by events, whatever streams c3h_set_stream and c3h_pca_set_stream
+ * installed.  *rows_added (host) is the number of rows; nsample grows by it (x 24 with rotate24).
+ * Before anything is enqueued: C3H_ERR_ARG if the object and the context are on different
+ * devices, and whatever c3h_pca_add_data returns for that F and rotate24 (rotate24 at 117, a
+ * differing F). */
+int c3h_pca_add_c3_frames(c3h_pca* pca, c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t nframes,
+                          int on_device, float leaf, float z_limit, const c3h_extract_params* p, int32_t rotate24,
+                          int64_t* rows_added, c3h_frame_info* info /* may be NULL */);
 /* PCA::solve(regularization_flg, regularization_nolm) (pca.cpp:73-105) + sortVecAndVal */
 int c3h_pca_solve(c3h_pca* pca, int32_t regularization_flg, float regularization_nolm);
 /* getAxis / getVariance / getMean after solve: axis dim x dim column-major (eigenvector i

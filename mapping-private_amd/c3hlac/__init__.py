@@ -507,6 +507,61 @@ class Context:
             eviews.append(eflat[i * row_cap:i * row_cap + h] if ok else None)
         return views, eviews, fi
 
+    def extract_c3_frames_packed(self, frames, leaf, variant, thr, subdiv=0, offset=(0, 0, 0),
+                                 color_mode=COLOR_C3_DOUBLE, z_limit=float("inf"), cap=None, rows=None, ids=None):
+        """c3h_extract_c3_frames_packed: the rows of extract_c3_frames with exist > 0 only, all frames
+        one after another (frame order, then row order) -- the layout pca_scene / pca_models add.
+        cap: the rows the output holds (None: a count query runs first and the tensors are sized
+        exactly).  rows: a contiguous float32 device tensor of >= cap * variant elements, ids: a
+        contiguous int32 one of >= cap * 4 (the 16-byte c3h_packed_row records: frame, exist, row as
+        two words); None: new ones.  Returns (rows[:n], frame, row, exist, frame_first, info): the
+        (n, variant) rows, per row its frame's index in the call (int32), its ordinal in the frame
+        (int64) and its exist value (int32), frame_first (numpy int64, len(frames) + 1: frame i's
+        rows are frame_first[i] .. frame_first[i + 1]) and the structured info of extract_c3_frames.
+        More rows than cap: C3HError (C3H_ERR_RANGE) with the number needed in its attribute
+        `needed`; the caller's tensors hold the rows below cap and are untouched from cap on."""
+        import torch
+        if not isinstance(frames, PointFrames):
+            frames = self.prepare_point_frames(frames)
+        nf, variant = len(frames), int(variant)
+        dev = "cuda:%d" % self.device
+        p = self._extract_params(variant, thr, subdiv, offset, color_mode)
+        info = (_capi.FrameInfo * max(nf, 1))()
+        first = np.zeros(nf + 1, np.int64)
+        n = C.c_int64(0)
+
+        def call(c, r, i):
+            return self.lib.c3h_extract_c3_frames_packed(self.h, ptr(frames.ptrs), ptr(frames.ns), nf, int(frames.on_device),
+                                                         float(leaf), float(z_limit), C.byref(p), c, ptr(r), ptr(i),
+                                                         C.byref(n), ptr(first), info)
+        if cap is None:
+            self._chk(call(0, None, None), "extract_c3_frames_packed (count)")
+            cap = n.value
+        cap = int(cap)
+        fresh = rows is None or ids is None
+        if rows is None:
+            rows = torch.zeros(max(cap * variant, 1), dtype=torch.float32, device=dev)
+        if ids is None:
+            ids = torch.zeros(max(cap * 4, 4), dtype=torch.int32, device=dev)
+        for name, t, dt, need in (("rows", rows, torch.float32, cap * variant), ("ids", ids, torch.int32, cap * 4)):
+            if not hasattr(t, "data_ptr") or t.dtype != dt or not t.is_contiguous() or t.numel() < need or \
+                    t.device.type != "cuda" or (t.device.index or 0) != self.device:
+                raise ValueError("extract_c3_frames_packed: %s must be a contiguous %s tensor of >= %d elements on %s"
+                                 % (name, dt, need, dev))
+        if fresh:  # (the fills run on torch's stream, the library on the context's: the fills first)
+            torch.cuda.current_stream(rows.device).synchronize()
+        rc = call(cap, rows if cap > 0 else None, ids if cap > 0 else None)
+        self.synchronize()
+        if rc == -5 and n.value > cap:  # C3H_ERR_RANGE for the call: the count is the number needed
+            e = _capi.C3HError("extract_c3_frames_packed failed: C3H_ERR_RANGE %d rows, cap %d" % (n.value, cap))
+            e.needed = n.value
+            raise e
+        self._chk(rc, "extract_c3_frames_packed")
+        k = min(n.value, cap)  # (cap 0 is the count query: no row, frame_first[-1] the count)
+        rec = ids.view(-1)[:4 * k].view(k, 4)
+        row = rec[:, 2:4].contiguous().view(torch.int64).view(k)
+        return rows.view(-1)[:k * variant].view(k, variant), rec[:, 0], row, rec[:, 1], first, self._frame_info(info, nf)
+
     def run_vosch_point_frames(self, frames, leaf, canvas_b, ranges, exist_threshold, dim=137, thr=(0, 0, 0), subdiv=0,
                                offset=(0, 0, 0), rsd_radius=0.01, normalize=False, normals_radius=0.02,
                                viewpoint=(0.0, 0.0, 0.0), color_mode=COLOR_C3_DOUBLE, z_limit=float("inf"),
@@ -952,6 +1007,12 @@ class PCA:
             raise _capi.C3HError("%s failed: %s %s" % (what, _capi.ERRORS.get(rc, rc), m.decode() if m else ""))
         return rc
 
+    def set_stream(self, stream_handle):
+        """c3h_pca_set_stream: a HIP stream handle (torch.cuda.Stream.cuda_stream), or None for the
+        object's own stream."""
+        self._check(self.lib.c3h_pca_set_stream(self.h, C.c_void_p(stream_handle) if stream_handle else None),
+                    "pca_set_stream")
+
     def set_compress(self, axis, var, dim):
         """compressFeature's projection: the first dim columns of axis (F, F'), whitened by var."""
         F = axis.shape[0]
@@ -972,6 +1033,23 @@ class PCA:
                     "pca_add_data")
 
     addData = add_data
+
+    def add_c3_frames(self, ctx, frames, leaf, variant, thr, subdiv=0, offset=(0, 0, 0), color_mode=COLOR_C3_DOUBLE,
+                      z_limit=float("inf"), rotate24=False):
+        """c3h_pca_add_c3_frames: voxelize + extract + addData of every row with exist > 0 for a batch
+        of point clouds (a list as Context.run_point_frames takes it, or a PointFrames) on ctx, a
+        Context on this object's device -- extract_c3_hlac_scene / extract_c3_hlac_models followed by
+        pca_scene / pca_models, without the rows leaving the device.  Returns (rows_added, info)."""
+        if not isinstance(frames, PointFrames):
+            frames = ctx.prepare_point_frames(frames)
+        nf = len(frames)
+        p = Context._extract_params(variant, thr, subdiv, offset, color_mode)
+        info = (_capi.FrameInfo * max(nf, 1))()
+        n = C.c_int64(0)
+        self._check(self.lib.c3h_pca_add_c3_frames(self.h, ctx.h, ptr(frames.ptrs), ptr(frames.ns), nf, int(frames.on_device),
+                                                   float(leaf), float(z_limit), C.byref(p), int(bool(rotate24)),
+                                                   C.byref(n), info), "pca_add_c3_frames")
+        return n.value, Context._frame_info(info, nf)
 
     def solve(self, regularization_flg=False, regularization_nolm=0.0001):
         self._check(self.lib.c3h_pca_solve(self.h, int(bool(regularization_flg)), regularization_nolm), "pca_solve")

@@ -136,6 +136,10 @@ _SIGS = {
                                            C.c_int64, _P, _P]),
     "c3h_extract_c3_frames": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int, C.c_float, C.c_float, _P, C.c_int64, _P, _P,
                                         _P]),
+    "c3h_extract_c3_frames_packed": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int, C.c_float, C.c_float, _P, C.c_int64, _P,
+                                               _P, C.POINTER(C.c_int64), _P, _P]),
+    "c3h_pca_add_c3_frames": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int, C.c_float, C.c_float, _P, C.c_int32,
+                                        C.POINTER(C.c_int64), _P]),
     "c3h_run_vosch_point_frames": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int, C.c_float, C.c_float, _P, C.c_int32,
                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P,
                                              _P]),

@@ -1,8 +1,9 @@
 // c3_sparse.h -- host arithmetic of the sparse batched C3-HLAC-981 / 117 (c3_sparse.hip): the sort
-// key that groups a batch's voxels by output row, the chunk plan of a group, the subdivision of an
-// acting cell, and the inverses of the 981-bin and 117-bin layouts as the tables the accumulate
-// phases read.  Plain C++: the kernels (c3_sparse.hip), the launch code (capi_vosch.hip) and the
-// host checks (tests/c3_sparse_check.cpp, tests/c3_rows_check.cpp) include it.
+// key that groups a batch's voxels by output row, the chunk plan of a group, the packed position of a
+// group (the packed output), the subdivision of an acting cell, and the inverses of the 981-bin and
+// 117-bin layouts as the tables the accumulate phases read.  Plain C++: the kernels (c3_sparse.hip),
+// the launch code (capi_vosch.hip) and the host checks (tests/c3_sparse_check.cpp,
+// tests/c3_rows_check.cpp, tests/packed_rows_check.cpp) include it.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -48,7 +49,58 @@ struct C3sChunk {
   uint32_t count;   // voxels, 1 .. kC3sChunk
   int32_t multi;    // the ordinal of its group among those of several chunks, or -1
   int32_t pad;
+  int64_t slot;     // packed mode: the packed position of its group's row in the call; else -1
 };
+
+// ---- the packed output ---------------------------------------------------------------------------
+// c3h_extract_c3_frames_packed writes only the rows that hold a voxel, in the order of the sorted
+// keys (frame, then row ordinal): the packed position of a group is the number of group heads in
+// front of it.  A head is a sorted position whose key is a row's and differs from the key before.
+// The plan works on tiles of kC3sPlanTile sorted positions, a workgroup of 256 threads a tile,
+// thread tid at the positions t * tile + it * 256 + tid (it = 0 .. kC3sPlanItems - 1).  Three
+// launches give every head its ordinal without a workgroup waiting on another: the heads of every
+// tile (c3s_pack_count), an exclusive scan of those totals by one workgroup (c3s_pack_scan), and in
+// the plan the heads in front within the tile: the whole rounds before `it` and, of round `it`,
+// the waves before this one and the lanes of this wave's ballot below this lane.
+constexpr int kC3sPlanItems = 8;
+constexpr int kC3sPlanTile = 256 * kC3sPlanItems;
+constexpr int kC3sPlanWaves = 4;
+
+struct C3sPackedRow {  // c3h_packed_row (c3hlac_mi355x.h)
+  int32_t frame;       // the frame's index in the call
+  int32_t exist;       // exist_voxel_num of the row
+  int64_t row;         // the row's ordinal in its frame
+};
+static_assert(sizeof(C3sPackedRow) == 16, "the id record is 16 bytes");
+
+C3H_VF_HD inline bool c3s_head(const uint64_t* keys, int64_t i, uint64_t none) {
+  const uint64_t k = keys[i];
+  return k < none && (i == 0 || keys[i - 1] != k);
+}
+C3H_VF_HD inline int64_t c3s_plan_tiles(int64_t vtot) { return (vtot + kC3sPlanTile - 1) / kC3sPlanTile; }
+C3H_VF_HD inline int64_t c3s_plan_pos(int64_t t, int it, int tid) { return t * kC3sPlanTile + it * 256 + tid; }
+// heads of the tile in front of (round it, wave, lane): wave_heads[it' * kC3sPlanWaves + w] = the
+// heads of wave w in round it', ballot = the head lanes of this wave in round it
+C3H_VF_HD inline uint32_t c3s_pack_local(const uint32_t* wave_heads, int it, int wave, uint64_t ballot, int lane) {
+  uint32_t n = 0;
+  for (int j = 0; j < it * kC3sPlanWaves + wave; ++j) n += wave_heads[j];
+  const uint64_t below = ballot & (((uint64_t)1 << lane) - 1);
+  for (uint64_t b = below; b; b &= b - 1) ++n;
+  return n;
+}
+// the packed position in the call: the rows of the batches before, the tiles before, the heads before
+C3H_VF_HD inline int64_t c3s_pack_slot(int64_t base, int64_t tile_base, uint32_t local) { return base + tile_base + local; }
+// a row at `slot` is written (and its chunks are computed) only inside the caller's capacity
+C3H_VF_HD inline bool c3s_slot_written(int64_t slot, int64_t cap) { return slot < cap; }
+
+// exist_from (c3hlac_dev.h) on the host: exist_voxel_num from the sums of bins 0 and 1
+inline int32_t c3s_exist_of(float s0, float s1) {
+  const float n0 = (float)(1 / 255.0);
+  const float f0 = s0 * n0;
+  const float f1 = s1 * n0;
+  const float t = (f0 + f1) * 2.0f;
+  return (int32_t)((double)t + 0.001);
+}
 
 // ---- the subdivision of an acting cell ---------------------------------------------------------
 // c3_hlac.cpp:349-356 as offcell_contrib (c3hlac.hip) has it: a = floor(c / leaf) - min_b.  One

@@ -28,6 +28,17 @@
 //
 // The numbers of groups and chunks stay on the device: the launches take the host's upper bounds
 // (c3s_chunk_cap, c3s_multi_cap) and loop up to the device's counters.
+//
+// Packed mode (c3h_extract_c3_frames_packed, c3h_pca_add_c3_frames; launch_c3_packed): only the rows
+// that hold a voxel are written, one after another in the order of the sorted keys.  No fill.
+//   c3s_pack_count   workgroup = plan tile: its group heads
+//   c3s_pack_scan    one workgroup: the exclusive scan of the tiles' heads
+//   c3s_pack_frames  workgroup = frame: the heads in front of its first key (the host reads them)
+//   c3s_plan<true>   a head's packed position from the scan and its tile's ballots, into its chunks
+//                    (and multi_slot), -1 past the caller's capacity; frame and row of its id record
+//   c3s_accum<true>, c3s117_accum<true>, c3s_final<., true>  skip what has no slot; the epilogues
+//                    write rows + slot * variant and the id record's exist value
+// Every step is a launch boundary: no workgroup waits on another, no ordinal is an atomic's return.
 #include <algorithm>
 
 #include <hip/hip_runtime.h>
@@ -67,17 +78,25 @@ __global__ __launch_bounds__(256) void c3s_keys_kernel(const VfTable* __restrict
 // cnt[0]: chunks, cnt[1]: groups of several chunks.  A workgroup plans a tile of kC3sPlanTile
 // sorted positions and takes the chunk slots of all its heads with one atomic (a prefix sum over
 // its threads): an atomic per wave, all on one address, was 0.45 ms of a 64-frame call.
-constexpr int kC3sPlanItems = 8;
-constexpr int kC3sPlanTile = 256 * kC3sPlanItems;
+// kPacked: every head also takes its packed position (c3_sparse.h: the tiles before from
+// tile_base, the heads before within the tile from the waves' ballots), which its chunks and, with
+// several chunks, multi_slot carry, or -1 where the position lies at or past pack_cap; the frame
+// and row of its id record are written here.
+template <bool kPacked>
 __global__ __launch_bounds__(256) void c3s_plan_kernel(const uint64_t* __restrict__ keys, int64_t vtot, int64_t htot,
                                                        int64_t chunk_cap, int64_t multi_cap, uint32_t* __restrict__ cnt,
-                                                       C3sChunk* __restrict__ chunks, int64_t* __restrict__ multi_row) {
+                                                       C3sChunk* __restrict__ chunks, int64_t* __restrict__ multi_row,
+                                                       const int64_t* __restrict__ tile_base, int64_t pack_base,
+                                                       int64_t* __restrict__ multi_slot, const VfTable* __restrict__ T,
+                                                       C3sPackedRow* __restrict__ ids, int64_t pack_cap, int frame0) {
   __shared__ uint32_t s_wave[4];
   __shared__ uint32_t s_base;
+  __shared__ uint32_t s_heads[kPacked ? kC3sPlanItems * kC3sPlanWaves : 1];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t ntiles = (vtot + kC3sPlanTile - 1) / kC3sPlanTile;
   for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {  // (uniform over the workgroup)
     int64_t len[kC3sPlanItems];
+    uint64_t bal[kPacked ? kC3sPlanItems : 1];
     uint32_t mine = 0;
 #pragma unroll
     for (int it = 0; it < kC3sPlanItems; ++it) {
@@ -99,6 +118,10 @@ __global__ __launch_bounds__(256) void c3s_plan_kernel(const uint64_t* __restric
       }
       len[it] = L;
       mine += (uint32_t)c3s_chunks(L);
+      if constexpr (kPacked) {
+        bal[it] = __ballot(L > 0);
+        if (lane == 0) s_heads[it * kC3sPlanWaves + wave] = (uint32_t)__popcll(bal[it]);
+      }
     }
     uint32_t incl = mine;
 #pragma unroll
@@ -122,6 +145,17 @@ __global__ __launch_bounds__(256) void c3s_plan_kernel(const uint64_t* __restric
       if (nch == 0) continue;
       const int64_t i = t * kC3sPlanTile + it * 256 + tid;
       const uint64_t k = keys[i];
+      int64_t slot = -1;
+      if constexpr (kPacked) {
+        slot = c3s_pack_slot(pack_base, tile_base[t], c3s_pack_local(s_heads, it, wave, bal[it], lane));
+        if (!c3s_slot_written(slot, pack_cap)) {
+          slot = -1;  // past the caller's capacity: its chunks are skipped, nothing of it is written
+        } else if (ids) {  // (the row's exist value: the epilogue that sums it)
+          const int f = vf_frame_of(T->hpre, T->nf, (int64_t)k);
+          ids[slot].frame = frame0 + f;
+          ids[slot].row = (int64_t)k - T->hpre[f];
+        }
+      }
       int32_t multi = -1;
       bool ok = true;
       if (nch > 1) {
@@ -130,6 +164,7 @@ __global__ __launch_bounds__(256) void c3s_plan_kernel(const uint64_t* __restric
         if (ok) {
           multi = (int32_t)m;
           multi_row[m] = (int64_t)k;
+          if constexpr (kPacked) multi_slot[m] = slot;
         }
       }
       for (int64_t c = 0; ok && c < nch && base + c < chunk_cap; ++c) {
@@ -139,11 +174,88 @@ __global__ __launch_bounds__(256) void c3s_plan_kernel(const uint64_t* __restric
         ch.count = (uint32_t)c3s_chunk_len(L, c);
         ch.multi = multi;
         ch.pad = 0;
+        ch.slot = slot;
         chunks[base + c] = ch;
       }
       base += nch;
     }
+    if constexpr (kPacked) __syncthreads();  // s_heads is read: the next tile writes it
   }
+}
+
+// ---- the packed position of a group (c3_sparse.h) ----------------------------------------------------
+// the heads of every plan tile
+__global__ __launch_bounds__(256) void c3s_pack_count_kernel(const uint64_t* __restrict__ keys, int64_t vtot, int64_t htot,
+                                                             uint32_t* __restrict__ tile_heads) {
+  __shared__ uint32_t s_n[kC3sPlanWaves];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t ntiles = c3s_plan_tiles(vtot);
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {  // (uniform over the workgroup)
+    uint32_t n = 0;
+#pragma unroll
+    for (int it = 0; it < kC3sPlanItems; ++it) {
+      const int64_t i = c3s_plan_pos(t, it, tid);
+      n += (uint32_t)__popcll(__ballot(i < vtot && c3s_head(keys, i, c3s_none(htot))));
+    }
+    if (lane == 0) s_n[wave] = n;
+    __syncthreads();
+    if (tid == 0) tile_heads[t] = s_n[0] + s_n[1] + s_n[2] + s_n[3];
+    __syncthreads();  // s_n is read: the next tile writes it
+  }
+}
+
+// One workgroup: tile_base[t] = the heads of the tiles before t, tile_base[ntiles] their number.  The
+// tiles go 256 at a time, the carry in a register of every thread.
+__global__ __launch_bounds__(256) void c3s_pack_scan_kernel(const uint32_t* __restrict__ tile_heads, int64_t ntiles,
+                                                            int64_t* __restrict__ tile_base) {
+  __shared__ uint32_t s_wave[kC3sPlanWaves];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int64_t carry = 0;
+  for (int64_t b0 = 0; b0 < ntiles; b0 += 256) {
+    const int64_t i = b0 + tid;
+    const uint32_t v = i < ntiles ? tile_heads[i] : 0u;
+    uint32_t incl = v;  // (a round holds at most 256 * kC3sPlanTile heads)
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t y = __shfl_up(incl, d, 64);
+      if (lane >= d) incl += y;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    uint32_t pre = 0;
+    for (int w = 0; w < wave; ++w) pre += s_wave[w];
+    if (i < ntiles) tile_base[i] = carry + pre + incl - v;
+    carry += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    __syncthreads();  // s_wave is read: the next round writes it
+  }
+  if (tid == 0) tile_base[ntiles] = carry;
+}
+
+// Workgroup f = 0 .. nf: frame_first[f] = the heads in front of frame f's first key, i.e. in front of
+// the first sorted position whose key is hpre[f] or more (hpre[nf] = htot, the "none" key: all heads)
+__global__ __launch_bounds__(256) void c3s_pack_frames_kernel(const VfTable* __restrict__ T, const uint64_t* __restrict__ keys,
+                                                              int64_t vtot, const int64_t* __restrict__ tile_base,
+                                                              int64_t* __restrict__ frame_first) {
+  __shared__ uint32_t s_n[kC3sPlanWaves];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int f = blockIdx.x;
+  const uint64_t key = (uint64_t)T->hpre[f], none = c3s_none(T->hpre[T->nf]);
+  int64_t lo = 0, hi = vtot;  // (the same search in every thread)
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (keys[mid] < key) lo = mid + 1;
+    else hi = mid;
+  }
+  const int64_t t = lo / kC3sPlanTile;
+  uint32_t n = 0;
+#pragma unroll
+  for (int it = 0; it < kC3sPlanItems; ++it) {
+    const int64_t i = c3s_plan_pos(t, it, tid);
+    n += (uint32_t)__popcll(__ballot(i < lo && c3s_head(keys, i, none)));
+  }
+  if (lane == 0) s_n[wave] = n;
+  __syncthreads();
+  if (tid == 0) frame_first[f] = tile_base[t] + (s_n[0] + s_n[1] + s_n[2] + s_n[3]);  // (lo == vtot on a tile's edge: t = ntiles, no head counted)
 }
 
 // kPer rows per workgroup, 256 / kPer threads each (1: a workgroup per row of 981; 4: a wave per
@@ -183,12 +295,22 @@ struct C3sThr {
   int v[3];
 };
 
+// Where the epilogues write in packed mode: row `slot` at rows + slot * variant and its exist value
+// into the id record at ids + slot (ids may be nullptr).  The plan left slot -1 past the capacity.
+struct C3sOut {
+  float* rows;
+  C3sPackedRow* ids;
+};
+
+// kPacked: a chunk without a slot is skipped whole; the epilogue of a group of one chunk writes to
+// po, not into the frame's slot
+template <bool kPacked>
 __global__ __launch_bounds__(kC3sBlock) void c3s_accum_kernel(const VfTable* __restrict__ T,
                                                               const uint32_t* __restrict__ order,
                                                               const C3sChunk* __restrict__ chunks,
                                                               const uint32_t* __restrict__ cnt, int64_t chunk_cap,
                                                               const uint32_t* __restrict__ lut, C3sThr thr, int stride,
-                                                              int col0, unsigned long long* __restrict__ acc) {
+                                                              int col0, unsigned long long* __restrict__ acc, C3sOut po) {
   __shared__ uint64_t s_w[kC3sSlice * kC3sPos];
   __shared__ uint32_t s_ex[2];
   const int tid = threadIdx.x;
@@ -211,6 +333,9 @@ __global__ __launch_bounds__(kC3sBlock) void c3s_accum_kernel(const VfTable* __r
   const int64_t nchunks = std::min<int64_t>((int64_t)cnt[0], chunk_cap);
   for (int64_t ci = blockIdx.x; ci < nchunks; ci += gridDim.x) {
     const C3sChunk ch = chunks[ci];
+    if constexpr (kPacked) {
+      if (ch.slot < 0) continue;  // (uniform over the workgroup)
+    }
     const int f = vf_frame_of(T->hpre, T->nf, ch.row);
     const VfFrame& fr = T->fr[f];
     const GrsdArgs& ga = fr.ga;
@@ -276,8 +401,14 @@ __global__ __launch_bounds__(kC3sBlock) void c3s_accum_kernel(const VfTable* __r
       __syncthreads();
       const int32_t exv = exist_from((float)s_ex[0], (float)s_ex[1]);
       const bool ex = exv != 0;
-      if (tid == 0 && fr.exist) fr.exist[ch.row - T->hpre[f]] = exv;
-      float* out = fr.rows + (ch.row - T->hpre[f]) * stride + col0;
+      float* out;
+      if constexpr (kPacked) {
+        if (tid == 0 && po.ids) po.ids[ch.slot].exist = exv;
+        out = po.rows + ch.slot * kC3sBins;
+      } else {
+        if (tid == 0 && fr.exist) fr.exist[ch.row - T->hpre[f]] = exv;
+        out = fr.rows + (ch.row - T->hpre[f]) * stride + col0;
+      }
 #pragma unroll
       for (int i = 0; i < kC3sBinsPerThread; ++i) {
         const int bin = tid + kC3sBlock * i;
@@ -287,19 +418,28 @@ __global__ __launch_bounds__(kC3sBlock) void c3s_accum_kernel(const VfTable* __r
   }
 }
 
-template <int kBins>
+template <int kBins, bool kPacked>
 __global__ __launch_bounds__(256) void c3s_final_kernel(const VfTable* __restrict__ T, const uint32_t* __restrict__ cnt,
                                                         int64_t multi_cap, const int64_t* __restrict__ multi_row,
-                                                        const unsigned long long* __restrict__ acc, int stride, int col0) {
+                                                        const unsigned long long* __restrict__ acc, int stride, int col0,
+                                                        const int64_t* __restrict__ multi_slot, C3sOut po) {
   const int64_t nm = std::min<int64_t>((int64_t)cnt[1], multi_cap);
   for (int64_t m = blockIdx.x; m < nm; m += gridDim.x) {
     const unsigned long long* hist = acc + m * kBins;
     const int64_t row = multi_row[m];
     const int f = vf_frame_of(T->hpre, T->nf, row);
-    float* out = T->fr[f].rows + (row - T->hpre[f]) * stride + col0;
     const int32_t exv = exist_from((float)hist[0], (float)hist[1]);
     const bool ex = exv != 0;
-    if (threadIdx.x == 0 && T->fr[f].exist) T->fr[f].exist[row - T->hpre[f]] = exv;
+    float* out;
+    if constexpr (kPacked) {
+      const int64_t slot = multi_slot[m];
+      if (slot < 0) continue;  // (its chunks added nothing)
+      if (threadIdx.x == 0 && po.ids) po.ids[slot].exist = exv;
+      out = po.rows + slot * kBins;
+    } else {
+      if (threadIdx.x == 0 && T->fr[f].exist) T->fr[f].exist[row - T->hpre[f]] = exv;
+      out = T->fr[f].rows + (row - T->hpre[f]) * stride + col0;
+    }
     for (int i = threadIdx.x; i < kBins; i += 256)
       out[i] = ex ? (float)hist[i] * (kBins == kC3sBins ? norm981(i) : norm117(i)) : 0.0f;
   }
@@ -311,13 +451,14 @@ __global__ __launch_bounds__(256) void c3s_final_kernel(const VfTable* __restric
 // (c3_sparse.h): the factor 13 leaves the accumulate phase.  Accumulate: lane = bins lane and
 // lane + 64, each the product of two fields of the record; the lanes walk the records together.
 // Nothing is shared between the waves of a workgroup, so no workgroup barrier is met: a wave's
-// LDS writes are ordered before its own later reads by wave_lds_fence.
+// LDS writes are ordered before its own later reads by wave_lds_fence.  kPacked: as c3s_accum_kernel.
+template <bool kPacked>
 __global__ __launch_bounds__(kC3sBlock) void c3s117_accum_kernel(const VfTable* __restrict__ T,
                                                                  const uint32_t* __restrict__ order,
                                                                  const C3sChunk* __restrict__ chunks,
                                                                  const uint32_t* __restrict__ cnt, int64_t chunk_cap,
                                                                  const uint32_t* __restrict__ lut, C3sThr thr, int stride,
-                                                                 int col0, unsigned long long* __restrict__ acc) {
+                                                                 int col0, unsigned long long* __restrict__ acc, C3sOut po) {
   __shared__ uint64_t s_w[kC3s117Waves][kC3s117Slice * kC3sPos];
   __shared__ uint32_t s_r[kC3s117Waves][kC3s117Slice * kC3s117Words];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -338,6 +479,9 @@ __global__ __launch_bounds__(kC3sBlock) void c3s117_accum_kernel(const VfTable* 
   const int64_t nchunks = std::min<int64_t>((int64_t)cnt[0], chunk_cap);
   for (int64_t ci = (int64_t)blockIdx.x * kC3s117Waves + wave; ci < nchunks; ci += (int64_t)gridDim.x * kC3s117Waves) {
     const C3sChunk ch = chunks[ci];
+    if constexpr (kPacked) {
+      if (ch.slot < 0) continue;  // (uniform over the wave; no workgroup barrier is met)
+    }
     const int f = vf_frame_of(T->hpre, T->nf, ch.row);
     const VfFrame& fr = T->fr[f];
     const GrsdArgs& ga = fr.ga;
@@ -418,8 +562,14 @@ __global__ __launch_bounds__(kC3sBlock) void c3s117_accum_kernel(const VfTable* 
     } else {
       const int32_t exv = exist_from((float)__shfl(sum[0], 0, 64), (float)__shfl(sum[0], 1, 64));
       const bool ex = exv != 0;
-      if (lane == 0 && fr.exist) fr.exist[ch.row - T->hpre[f]] = exv;
-      float* out = fr.rows + (ch.row - T->hpre[f]) * stride + col0;
+      float* out;
+      if constexpr (kPacked) {
+        if (lane == 0 && po.ids) po.ids[ch.slot].exist = exv;
+        out = po.rows + ch.slot * kC3s117Bins;
+      } else {
+        if (lane == 0 && fr.exist) fr.exist[ch.row - T->hpre[f]] = exv;
+        out = fr.rows + (ch.row - T->hpre[f]) * stride + col0;
+      }
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int bin = lane + 64 * i;
@@ -429,10 +579,64 @@ __global__ __launch_bounds__(kC3sBlock) void c3s117_accum_kernel(const VfTable* 
   }
 }
 
+// The packed pass (C3sPack, c3h_internal.h).  kC3sPackPlan: keys, sort, the heads of the tiles, their
+// scan, the frames' first positions, the plan with slots.  kC3sPackAccum: the accumulate launches
+// with packed epilogues.  c3s_fill_kernel is not launched: no row it would zero is written.
+hipError_t launch_c3_packed(const VfTable* d_tab, int64_t vtot, int64_t htot, const C3sBufs& b, const uint32_t* lut,
+                            const int32_t thr[3], int variant, hipStream_t s, const C3sPack& pk) {
+  if (vtot <= 0) return hipErrorInvalidValue;  // (a batch with a row has a voxel)
+  const int64_t chunk_cap = c3s_chunk_cap(vtot, htot), multi_cap = c3s_multi_cap(vtot), ntiles = c3s_plan_tiles(vtot);
+  const int tblocks = (int)std::min<int64_t>(ntiles, 8192);
+  hipError_t e = hipSuccess;
+  if (pk.phases & kC3sPackPlan) {
+    e = hipMemsetAsync(b.cnt, 0, 2 * sizeof(uint32_t), s);
+    if (e == hipSuccess && multi_cap > 0) e = hipMemsetAsync(b.acc, 0, (size_t)multi_cap * variant * 8, s);
+    if (e != hipSuccess) return e;
+    c3s_keys_kernel<<<c3s_blocks(vtot), 256, 0, s>>>(d_tab, vtot, htot, b.keys, b.idx);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    size_t bytes = *b.tmp_bytes;
+    e = rocprim::radix_sort_pairs(b.tmp, bytes, b.keys, b.keys2, b.idx, b.idx2, (size_t)vtot, 0, c3s_key_bits(htot), s);
+    if (e != hipSuccess) return e;
+    c3s_pack_count_kernel<<<tblocks, 256, 0, s>>>(b.keys2, vtot, htot, pk.tile_heads);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    c3s_pack_scan_kernel<<<1, 256, 0, s>>>(pk.tile_heads, ntiles, pk.tile_base);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    c3s_pack_frames_kernel<<<pk.nf + 1, 256, 0, s>>>(d_tab, b.keys2, vtot, pk.tile_base, pk.frame_first);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    c3s_plan_kernel<true><<<tblocks, 256, 0, s>>>(b.keys2, vtot, htot, chunk_cap, multi_cap, b.cnt, b.chunks, b.multi_row,
+                                                   pk.tile_base, pk.base, pk.multi_slot, d_tab, pk.ids, pk.cap, pk.frame0);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if (!(pk.phases & kC3sPackAccum)) return e;
+  const C3sOut po{pk.rows, pk.ids};
+  C3sThr t;
+  for (int a = 0; a < 3; ++a) t.v[a] = thr[a];
+  if (variant == kC3s117Bins) {
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((chunk_cap + kC3s117Waves - 1) / kC3s117Waves, 4096));
+    c3s117_accum_kernel<true><<<blocks, kC3sBlock, 0, s>>>(d_tab, b.idx2, b.chunks, b.cnt, chunk_cap, lut, t, 0, 0, b.acc, po);
+  } else {
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(chunk_cap, 4096));
+    c3s_accum_kernel<true><<<blocks, kC3sBlock, 0, s>>>(d_tab, b.idx2, b.chunks, b.cnt, chunk_cap, lut, t, 0, 0, b.acc, po);
+  }
+  e = hipGetLastError();
+  if (e != hipSuccess || multi_cap == 0) return e;
+  const int fblocks = (int)std::min<int64_t>(multi_cap, 4096);
+  if (variant == kC3s117Bins)
+    c3s_final_kernel<kC3s117Bins, true><<<fblocks, 256, 0, s>>>(d_tab, b.cnt, multi_cap, b.multi_row, b.acc, 0, 0, pk.multi_slot, po);
+  else
+    c3s_final_kernel<kC3sBins, true><<<fblocks, 256, 0, s>>>(d_tab, b.cnt, multi_cap, b.multi_row, b.acc, 0, 0, pk.multi_slot, po);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t launch_c3_sparse(const VfTable* d_tab, int64_t vtot, int64_t htot, const C3sBufs& b, const uint32_t* lut,
-                            const int32_t thr[3], int variant, int stride, int col0, hipStream_t s) {
+                            const int32_t thr[3], int variant, int stride, int col0, hipStream_t s, const C3sPack* pk) {
   const size_t n = (size_t)std::max<int64_t>(vtot, 1);
   const int bits = c3s_key_bits(htot);
   if (!b.tmp) {  // size query
@@ -443,6 +647,7 @@ hipError_t launch_c3_sparse(const VfTable* d_tab, int64_t vtot, int64_t htot, co
   }
   if (variant != kC3sBins && variant != kC3s117Bins) return hipErrorInvalidValue;
   if (htot <= 0) return hipSuccess;
+  if (pk) return launch_c3_packed(d_tab, vtot, htot, b, lut, thr, variant, s, *pk);
   if (variant == kC3s117Bins)  // (4,096 workgroups: 16,384 rows a sweep, as at 981)
     c3s_fill_kernel<4><<<(int)std::min<int64_t>((htot + 3) / 4, 4096), 256, 0, s>>>(d_tab, htot, variant, stride, col0);
   else
@@ -459,25 +664,26 @@ hipError_t launch_c3_sparse(const VfTable* d_tab, int64_t vtot, int64_t htot, co
   size_t bytes = *b.tmp_bytes;
   e = rocprim::radix_sort_pairs(b.tmp, bytes, b.keys, b.keys2, b.idx, b.idx2, (size_t)vtot, 0, bits, s);
   if (e != hipSuccess) return e;
-  c3s_plan_kernel<<<(int)std::min<int64_t>((vtot + kC3sPlanTile - 1) / kC3sPlanTile, 8192), 256, 0, s>>>(b.keys2, vtot, htot, chunk_cap, multi_cap, b.cnt, b.chunks, b.multi_row);
+  c3s_plan_kernel<false><<<(int)std::min<int64_t>((vtot + kC3sPlanTile - 1) / kC3sPlanTile, 8192), 256, 0, s>>>(b.keys2, vtot, htot, chunk_cap, multi_cap, b.cnt, b.chunks, b.multi_row, nullptr, 0, nullptr, nullptr, nullptr, 0, 0);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
+  const C3sOut none{nullptr, nullptr};
   C3sThr t;
   for (int a = 0; a < 3; ++a) t.v[a] = thr[a];
   if (variant == kC3s117Bins) {
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((chunk_cap + kC3s117Waves - 1) / kC3s117Waves, 4096));
-    c3s117_accum_kernel<<<blocks, kC3sBlock, 0, s>>>(d_tab, b.idx2, b.chunks, b.cnt, chunk_cap, lut, t, stride, col0, b.acc);
+    c3s117_accum_kernel<false><<<blocks, kC3sBlock, 0, s>>>(d_tab, b.idx2, b.chunks, b.cnt, chunk_cap, lut, t, stride, col0, b.acc, none);
   } else {
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(chunk_cap, 4096));
-    c3s_accum_kernel<<<blocks, kC3sBlock, 0, s>>>(d_tab, b.idx2, b.chunks, b.cnt, chunk_cap, lut, t, stride, col0, b.acc);
+    c3s_accum_kernel<false><<<blocks, kC3sBlock, 0, s>>>(d_tab, b.idx2, b.chunks, b.cnt, chunk_cap, lut, t, stride, col0, b.acc, none);
   }
   e = hipGetLastError();
   if (e != hipSuccess || multi_cap == 0) return e;
   const int fblocks = (int)std::min<int64_t>(multi_cap, 4096);
   if (variant == kC3s117Bins)
-    c3s_final_kernel<kC3s117Bins><<<fblocks, 256, 0, s>>>(d_tab, b.cnt, multi_cap, b.multi_row, b.acc, stride, col0);
+    c3s_final_kernel<kC3s117Bins, false><<<fblocks, 256, 0, s>>>(d_tab, b.cnt, multi_cap, b.multi_row, b.acc, stride, col0, nullptr, none);
   else
-    c3s_final_kernel<kC3sBins><<<fblocks, 256, 0, s>>>(d_tab, b.cnt, multi_cap, b.multi_row, b.acc, stride, col0);
+    c3s_final_kernel<kC3sBins, false><<<fblocks, 256, 0, s>>>(d_tab, b.cnt, multi_cap, b.multi_row, b.acc, stride, col0, nullptr, none);
   return hipGetLastError();
 }
 

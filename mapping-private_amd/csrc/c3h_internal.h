@@ -512,8 +512,32 @@ struct C3sBufs {
   void* tmp;
   size_t* tmp_bytes;
 };
+// Packed mode (pk != nullptr): no row of the table's frames is written.  The rows that hold a voxel
+// go, in the order of the sorted keys, to rows + slot * variant and their id records to ids + slot
+// (ids may be nullptr) where slot < cap; slot = base + the row's ordinal among the batch's non-empty
+// rows.  phases: kC3sPackPlan runs the keys, the sort, the pack and the plan and leaves
+// frame_first[0 .. nf] (device: the batch's packed rows in front of every frame, [nf] their
+// number); kC3sPackAccum the accumulate launches of a planned batch.  stride and col0 are not read.
+enum { kC3sPackPlan = 1, kC3sPackAccum = 2 };
+struct C3sPack {
+  float* rows;
+  C3sPackedRow* ids;
+  int64_t cap, base;
+  int frame0;                 // the call's index of the batch's first frame
+  int nf;                     // frames of the batch
+  int phases;
+  uint32_t* tile_heads;       // c3s_plan_tiles(vtot)
+  int64_t* tile_base;         // c3s_plan_tiles(vtot) + 1
+  int64_t* multi_slot;        // c3s_multi_cap(vtot)
+  int64_t* frame_first;       // nf + 1
+};
 hipError_t launch_c3_sparse(const VfTable* d_tab, int64_t vtot, int64_t htot, const C3sBufs& b, const uint32_t* lut,
-                            const int32_t thr[3], int variant, int stride, int col0, hipStream_t s);
+                            const int32_t thr[3], int variant, int stride, int col0, hipStream_t s,
+                            const C3sPack* pk = nullptr);
+// the PCA object (pca.hip) as c3h_pca_add_c3_frames (capi_vosch.hip) sees it
+int pca_device(const c3h_pca* p);
+hipStream_t pca_stream(const c3h_pca* p);
+void pca_set_error(c3h_pca* p, const std::string& msg);
 // What the host knows of one frame of the front: the normals' half after its c3h_voxelize, the
 // GRSD half after its head (capi_vosch.hip fills a VfFrame from it)
 struct VfHostFrame {
@@ -805,6 +829,15 @@ struct c3h_ctx {
   c3h::DevBuf<int64_t> c3s_multi_row;
   c3h::DevBuf<unsigned long long> c3s_acc;
   c3h::DevBuf<uint8_t> c3s_tmp;
+  // its packed output (c3h_extract_c3_frames_packed, c3h_pca_add_c3_frames)
+  c3h::DevBuf<uint32_t> c3s_tile_heads;  // the plan tiles' heads
+  c3h::DevBuf<int64_t> c3s_tile_base;    // their exclusive scan
+  c3h::DevBuf<int64_t> c3s_multi_slot;   // beside c3s_multi_row
+  c3h::DevBuf<int64_t> c3s_frame_first;  // nb + 1: the batch's packed rows in front of every frame
+  int64_t* c3s_pack_host = nullptr;      // pinned: its readback
+  c3h::DevBuf<float> c3s_pca_rows;       // c3h_pca_add_c3_frames: a batch's packed rows
+  hipEvent_t c3s_rows_ev = nullptr;      // the rows are written (the PCA's stream waits),
+  hipEvent_t c3s_read_ev = nullptr;      // the SYRK has read them (the context's stream waits)
   // voxeliser state (voxelize.hip): toroidal accumulators, entry / grid-word lists by
   // epoch parity, counters; the grid words the previous frame wrote are cleared by the next
   c3h::DevBuf<ulonglong2> vacc;

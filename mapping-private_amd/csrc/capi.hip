@@ -15,32 +15,12 @@
 #include <cstring>
 
 #include "capi_host.h"
+#include "colour_lut.h"
 #include "occ_sched.h"
 
 using namespace c3h;
 
 namespace {
-
-// setColor as a 256-entry table of packed (r | r_ << 8) channel pairs, one table per
-// C3H_COLOR_* mode (color_chlac.hpp:148-179)
-void host_lut(int color_mode, uint32_t* out) {
-  const float angle_norm = M_PI / 510;  // color_chlac/include/color_chlac/color_chlac.h:9
-  for (int v = 0; v < 256; ++v) {
-    const float a = v * angle_norm;
-    int s, c;
-    if (color_mode == C3H_COLOR_CHLAC) {  // ColorCHLAC: r_ = 255 - r
-      s = v;
-      c = 255 - v;
-    } else if (color_mode == C3H_COLOR_C3_DOUBLE) {
-      s = (int)(255 * std::sin((double)a));
-      c = (int)(255 * std::cos((double)a));
-    } else {
-      s = (int)(255 * sinf(a));
-      c = (int)(255 * cosf(a));
-    }
-    out[v] = (uint32_t)s | ((uint32_t)c << 8);
-  }
-}
 
 // search.cpp:218-251
 void get_range(int mode, int r1, int r2, int r3, int* xr, int* yr, int* zr) {
@@ -687,6 +667,9 @@ void c3h_destroy(c3h_ctx* ctx) {
   if (ctx->vf_htab) (void)hipHostFree(ctx->vf_htab);
   if (ctx->vh_host) (void)hipHostFree(ctx->vh_host);
   if (ctx->vf_up_ev) (void)hipEventDestroy(ctx->vf_up_ev);
+  if (ctx->c3s_pack_host) (void)hipHostFree(ctx->c3s_pack_host);
+  if (ctx->c3s_rows_ev) (void)hipEventDestroy(ctx->c3s_rows_ev);
+  if (ctx->c3s_read_ev) (void)hipEventDestroy(ctx->c3s_read_ev);
   if (ctx->h_recs) (void)hipHostFree(ctx->h_recs);
   if (ctx->h_dl) (void)hipHostFree(ctx->h_dl);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);

@@ -2,7 +2,8 @@
 // front (vosch_front.hip) for one frame (c3h_compute_normals, c3h_extract_grsd,
 // c3h_extract_vosch and their getters) and for a batch of frames (c3h_extract_vosch_frames,
 // c3h_run_vosch_point_frames and theirs), and c3h_extract_c3_frames: the batched voxel head and the
-// sparse C3-HLAC pass without the front (c3_rows_front).
+// sparse C3-HLAC pass without the front (c3_rows_front), with c3h_extract_c3_frames_packed and
+// c3h_pca_add_c3_frames on its packed mode (only the rows that hold a voxel, one after another).
 //
 // The head of a batch gives the front what only a voxeliser can: every frame's voxel grid
 // geometry, its exact centroids in leaf order and their voxel keys and, at dim 137 (at head 0 also
@@ -169,9 +170,20 @@ void fill_record(c3h_ctx* ctx, c3h::VfTable* ht, int j, const c3h::VfHostFrame& 
 }
 
 // The sparse C3-HLAC pass (c3_sparse.hip) over the uploaded table: columns col0 .. col0 + variant - 1
-// of every row, rows of `stride` floats
+// of every row, rows of `stride` floats.  pk (packed mode, c3h_internal.h): its rows, ids, cap, base,
+// frame0, nf and phases are the caller's, the context's pack buffers are filled in here.
 int c3_sparse_run(c3h_ctx* ctx, int64_t vtot, int64_t htot, const uint32_t* lut, const int32_t thr[3], int variant,
-                  int stride, int col0) {
+                  int stride, int col0, c3h::C3sPack* pk = nullptr) {
+  if (pk) {
+    ENSURE(ctx->c3s_tile_heads, c3h::c3s_plan_tiles(vtot));
+    ENSURE(ctx->c3s_tile_base, c3h::c3s_plan_tiles(vtot) + 1);
+    ENSURE(ctx->c3s_multi_slot, c3h::c3s_multi_cap(vtot));
+    ENSURE(ctx->c3s_frame_first, c3h::kVfMaxFrames + 1);
+    pk->tile_heads = ctx->c3s_tile_heads.p;
+    pk->tile_base = ctx->c3s_tile_base.p;
+    pk->multi_slot = ctx->c3s_multi_slot.p;
+    pk->frame_first = ctx->c3s_frame_first.p;
+  }
   ENSURE(ctx->c3s_keys, vtot);
   ENSURE(ctx->c3s_keys2, vtot);
   ENSURE(ctx->c3s_idx, vtot);
@@ -187,7 +199,7 @@ int c3_sparse_run(c3h_ctx* ctx, int64_t vtot, int64_t htot, const uint32_t* lut,
   ENSURE(ctx->c3s_tmp, std::max<size_t>(sort_bytes, 1));
   sort_bytes = ctx->c3s_tmp.n;
   b.tmp = ctx->c3s_tmp.p;
-  HIPCHK(c3h::launch_c3_sparse(ctx->vf_tab.p, vtot, htot, b, lut, thr, variant, stride, col0, ctx->stream));
+  HIPCHK(c3h::launch_c3_sparse(ctx->vf_tab.p, vtot, htot, b, lut, thr, variant, stride, col0, ctx->stream, pk));
   return C3H_OK;
 }
 
@@ -656,12 +668,70 @@ int vosch_front(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t
   return C3H_OK;
 }
 
+// The packed mode of c3_rows_front: only the rows that hold a voxel, in the order (frame, row).
+// c3h_extract_c3_frames_packed: rows / ids / cap are the caller's (rows == nullptr: the count alone).
+// c3h_pca_add_c3_frames (pca != nullptr): per batch the count is read, a buffer of the context is
+// sized to it, the rows go to the PCA object's accumulator.
+struct PackedCall {
+  int64_t cap = 0;
+  float* rows = nullptr;
+  c3h::C3sPackedRow* ids = nullptr;
+  int64_t* frame_first = nullptr;  // host, nframes + 1, may be nullptr
+  c3h_pca* pca = nullptr;
+  int rotate24 = 0;
+  int64_t total = 0;               // out: the rows of the call
+  // the batch whose frame_first readback is in flight
+  int pend_b0 = 0, pend_nb = 0;
+};
+
+// After a wait on the context's stream: the pending batch's packed rows in front of its frames
+void packed_take(c3h_ctx* ctx, PackedCall* pc) {
+  for (int j = 0; j < pc->pend_nb; ++j)
+    if (pc->frame_first) pc->frame_first[pc->pend_b0 + j] = pc->total + ctx->c3s_pack_host[j];
+  if (pc->pend_nb) pc->total += ctx->c3s_pack_host[pc->pend_nb];
+  pc->pend_nb = 0;
+}
+
+// One batch of c3h_pca_add_c3_frames behind its plan: the count, the buffer, the accumulate launches,
+// the hand-over.  The PCA's stream waits for the rows (c3s_rows_ev); the context's stream waits,
+// before it writes the buffer again, until the SYRK has read them (c3s_read_ev).
+int packed_to_pca(c3h_ctx* ctx, PackedCall* pc, c3h::C3sPack* pk, int64_t vtot, int64_t htot, const uint32_t* lut,
+                  const int32_t thr[3], int variant) {
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const int64_t count = ctx->c3s_pack_host[pk->nf];
+  pc->pend_nb = 0;
+  if (count == 0) return C3H_OK;
+  const bool first = !ctx->c3s_rows_ev;
+  if (first) {
+    HIPCHK(hipEventCreateWithFlags(&ctx->c3s_rows_ev, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&ctx->c3s_read_ev, hipEventDisableTiming));
+  }
+  if (!first) {
+    if (ctx->c3s_pca_rows.n < (size_t)count * variant) HIPCHK(hipEventSynchronize(ctx->c3s_read_ev));  // the buffer is freed
+    else HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->c3s_read_ev, 0));
+  }
+  ENSURE(ctx->c3s_pca_rows, (size_t)count * variant);
+  pk->rows = ctx->c3s_pca_rows.p;
+  pk->phases = c3h::kC3sPackAccum;
+  int rc = c3_sparse_run(ctx, vtot, htot, lut, thr, variant, variant, 0, pk);
+  if (rc != C3H_OK) return rc;
+  hipStream_t ps = c3h::pca_stream(pc->pca);
+  HIPCHK(hipEventRecord(ctx->c3s_rows_ev, ctx->stream));
+  HIPCHK(hipStreamWaitEvent(ps, ctx->c3s_rows_ev, 0));
+  rc = c3h_pca_add_data(pc->pca, ctx->c3s_pca_rows.p, count, variant, variant, pc->rotate24, 1);
+  // (recorded whatever add_data returned: the next wait must not meet an event never recorded)
+  HIPCHK(hipEventRecord(ctx->c3s_read_ev, ps));
+  if (rc != C3H_OK) return fail(ctx, rc, std::string("c3h_pca_add_c3_frames: ") + c3h_pca_last_error(pc->pca));
+  pc->total += count;
+  return C3H_OK;
+}
+
 // c3h_extract_c3_frames: the batched voxel head, then the sparse C3-HLAC pass alone -- frame i's
 // rows at d_rows + i * row_cap * variant, its exist values at d_exist + i * row_cap.  No search
-// grid, normal, RSD or GRSD buffer is touched.
+// grid, normal, RSD or GRSD buffer is touched.  pc: the packed mode (row_cap INT64_MAX, no d_rows).
 int c3_rows_front(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t nframes, int on_device, float leaf,
                   float z_limit, const c3h_extract_params* e, int64_t row_cap, float* d_rows, int32_t* d_exist,
-                  c3h_frame_info* info) {
+                  c3h_frame_info* info, PackedCall* pc = nullptr) {
   HIPCHK(hipSetDevice(ctx->device));
   const int B = std::max(1, std::min(ctx->nbatch, c3h::kVfMaxFrames));
   for (int b0 = 0; b0 < nframes; b0 += B) {
@@ -699,6 +769,7 @@ int c3_rows_front(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32
     for (int j = 0; j < nb; ++j) upper += std::max<int64_t>(n[b0 + j], 0);
     // the previous batch's launches read the buffers that may grow now
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (pc) packed_take(ctx, pc);  // (that wait also brought the previous batch's count)
     c3h::VfTable* ht = nullptr;
     int rc = front_begin(ctx, nb, &ht);
     if (rc != C3H_OK) return rc;
@@ -706,12 +777,16 @@ int c3_rows_front(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32
     ENSURE(ctx->vf_cent, upper);
     ENSURE(ctx->vf_vkeys, upper);
     rc = head_batch(ctx, pts + b0, n + b0, nb, on_device, leaf, z_limit, &p, variant, row_cap,
-                    d_rows + (size_t)b0 * row_cap * variant, q, ht, ff.data(), info + b0, true);
+                    pc ? nullptr : d_rows + (size_t)b0 * row_cap * variant, q, ht, ff.data(), info + b0, true);
     if (rc != C3H_OK) return rc;
     const int64_t vtot = ht->vpre[nb], htot = ht->hpre[nb];
-    if (htot == 0) continue;
+    if (htot == 0 || (pc && vtot == 0)) {
+      for (int j = 0; pc && pc->frame_first && j < nb; ++j) pc->frame_first[b0 + j] = pc->total;
+      continue;
+    }
     ENSURE(ctx->vf_tab, 1);
     for (int j = 0; j < nb; ++j) {
+      if (pc) ff[(size_t)j].rows = nullptr;  // (no frame has a slot)
       if (d_exist && ff[(size_t)j].H > 0) ff[(size_t)j].exist = d_exist + (size_t)(b0 + j) * row_cap;
       fill_record(ctx, ht, j, ff[(size_t)j], false);
     }
@@ -719,8 +794,35 @@ int c3_rows_front(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32
                           hipMemcpyHostToDevice, ctx->stream));
     if (!ctx->vf_up_ev) HIPCHK(hipEventCreateWithFlags(&ctx->vf_up_ev, hipEventDisableTiming));
     HIPCHK(hipEventRecord(ctx->vf_up_ev, ctx->stream));
-    rc = c3_sparse_run(ctx, vtot, htot, lut, p.thr, variant, variant, 0);
+    if (!pc) {
+      rc = c3_sparse_run(ctx, vtot, htot, lut, p.thr, variant, variant, 0);
+      if (rc != C3H_OK) return rc;
+      continue;
+    }
+    if (!ctx->c3s_pack_host) HIPCHK(hipHostMalloc(&ctx->c3s_pack_host, (c3h::kVfMaxFrames + 1) * sizeof(int64_t)));
+    c3h::C3sPack pk{};
+    pk.rows = pc->rows;
+    pk.ids = pc->ids;
+    pk.cap = pc->pca ? INT64_MAX : pc->cap;  // (the PCA's buffer is sized to the count: every row has a place)
+    pk.base = pc->pca ? 0 : pc->total;
+    pk.frame0 = b0;
+    pk.nf = nb;
+    pk.phases = pc->pca || !pc->rows ? c3h::kC3sPackPlan : c3h::kC3sPackPlan | c3h::kC3sPackAccum;
+    rc = c3_sparse_run(ctx, vtot, htot, lut, p.thr, variant, variant, 0, &pk);
     if (rc != C3H_OK) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->c3s_pack_host, ctx->c3s_frame_first.p, (size_t)(nb + 1) * sizeof(int64_t),
+                          hipMemcpyDeviceToHost, ctx->stream));
+    pc->pend_b0 = b0;
+    pc->pend_nb = nb;
+    if (pc->pca) {
+      rc = packed_to_pca(ctx, pc, &pk, vtot, htot, lut, p.thr, variant);
+      if (rc != C3H_OK) return rc;
+    }
+  }
+  if (pc) {
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    packed_take(ctx, pc);
+    if (pc->frame_first) pc->frame_first[nframes] = pc->total;
   }
   return C3H_OK;
 }
@@ -898,6 +1000,84 @@ int c3h_extract_c3_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* 
     info = own.data();
   }
   return c3_rows_front(ctx, pts, n, nframes, on_device, leaf, z_limit, p, row_cap, d_rows, d_exist, info);
+}
+
+static_assert(sizeof(c3h_packed_row) == sizeof(c3h::C3sPackedRow) && offsetof(c3h_packed_row, frame) == offsetof(c3h::C3sPackedRow, frame) &&
+                  offsetof(c3h_packed_row, exist) == offsetof(c3h::C3sPackedRow, exist) &&
+                  offsetof(c3h_packed_row, row) == offsetof(c3h::C3sPackedRow, row),
+              "c3h_packed_row is the kernels' id record");
+
+// the whole-call checks of c3h_extract_c3_frames, for the packed entry points too
+static int c3_frames_args(c3h_ctx* ctx, const char* who, const float* const* pts, const int64_t* n, int32_t nframes, float leaf,
+                          const c3h_extract_params* p) {
+  if (!ctx || !p || nframes < 0 || (nframes > 0 && (!pts || !n))) return C3H_ERR_ARG;
+  if ((p->variant != 981 && p->variant != 117) || p->color_mode < C3H_COLOR_C3_FLOAT || p->color_mode > C3H_COLOR_CHLAC)
+    return fail(ctx, C3H_ERR_ARG, std::string(who) + ": variant must be 981 or 117, color_mode a C3H_COLOR_* value");
+  if (!(leaf > 0)) return fail(ctx, C3H_ERR_ARG, std::string(who) + ": leaf must be > 0");
+  return C3H_OK;
+}
+
+int c3h_extract_c3_frames_packed(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t nframes, int on_device,
+                                 float leaf, float z_limit, const c3h_extract_params* p, int64_t packed_cap, float* d_rows,
+                                 c3h_packed_row* d_ids, int64_t* n_packed, int64_t* frame_first, c3h_frame_info* info) {
+  const char* who = "c3h_extract_c3_frames_packed";
+  int rc = c3_frames_args(ctx, who, pts, n, nframes, leaf, p);
+  if (rc != C3H_OK) return rc;
+  if (!n_packed || packed_cap < 0 || (packed_cap > 0 && !d_rows) || (!d_rows && d_ids))
+    return fail(ctx, C3H_ERR_ARG, std::string(who) + ": packed_cap / d_rows / n_packed");
+  QUIESCE(ctx);
+  std::vector<c3h_frame_info> own;
+  if (!info) {
+    own.resize((size_t)std::max(nframes, 1));
+    info = own.data();
+  }
+  PackedCall pc;
+  pc.cap = packed_cap;
+  pc.rows = d_rows;
+  pc.ids = reinterpret_cast<c3h::C3sPackedRow*>(d_ids);
+  pc.frame_first = frame_first;
+  *n_packed = 0;
+  rc = c3_rows_front(ctx, pts, n, nframes, on_device, leaf, z_limit, p, INT64_MAX, nullptr, nullptr, info, &pc);
+  if (rc != C3H_OK) return rc;
+  *n_packed = pc.total;
+  if (d_rows && pc.total > packed_cap)
+    return fail(ctx, C3H_ERR_RANGE, std::string(who) + ": more rows than packed_cap (n_packed holds the number needed)");
+  return C3H_OK;
+}
+
+int c3h_pca_add_c3_frames(c3h_pca* pca, c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t nframes,
+                          int on_device, float leaf, float z_limit, const c3h_extract_params* p, int32_t rotate24,
+                          int64_t* rows_added, c3h_frame_info* info) {
+  const char* who = "c3h_pca_add_c3_frames";
+  if (!pca) return C3H_ERR_ARG;
+  int rc = c3_frames_args(ctx, who, pts, n, nframes, leaf, p);
+  if (rc != C3H_OK) {
+    if (ctx) c3h::pca_set_error(pca, std::string(who) + ": " + c3h_last_error(ctx));
+    return rc;
+  }
+  if (!rows_added) return fail(ctx, C3H_ERR_ARG, std::string(who) + ": rows_added");
+  *rows_added = 0;
+  if (c3h::pca_device(pca) != ctx->device) {
+    c3h::pca_set_error(pca, std::string(who) + ": the PCA object and the context are on different devices");
+    return fail(ctx, C3H_ERR_ARG, std::string(who) + ": the PCA object and the context are on different devices");
+  }
+  // what c3h_pca_add_data refuses (a differing F, rotate24 at 117) it refuses here, with its status
+  // and message, before anything is enqueued: an add of no rows
+  rc = c3h_pca_add_data(pca, nullptr, 0, p->variant, p->variant, rotate24, 1);
+  if (rc != C3H_OK) return fail(ctx, rc, std::string(who) + ": " + c3h_pca_last_error(pca));
+  QUIESCE(ctx);
+  std::vector<c3h_frame_info> own;
+  if (!info) {
+    own.resize((size_t)std::max(nframes, 1));
+    info = own.data();
+  }
+  PackedCall pc;
+  pc.pca = pca;
+  pc.rotate24 = rotate24;
+  rc = c3_rows_front(ctx, pts, n, nframes, on_device, leaf, z_limit, p, INT64_MAX, nullptr, nullptr, info, &pc);
+  *rows_added = pc.total;
+  if (rc != C3H_OK) c3h::pca_set_error(pca, c3h_last_error(ctx));
+  return rc;
 }
 
 int c3h_run_vosch_point_frames(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t nframes, int on_device,

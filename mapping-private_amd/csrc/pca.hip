@@ -398,6 +398,11 @@ int syrk_rows(c3h_pca* p, const float* X, int64_t n, int64_t ld, DevBuf<double>&
 
 }  // namespace
 
+// what c3h_pca_add_c3_frames (capi_vosch.hip) needs of the object
+int c3h::pca_device(const c3h_pca* p) { return p->device; }
+hipStream_t c3h::pca_stream(const c3h_pca* p) { return p->stream; }
+void c3h::pca_set_error(c3h_pca* p, const std::string& msg) { p->err = msg; }
+
 extern "C" {
 
 int c3h_pca_create(int hip_device, int32_t mean_flg, c3h_pca** out) {

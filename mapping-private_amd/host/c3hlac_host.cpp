@@ -592,6 +592,39 @@ void PCA::addDataRotated24(const std::vector<float>& feature) {
   if (rows_[1].size() >= kPcaBatchRows * F_) flush(true);
 }
 
+int64_t PCA::addClouds(const Context& ctx, const std::vector<std::vector<PointXYZRGB> >& clouds, int variant, int thr_r,
+                       int thr_g, int thr_b, float voxel_size, int subdiv, const Vector3i& offsets, int color_mode,
+                       bool rotated24) {
+  const int nf = (int)clouds.size();
+  if (nf == 0) return 0;
+  if (F_ == -1) F_ = variant;
+  if (variant != F_) throw Error(C3H_ERR_ARG, "PCA::addData: vector size differs");
+  flush(false);  // the pending host rows first: addData's order
+  flush(true);
+  c3h_extract_params p;
+  p.variant = variant;
+  p.thr[0] = thr_r;
+  p.thr[1] = thr_g;
+  p.thr[2] = thr_b;
+  p.subdiv = subdiv;
+  for (int a = 0; a < 3; ++a) p.offset[a] = offsets[a];
+  p.color_mode = color_mode;
+  std::vector<const float*> ptrs((size_t)nf);
+  std::vector<int64_t> n((size_t)nf);
+  for (int i = 0; i < nf; ++i) {
+    ptrs[(size_t)i] = clouds[(size_t)i].empty() ? nullptr : &clouds[(size_t)i][0].x;
+    n[(size_t)i] = (int64_t)clouds[(size_t)i].size();
+  }
+  std::vector<c3h_frame_info> info((size_t)nf);
+  int64_t added = 0;
+  const int rc = c3h_pca_add_c3_frames(handle(), ctx.get(), ptrs.data(), n.data(), nf, 0, voxel_size,
+                                       std::numeric_limits<float>::infinity(), &p, rotated24 ? 1 : 0, &added, info.data());
+  if (rc != C3H_OK) throw Error(rc, std::string("PCA::addClouds: ") + c3h_pca_last_error(h_));
+  for (int i = 0; i < nf; ++i)
+    if (info[(size_t)i].status < 0) throw Error(info[(size_t)i].status, "PCA::addClouds: cloud " + std::to_string(i) + " was refused");
+  return added;
+}
+
 void PCA::setCompress(const MatrixXf& axis, const std::vector<float>& variance, int dim, bool whitening) {
   const int F = axis.rows;
   if (dim <= 0 || dim > axis.cols || (whitening && (int)variance.size() < dim))

@@ -366,6 +366,16 @@ class PCA {
   // (addDataRotated24 = the 24 addData calls of pca_models.cpp:109-171)
   void setCompress(const MatrixXf& axis, const std::vector<float>& variance, int dim, bool whitening = true);
   void addDataRotated24(const std::vector<float>& feature);
+  // extract_c3_hlac_scene + pca_scene (rotated24: extract_c3_hlac_models + pca_models) over several
+  // clouds in one c3h_pca_add_c3_frames call: limitPoint + getVoxelGrid + extractC3HLACSignature981 /
+  // 117 of every cloud, and addData (addDataRotated24) of every row writeFeature would keep
+  // (exist_voxel_num > 0), without the rows leaving the device.  `ctx` must be on this object's
+  // device and holds no single-frame grid afterwards.  Returns the rows added; a cloud the call
+  // refuses throws Error with its status (the rows of the other clouds stay added).
+  int64_t addClouds(const Context& ctx, const std::vector<std::vector<PointXYZRGB> >& clouds, int variant,
+                    int color_threshold_r, int color_threshold_g, int color_threshold_b, float voxel_size,
+                    int subdivision_size = 0, const Vector3i& offsets = Vector3i(),
+                    int color_mode = C3H_COLOR_C3_DOUBLE, bool rotated24 = false);
   void solve(bool regularization_flg = false, float regularization_nolm = 0.0001f);
   void read(const char* filename, bool ascii = false);
   void write(const char* filename, bool ascii = false) const;
