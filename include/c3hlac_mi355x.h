@@ -504,14 +504,15 @@ int c3h_stream_feature_frames(c3h_ctx* ctx, const float* const* d_feat, const in
  *     stable radix sort of (frame, voxel) keys whose runs are the voxels with their points in
  *     input order, one thread per run for the centroid, and a second synchronisation for the
  *     frames' voxel counts: two per batch, whatever the number of frames.  Host clouds are
- *     staged once, straight into the batch's concatenation.  At dim 137 the C3-HLAC-117 extract
- *     still runs frame by frame, on a grid buffer of the head's own that holds one frame's
- *     words at a time, and writes columns 20 .. 136.  At dim 1001 the C3-HLAC-981 columns of the
- *     whole batch come from one sparse pass over the frames' sorted voxel lists (no dense grid,
+ *     staged once, straight into the batch's concatenation.  The colour columns of the whole
+ *     batch -- C3-HLAC-117 in columns 20 .. 136 at dim 137, C3-HLAC-981 in columns 20 .. 1000 at
+ *     dim 1001 -- come from one sparse pass over the frames' sorted voxel lists (no dense grid,
  *     no off-cell records, no per-frame launch; memory proportional to voxels and rows): a sort
- *     that groups the voxels by row, then exact integer sums per row.  A frame the per-frame
- *     extract refuses only for its dense tiling (more than 32,767 tile segments on an axis)
- *     succeeds here; every other status is that of head 0.  After such a call the context holds no
+ *     that groups the voxels by row, then exact integer sums per row.  At either dim a frame the
+ *     per-frame extract refuses only for its dense tiling (more than 32,767 tile segments on an
+ *     axis) succeeds here.  Every other status is that of head 0, but for one corner: with an
+ *     invalid color_mode a frame without rows has status 0 at dim 137 (C3H_ERR_ARG at dim 1001
+ *     and at head 0).  After such a call the context holds no
  *     single-frame grid: until the next c3h_voxelize / c3h_set_grid, c3h_compute_normals,
  *     c3h_extract, c3h_extract_grsd, c3h_extract_vosch, c3h_extract_convosch and c3h_get_grid_info return
  *     C3H_ERR_STATE.  The single-frame voxeliser's own buffers and bookkeeping are not touched.

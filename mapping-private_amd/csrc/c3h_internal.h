@@ -227,16 +227,6 @@ struct VhSortBufs {
 // and voxel indices at cent / vkeys + vord[f], in leaf-layout order; rec[f].n_occ, n_off
 hipError_t launch_vh_voxels(const VhTable* d_tab, int nf, const VfKey& key, int64_t ptot, VhSortBufs& b, float4* cent,
                             int32_t* vkeys, VhRec* rec, hipStream_t s);
-// the off-cell records ({voxel index, centroid cell xyz, the same, 0} relative to min_b, as the
-// single-frame voxeliser files them) of every frame, frame f's at offcell + 8 * opre.v[f]
-struct VhOffPre {
-  int64_t v[kVfMaxFrames + 1];
-};
-hipError_t launch_vh_offcell(const VhTable* d_tab, int nf, const int64_t* vord, int64_t vtot, const float4* cent,
-                             const int32_t* vkeys, const VhOffPre& opre, VhRec* rec, int32_t* offcell, hipStream_t s);
-// a frame's colour words into a zero grid through its voxel list (set = 1), and out again (0)
-hipError_t launch_vh_grid_words(const float4* cent, const int32_t* vkeys, int64_t nc, uint32_t* grid, int set,
-                                hipStream_t s);
 int64_t scan_blocks(int64_t n);
 hipError_t launch_leaf_layout(const uint32_t* grid, int64_t nvox, int32_t* leaf,
                               uint32_t* block_sums, int64_t nblocks, hipStream_t s);
@@ -819,10 +809,9 @@ struct c3h_ctx {
   c3h::DevBuf<c3h::VhTable> vh_tab;
   c3h::DevBuf<c3h::VhRec> vh_rec;
   c3h::DevBuf<uint32_t> vh_head, vh_sums;
-  c3h::DevBuf<int32_t> vh_ord, vh_offcell;
+  c3h::DevBuf<int32_t> vh_ord;
   c3h::DevBuf<int64_t> vh_vord;
-  c3h::DevBuf<uint32_t> vh_grid;    // dim 137: one frame's words at a time, zero between frames
-  // dim 1001 at head 1: the sparse batched C3-HLAC-981 (c3_sparse.hip)
+  // dim 137 / 1001 at head 1, c3h_extract_c3_frames: the sparse batched C3-HLAC (c3_sparse.hip)
   c3h::DevBuf<uint64_t> c3s_keys, c3s_keys2;
   c3h::DevBuf<uint32_t> c3s_idx, c3s_idx2, c3s_cnt;
   c3h::DevBuf<c3h::C3sChunk> c3s_chunks;

@@ -1154,18 +1154,33 @@ bool c3h::extract_params_ok(const c3h_extract_params* p) {
          p->color_mode <= C3H_COLOR_CHLAC;
 }
 
-c3h::VoxelExtras c3h::voxelize_extras(const c3h_ctx* ctx) {
+namespace {
+
+// What a one-frame extract takes from the voxeliser that made its grid: the records of the
+// voxels whose centroid lies in another cell (the extract corrects their contribution), and
+// whether the single-frame voxeliser's list of the grid's words may stamp the tiles
+struct VoxelExtras {
+  const int32_t* offcell = nullptr;
+  int64_t n_offcell = 0;
+  bool listed = false;
+};
+
+// of the grid in use: the last c3h_voxelize's, or none
+VoxelExtras voxelize_extras(const c3h_ctx* ctx) {
   VoxelExtras vx;
-  if (!ctx || !ctx->table_valid || ctx->grid_ptr != ctx->grid.p) return vx;
+  if (!ctx->table_valid || ctx->grid_ptr != ctx->grid.p) return vx;
   vx.offcell = ctx->voffcell.p;
   vx.n_offcell = ctx->n_offcell;
   vx.listed = ctx->vargs.lists != nullptr;
   return vx;
 }
 
+}  // namespace
+
 int c3h::extract_frames(c3h_ctx* ctx, const uint32_t* const* grids, int nf, const c3h_extract_params* p,
-                        int32_t subdiv_out[3], int64_t* hist_num_out, const VoxelExtras& vx) {
+                        int32_t subdiv_out[3], int64_t* hist_num_out) {
   if (!ctx || !p) return C3H_ERR_ARG;
+  const VoxelExtras vx = voxelize_extras(ctx);
   if (!extract_params_ok(p))
     return fail(ctx, C3H_ERR_ARG, "c3h_extract: variant must be 981 or 117, color_mode a C3H_COLOR_* value");
   if (!ctx->have_grid) return fail(ctx, C3H_ERR_STATE, "c3h_extract: no grid");

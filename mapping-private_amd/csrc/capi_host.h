@@ -95,21 +95,8 @@ inline int pc2_check(c3h_ctx* ctx, uint32_t height, uint32_t width, uint32_t poi
 // the single-frame path's steps the batch code and the GRSD front sequence (capi.hip)
 int mode_schedule(int r1, int r2, int r3, int rotate, int* modes);
 bool extract_params_ok(const c3h_extract_params* p);
-// What a one-frame extract takes from the voxeliser that made its grid: the records of the
-// voxels whose centroid lies in another cell (the extract corrects their contribution), and
-// whether the single-frame voxeliser's list of the grid's words may stamp the tiles
-struct VoxelExtras {
-  const int32_t* offcell = nullptr;
-  int64_t n_offcell = 0;
-  bool listed = false;
-};
-VoxelExtras voxelize_extras(const c3h_ctx* ctx);  // of the grid in use: the last c3h_voxelize's, or none
 int extract_frames(c3h_ctx* ctx, const uint32_t* const* grids, int nf, const c3h_extract_params* p,
-                   int32_t subdiv_out[3], int64_t* hist_num, const VoxelExtras& vx);
-inline int extract_frames(c3h_ctx* ctx, const uint32_t* const* grids, int nf, const c3h_extract_params* p,
-                          int32_t subdiv_out[3], int64_t* hist_num) {
-  return extract_frames(ctx, grids, nf, p, subdiv_out, hist_num, voxelize_extras(ctx));
-}
+                   int32_t subdiv_out[3], int64_t* hist_num);
 int search_frames(c3h_ctx* ctx, int nf, const int32_t range[3], int32_t thr, int32_t rotate,
                   c3h_det* const* d_outs, int clean);
 int grsd_frame_head(c3h_ctx* ctx, const c3h_grsd_params* p, int32_t sb[3], int64_t* Hout, float* inv_s);

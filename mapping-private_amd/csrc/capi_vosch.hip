@@ -6,16 +6,15 @@
 // c3h_pca_add_c3_frames on its packed mode (only the rows that hold a voxel, one after another).
 //
 // The head of a batch gives the front what only a voxeliser can: every frame's voxel grid
-// geometry, its exact centroids in leaf order and their voxel keys and, at dim 137 (at head 0 also
-// at dim 1001, ConVOSCH), the C3-HLAC rows (extract_frames), whose columns go straight into the
-// frame's output rows.  At dim 1001 the batched head leaves the colour columns to the front: one
-// sparse C3-HLAC-981 pass over the whole batch's voxel lists (c3_sparse.hip), launched by front_run.
-// c3h_set_vosch_head chooses it.  1 (head_batch): the batched voxel head of voxelize.hip (vh_*)
-// -- a bounds pass over the batch's concatenated points, the host's decision per frame
-// (vosch_frames.h), one sort whose runs are the voxels, a thread per run -- with two host
-// synchronisations per batch; the extract still runs per frame, on a grid of the head's own.
+// geometry, its exact centroids in leaf order and their voxel keys.  c3h_set_vosch_head chooses it.
+// 1 (head_batch): the batched voxel head of voxelize.hip (vh_*) -- a bounds pass over the batch's
+// concatenated points, the host's decision per frame (vosch_frames.h), one sort whose runs are the
+// voxels, a thread per run -- with two host synchronisations per batch and no launch per frame.
+// It leaves the colour columns of dim 137 and dim 1001 to the front: one sparse C3-HLAC pass (117
+// or 981 bins) over the whole batch's voxel lists (c3_sparse.hip), launched by front_run.
 // 0 (front_head): per frame, in turn, c3h_voxelize (which synchronises the host), the exact
-// centroids, the leaf layout and the extract.  What a frame leaves for the front is small: its
+// centroids, the leaf layout and, at dim 137 and 1001, the dense C3-HLAC extract (extract_frames),
+// whose columns go straight into the frame's output rows.  What a frame leaves for the front is small: its
 // geometry on the host (VfHostFrame), its centroids in leaf order and their voxel keys.  Everything else --
 // search grids, normals, RSD, GRSD transitions, columns 0 .. 19 -- runs once per batch over a
 // device table of per-frame records.  The single-frame entry points are a batch of one frame in
@@ -40,7 +39,7 @@ struct FrontParams {
   float max_dist;  // kStageGrsd: the RSD radius,
   float norm;      //   the factor of the rows
   int dim;         //   and their stride
-  // the batched head at dim 1001: columns 20 .. by the sparse C3-HLAC-981 (c3_sparse.hip)
+  // the batched head at dim 137 / 1001: columns 20 .. by the sparse C3-HLAC pass (c3_sparse.hip)
   const uint32_t* c3s_lut = nullptr;  // the colour mode's LUT, or nullptr: no such columns
   int32_t c3s_thr[3] = {0, 0, 0};
 };
@@ -127,6 +126,57 @@ void push_prefixes(c3h::VfTable* ht, int j, const c3h::VfHostFrame& fr) {
   ht->hpre[j + 1] = ht->hpre[j] + fr.H;
 }
 
+// info[j] of a frame whose status is st and, where it succeeded, whose host record is fr
+void fill_info(c3h_frame_info* fi, int st, const c3h::VfHostFrame& fr, int64_t n_moved) {
+  memset(fi, 0, sizeof(*fi));
+  fi->status = st;
+  if (st < 0) return;
+  for (int a = 0; a < 3; ++a) {
+    fi->div_b[a] = fr.gi.div_b[a];
+    fi->min_b[a] = fr.gi.min_b[a];
+    fi->subdiv_b[a] = fr.sb[a];
+  }
+  fi->n_valid = fr.gi.n_valid;
+  fi->n_occ = fr.gi.n_occ;
+  fi->n_moved = fr.H > 0 ? (int32_t)n_moved : 0;
+}
+
+// The batched head has no single-frame grid to leave: none is held from here on
+void drop_single_frame(c3h_ctx* ctx) {
+  ctx->have_grid = false;
+  ctx->table_valid = false;
+  ctx->vcent_valid = false;
+  ctx->normals_valid = false;
+  ctx->rsd_n = 0;
+  ctx->grid_ptr = nullptr;
+  ctx->have_feat = false;
+  ctx->feat_listed = false;
+  ctx->g_valid = false;
+  ctx->rows_valid = false;
+}
+
+// the points a batch can hold at most (negative counts: the frame fails, none)
+int64_t batch_points(const int64_t* n, int nb) {
+  int64_t upper = 0;
+  for (int j = 0; j < nb; ++j) upper += std::max<int64_t>(n[j], 0);
+  return upper;
+}
+
+// A batch of nb frames begins: its host table and the buffers every head fills, sized by the
+// points it can hold.  who: the entry point's name in the messages.
+int batch_begin(c3h_ctx* ctx, const char* who, const int64_t* n, int nb, int on_device, c3h::VfTable** ht) {
+  const int64_t upper = batch_points(n, nb);
+  if (upper > c3h::kVfMaxPoints) return fail(ctx, C3H_ERR_RANGE, std::string(who) + ": a batch holds 2^32 points or more");
+  // the previous batch's launches read the buffers that may grow now
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const int rc = front_begin(ctx, nb, ht);
+  if (rc != C3H_OK) return rc;
+  if (!on_device) ENSURE(ctx->vf_pts, upper);
+  ENSURE(ctx->vf_cent, upper);
+  ENSURE(ctx->vf_vkeys, upper);
+  return C3H_OK;
+}
+
 // frame j's record of the table, from its prefixes and the front's buffers (both final).
 // grids == false (c3_rows_front): no search grid, RSD type or transition buffer exists; those
 // fields stay zero
@@ -167,6 +217,15 @@ void fill_record(c3h_ctx* ctx, c3h::VfTable* ht, int j, const c3h::VfHostFrame& 
   t.layout = fr.layout;
   t.rows = fr.rows;
   t.exist = fr.exist;
+}
+
+// The first nb records of the host table to the device; vf_up_ev tells when the host copy is read
+int table_upload(c3h_ctx* ctx, const c3h::VfTable* ht, int nb) {
+  HIPCHK(hipMemcpyAsync(ctx->vf_tab.p, ht, offsetof(c3h::VfTable, fr) + (size_t)nb * sizeof(c3h::VfFrame),
+                        hipMemcpyHostToDevice, ctx->stream));
+  if (!ctx->vf_up_ev) HIPCHK(hipEventCreateWithFlags(&ctx->vf_up_ev, hipEventDisableTiming));
+  HIPCHK(hipEventRecord(ctx->vf_up_ev, ctx->stream));
+  return C3H_OK;
 }
 
 // The sparse C3-HLAC pass (c3_sparse.hip) over the uploaded table: columns col0 .. col0 + variant - 1
@@ -240,10 +299,8 @@ int front_run(c3h_ctx* ctx, c3h::VfTable* ht, const c3h::VfHostFrame* ff, int nb
     ENSURE(ctx->vf_trans, htot * 36);
   }
   for (int j = 0; j < nb; ++j) fill_record(ctx, ht, j, ff[j]);
-  HIPCHK(hipMemcpyAsync(ctx->vf_tab.p, ht, offsetof(c3h::VfTable, fr) + (size_t)nb * sizeof(c3h::VfFrame),
-                        hipMemcpyHostToDevice, ctx->stream));
-  if (!ctx->vf_up_ev) HIPCHK(hipEventCreateWithFlags(&ctx->vf_up_ev, hipEventDisableTiming));
-  HIPCHK(hipEventRecord(ctx->vf_up_ev, ctx->stream));
+  const int up = table_upload(ctx, ht, nb);
+  if (up != C3H_OK) return up;
   if (stages & kStageNormals) {
     HIPCHK(c3h::vf_nbr_build(ctx->vf_tab.p, 0, key, ptot, ctot, ctx->vf_keys.p, ctx->vf_keys2.p, ctx->vf_idx.p,
                              ctx->vf_idx2.p, ctx->vf_cstart.p, ctx->vf_cend.p, ctx->vf_tmp.p, &tb, ctx->stream));
@@ -266,7 +323,7 @@ int front_run(c3h_ctx* ctx, c3h::VfTable* ht, const c3h::VfHostFrame* ff, int nb
     HIPCHK(c3h::launch_vf_grsd(ctx->vf_tab.p, vtot, ctx->stream));
     HIPCHK(c3h::launch_vf_rows(ctx->vf_tab.p, htot, ctx->vf_trans.p, q.norm, q.dim, ctx->stream));
   }
-  if (q.c3s_lut && htot > 0) return c3_sparse_run(ctx, vtot, htot, q.c3s_lut, q.c3s_thr, c3h::kC3sBins, q.dim, 20);
+  if (q.c3s_lut && htot > 0) return c3_sparse_run(ctx, vtot, htot, q.c3s_lut, q.c3s_thr, q.dim - 20, q.dim, 20);
   return C3H_OK;
 }
 
@@ -278,7 +335,7 @@ float grsd_norm(const c3h_grsd_params* gp) { return gp->normalize ? (float)(20.0
 // of rows of 20 + variant floats.  117: VOSCH.  981: ConVOSCH, always from the f32 rows (fp16
 // search precision applies to the search only: the extract's f16-row route is not taken here)
 int c3_cols(c3h_ctx* ctx, const c3h_grsd_params* gp, int variant, const int32_t thr[3], int32_t color_mode, int64_t H,
-            float* rows, const c3h::VoxelExtras& vx) {
+            float* rows) {
   c3h_extract_params e{};
   e.variant = variant;
   for (int a = 0; a < 3; ++a) {
@@ -292,7 +349,7 @@ int c3_cols(c3h_ctx* ctx, const c3h_grsd_params* gp, int variant, const int32_t 
   int64_t H2 = 0;
   const bool prec16 = ctx->prec16;
   ctx->prec16 = false;
-  const int rc = c3h::extract_frames(ctx, &g, 1, &e, sb2, &H2, vx);
+  const int rc = c3h::extract_frames(ctx, &g, 1, &e, sb2, &H2);
   ctx->prec16 = prec16;
   if (rc != C3H_OK) return rc;
   if (H2 != H) return fail(ctx, C3H_ERR_STATE, "extract_vosch: GRSD / C3 subdivisions differ");
@@ -354,7 +411,7 @@ int front_head(c3h_ctx* ctx, const float* pts, int64_t n, int on_device, float l
     HIPCHK(hipMemcpyAsync(ctx->vf_cent.p + v0, ctx->dsamp.p, (size_t)fr->nc * 16, hipMemcpyDeviceToDevice, ctx->stream));
     fr->cent = ctx->vf_cent.p + v0;
   }
-  if (dim != 20) return c3_cols(ctx, &p->grsd, dim - 20, p->thr, p->color_mode, fr->H, fr->rows, c3h::voxelize_extras(ctx));
+  if (dim != 20) return c3_cols(ctx, &p->grsd, dim - 20, p->thr, p->color_mode, fr->H, fr->rows);
   return C3H_OK;
 }
 
@@ -378,10 +435,12 @@ const char* head_reason(int reason) {
 // status, info, VfHostFrame and prefixes as nb front_head calls leave them, with two host
 // synchronisations for the batch -- the bounds of the frames, then their voxel counts.  The
 // centroids and voxel keys of all frames are runs of one sort over the concatenated points; the
-// context's single-frame grid and voxeliser state are not used (vh_* buffers), only, at dim 137,
-// the extract's own buffers.  d_rows: the slot of the batch's first frame.  c3_only
-// (c3_rows_front): dim is the C3-HLAC variant, the rows' stride; no search grid is sized or
-// checked, and negative thresholds make every frame the reference's silent-empty case.
+// context's single-frame grid, voxeliser state and extract buffers are not used (vh_* buffers).
+// dim: the rows' stride.  d_rows: the slot of the batch's first frame.  c3_only (c3_rows_front):
+// dim is the C3-HLAC variant; no search grid is sized or checked, and negative thresholds make
+// every frame the reference's silent-empty case.  Otherwise the colour columns of dim 137 / 1001
+// come from the front's sparse pass (front_run): what the per-frame extract of head 0 refuses of
+// the call's colour mode and thresholds is refused here, per frame, with its status and message.
 int head_batch(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int nb, int on_device, float leaf, float z_limit,
                const c3h_vosch_params* p, int dim, int64_t row_cap, float* d_rows, const FrontParams& q,
                c3h::VfTable* ht, c3h::VfHostFrame* ff, c3h_frame_info* info, bool c3_only = false) {
@@ -494,86 +553,37 @@ int head_batch(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int nb, 
     HIPCHK(hipMemcpyAsync(hh->back, ctx->vh_rec.p, (size_t)nb * sizeof(c3h::VhRec), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
-  // ---- the frames' centroids and voxel keys (runs' ordinals: frame after frame), off-cell records
-  c3h::VhOffPre opre{};
+  // ---- the frames' centroids and voxel keys (runs' ordinals: frame after frame), status and info
+  const bool colour = !c3_only && dim != 20;
+  const bool bad_mode = p->color_mode < C3H_COLOR_C3_FLOAT || p->color_mode > C3H_COLOR_CHLAC;
+  const bool bad_thr = p->thr[0] < 0 || p->thr[1] < 0 || p->thr[2] < 0;
   int64_t vall = 0;
   for (int j = 0; j < nb; ++j) {
     c3h::VfHostFrame& fr = ff[j];
-    opre.v[j + 1] = opre.v[j];
-    if (reason[j] != c3h::kVhGood) continue;
-    const int64_t n_occ = hh->back[j].n_occ;
-    fr.gi.n_occ = n_occ;
-    fr.nc = fr.H > 0 ? n_occ : 0;
-    fr.cent = ctx->vf_cent.p + vall;
-    fr.vkeys = ctx->vf_vkeys.p + vall;
-    fr.layout = nullptr;
-    vall += n_occ;
-    if (dim == 137 && fr.H > 0) opre.v[j + 1] += hh->back[j].n_off;
-  }
-  if (opre.v[nb] > 0) {
-    ENSURE(ctx->vh_offcell, (size_t)opre.v[nb] * 8);
-    HIPCHK(c3h::launch_vh_offcell(ctx->vh_tab.p + 1, nb, ctx->vh_vord.p, vall, ctx->vf_cent.p, ctx->vf_vkeys.p, opre,
-                                  ctx->vh_rec.p, ctx->vh_offcell.p, ctx->stream));
-  }
-  if (dim == 137 && vall > 0) {  // the grid of one frame at a time: zero but for the words of the frame in hand
-    if (ctx->vh_grid.n < (size_t)max_vox) {
-      ENSURE(ctx->vh_grid, max_vox);
-      HIPCHK(hipMemsetAsync(ctx->vh_grid.p, 0, ctx->vh_grid.n * 4, ctx->stream));
-    }
-  }
-  for (int j = 0; j < nb; ++j) {
-    c3h::VfHostFrame& fr = ff[j];
     int st = c3h::vh_status(reason[j]);
-    if (st == C3H_OK && dim == 137 && fr.H > 0) {
-      // the C3 columns by the single-frame extract on the head's grid: the frame's words in, out again
-      HIPCHK(c3h::launch_vh_grid_words(fr.cent, fr.vkeys, fr.nc, ctx->vh_grid.p, 1, ctx->stream));
-      ctx->info = fr.gi;
-      ctx->have_grid = true;
-      ctx->grid_ptr = ctx->vh_grid.p;
-      c3h::VoxelExtras vx;
-      vx.offcell = ctx->vh_offcell.p + 8 * opre.v[j];
-      vx.n_offcell = opre.v[j + 1] - opre.v[j];
-      st = c3_cols(ctx, &p->grsd, 117, p->thr, p->color_mode, fr.H, fr.rows, vx);
-      ctx->have_grid = false;
-      ctx->have_feat = false;
-      ctx->grid_ptr = nullptr;
-      const hipError_t e = c3h::launch_vh_grid_words(fr.cent, fr.vkeys, fr.nc, ctx->vh_grid.p, 0, ctx->stream);
-      if (e != hipSuccess) {
-        c3h::DevBuf<uint32_t> drop(std::move(ctx->vh_grid));  // not known to be zero any more
-        return c3h::hip_fail(ctx, "launch_vh_grid_words", e);
-      }
+    if (st == C3H_OK) {
+      const int64_t n_occ = hh->back[j].n_occ;
+      fr.gi.n_occ = n_occ;
+      fr.nc = fr.H > 0 ? n_occ : 0;
+      fr.cent = ctx->vf_cent.p + vall;
+      fr.vkeys = ctx->vf_vkeys.p + vall;
+      fr.layout = nullptr;
+      vall += n_occ;
+    }
+    if (st == C3H_OK && colour) {
+      // (a frame without rows keeps the status 0 it has always had here at dim 137, where the
+      // extract ran only for a frame with rows; at dim 1001, as at head 0, it is refused)
+      if (bad_mode && (fr.H > 0 || dim == 1001))
+        st = fail(ctx, C3H_ERR_ARG, "c3h_extract: variant must be 981 or 117, color_mode a C3H_COLOR_* value");
+      else if (fr.H > 0 && bad_thr)
+        st = fail(ctx, C3H_ERR_STATE, "extract_vosch: GRSD / C3 subdivisions differ");
       if (st < 0) {  // no centroid and no row of it goes on (its points are in the sort already: normals only)
         fr.H = 0;
         fr.nc = 0;
         fr.rows = nullptr;
       }
     }
-    if (st == C3H_OK && dim == 1001) {
-      // the colour columns come from the front's sparse pass (front_run); what the per-frame
-      // extract refuses is refused here with its status
-      if (p->color_mode < C3H_COLOR_C3_FLOAT || p->color_mode > C3H_COLOR_CHLAC)
-        st = fail(ctx, C3H_ERR_ARG, "c3h_extract: variant must be 981 or 117, color_mode a C3H_COLOR_* value");
-      else if (fr.H > 0 && (p->thr[0] < 0 || p->thr[1] < 0 || p->thr[2] < 0))
-        st = fail(ctx, C3H_ERR_STATE, "extract_vosch: GRSD / C3 subdivisions differ");
-      if (st < 0) {
-        fr.H = 0;
-        fr.nc = 0;
-        fr.rows = nullptr;
-      }
-    }
-    c3h_frame_info& fi = info[j];
-    memset(&fi, 0, sizeof(fi));
-    fi.status = st;
-    if (st >= 0) {
-      for (int a = 0; a < 3; ++a) {
-        fi.div_b[a] = fr.gi.div_b[a];
-        fi.min_b[a] = fr.gi.min_b[a];
-        fi.subdiv_b[a] = fr.sb[a];
-      }
-      fi.n_valid = fr.gi.n_valid;
-      fi.n_occ = fr.gi.n_occ;
-      fi.n_moved = fr.H > 0 ? (int32_t)hh->back[j].n_off : 0;
-    }
+    fill_info(&info[j], st, fr, hh->back[j].n_off);
     push_prefixes(ht, j, fr);
   }
   return C3H_OK;
@@ -587,18 +597,7 @@ int vosch_front(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t
   HIPCHK(hipSetDevice(ctx->device));
   const int B = std::max(1, std::min(ctx->nbatch, c3h::kVfMaxFrames));
   ctx->vf_nframes = 0;
-  if (ctx->vosch_head == 1) {  // the head has no single-frame grid to leave: none is held from here on
-    ctx->have_grid = false;
-    ctx->table_valid = false;
-    ctx->vcent_valid = false;
-    ctx->normals_valid = false;
-    ctx->rsd_n = 0;
-    ctx->grid_ptr = nullptr;
-    ctx->have_feat = false;
-    ctx->feat_listed = false;
-    ctx->g_valid = false;
-    ctx->rows_valid = false;
-  }
+  if (ctx->vosch_head == 1) drop_single_frame(ctx);
   ctx->vf_n.assign(n, n + nframes);
   ctx->vf_status.assign((size_t)nframes, 0);
   ctx->vf_ppre.assign((size_t)nframes + 1, 0);
@@ -609,24 +608,16 @@ int vosch_front(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t
   q.max_dist = rsd_max_dist(&p->grsd, leaf);
   q.norm = grsd_norm(&p->grsd);
   q.dim = dim;
-  if (dim == 1001 && ctx->vosch_head == 1 && p->color_mode >= C3H_COLOR_C3_FLOAT && p->color_mode <= C3H_COLOR_CHLAC) {
+  if (dim != 20 && ctx->vosch_head == 1 && p->color_mode >= C3H_COLOR_C3_FLOAT && p->color_mode <= C3H_COLOR_CHLAC) {
     q.c3s_lut = ctx->lut.p + 256 * p->color_mode;
     for (int a = 0; a < 3; ++a) q.c3s_thr[a] = p->thr[a];
   }
   std::vector<c3h::VfHostFrame> ff((size_t)B);
   for (int b0 = 0; b0 < nframes; b0 += B) {
     const int nb = std::min(B, nframes - b0);
-    int64_t upper = 0;
-    for (int j = 0; j < nb; ++j) upper += std::max<int64_t>(n[b0 + j], 0);
-    if (upper > c3h::kVfMaxPoints) return fail(ctx, C3H_ERR_RANGE, "vosch frames: a batch holds 2^32 points or more");
-    // the previous batch's launches read the buffers that may grow now
-    HIPCHK(hipStreamSynchronize(ctx->stream));
     c3h::VfTable* ht = nullptr;
-    int rc = front_begin(ctx, nb, &ht);
+    int rc = batch_begin(ctx, "vosch frames", n + b0, nb, on_device, &ht);
     if (rc != C3H_OK) return rc;
-    if (!on_device) ENSURE(ctx->vf_pts, upper);
-    ENSURE(ctx->vf_cent, upper);
-    ENSURE(ctx->vf_vkeys, upper);
     if (ctx->vosch_head == 1) {
       rc = head_batch(ctx, pts + b0, n + b0, nb, on_device, leaf, z_limit, p, dim, row_cap,
                       d_rows + (size_t)b0 * row_cap * dim, q, ht, ff.data(), info + b0);
@@ -637,22 +628,10 @@ int vosch_front(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32_t
       if (ctx->vosch_head != 1) {
         c3h::VfHostFrame& fr = ff[(size_t)j];
         fr = c3h::VfHostFrame{};
-        c3h_frame_info& fi = info[i];
-        memset(&fi, 0, sizeof(fi));
         const int st = front_head(ctx, pts[i], n[i], on_device, leaf, z_limit, p, dim, row_cap, ht->ppre[j], ht->vpre[j],
                                   d_rows + (size_t)i * row_cap * dim, &fr);
-        fi.status = st;
         if (st < 0) fr = c3h::VfHostFrame{};  // no points, cells, centroids or rows in the batch
-        else {
-          for (int a = 0; a < 3; ++a) {
-            fi.div_b[a] = fr.gi.div_b[a];
-            fi.min_b[a] = fr.gi.min_b[a];
-            fi.subdiv_b[a] = fr.sb[a];
-          }
-          fi.n_valid = fr.gi.n_valid;
-          fi.n_occ = fr.gi.n_occ;
-          fi.n_moved = fr.H > 0 ? (int32_t)ctx->n_offcell : 0;
-        }
+        fill_info(&info[i], st, fr, ctx->n_offcell);
         push_prefixes(ht, j, fr);
       }
       ctx->vf_status[(size_t)i] = info[i].status;
@@ -734,22 +713,11 @@ int c3_rows_front(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32
                   c3h_frame_info* info, PackedCall* pc = nullptr) {
   HIPCHK(hipSetDevice(ctx->device));
   const int B = std::max(1, std::min(ctx->nbatch, c3h::kVfMaxFrames));
-  for (int b0 = 0; b0 < nframes; b0 += B) {
-    int64_t upper = 0;
-    for (int j = b0; j < std::min(nframes, b0 + B); ++j) upper += std::max<int64_t>(n[j], 0);
-    if (upper > c3h::kVfMaxPoints) return fail(ctx, C3H_ERR_RANGE, "c3 frames: a batch holds 2^32 points or more");
-  }
-  ctx->vf_nframes = 0;  // the head has no single-frame grid to leave: none is held from here on
-  ctx->have_grid = false;
-  ctx->table_valid = false;
-  ctx->vcent_valid = false;
-  ctx->normals_valid = false;
-  ctx->rsd_n = 0;
-  ctx->grid_ptr = nullptr;
-  ctx->have_feat = false;
-  ctx->feat_listed = false;
-  ctx->g_valid = false;
-  ctx->rows_valid = false;
+  for (int b0 = 0; b0 < nframes; b0 += B)  // (refused before any batch runs)
+    if (batch_points(n + b0, std::min(B, nframes - b0)) > c3h::kVfMaxPoints)
+      return fail(ctx, C3H_ERR_RANGE, "c3 frames: a batch holds 2^32 points or more");
+  ctx->vf_nframes = 0;
+  drop_single_frame(ctx);
   const int variant = e->variant;
   c3h_vosch_params p{};
   p.grsd.subdiv = e->subdiv;
@@ -765,17 +733,10 @@ int c3_rows_front(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32
   std::vector<c3h::VfHostFrame> ff((size_t)B);
   for (int b0 = 0; b0 < nframes; b0 += B) {
     const int nb = std::min(B, nframes - b0);
-    int64_t upper = 0;
-    for (int j = 0; j < nb; ++j) upper += std::max<int64_t>(n[b0 + j], 0);
-    // the previous batch's launches read the buffers that may grow now
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (pc) packed_take(ctx, pc);  // (that wait also brought the previous batch's count)
     c3h::VfTable* ht = nullptr;
-    int rc = front_begin(ctx, nb, &ht);
+    int rc = batch_begin(ctx, "c3 frames", n + b0, nb, on_device, &ht);
     if (rc != C3H_OK) return rc;
-    if (!on_device) ENSURE(ctx->vf_pts, upper);
-    ENSURE(ctx->vf_cent, upper);
-    ENSURE(ctx->vf_vkeys, upper);
+    if (pc) packed_take(ctx, pc);  // (batch_begin's wait also brought the previous batch's count)
     rc = head_batch(ctx, pts + b0, n + b0, nb, on_device, leaf, z_limit, &p, variant, row_cap,
                     pc ? nullptr : d_rows + (size_t)b0 * row_cap * variant, q, ht, ff.data(), info + b0, true);
     if (rc != C3H_OK) return rc;
@@ -790,10 +751,8 @@ int c3_rows_front(c3h_ctx* ctx, const float* const* pts, const int64_t* n, int32
       if (d_exist && ff[(size_t)j].H > 0) ff[(size_t)j].exist = d_exist + (size_t)(b0 + j) * row_cap;
       fill_record(ctx, ht, j, ff[(size_t)j], false);
     }
-    HIPCHK(hipMemcpyAsync(ctx->vf_tab.p, ht, offsetof(c3h::VfTable, fr) + (size_t)nb * sizeof(c3h::VfFrame),
-                          hipMemcpyHostToDevice, ctx->stream));
-    if (!ctx->vf_up_ev) HIPCHK(hipEventCreateWithFlags(&ctx->vf_up_ev, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(ctx->vf_up_ev, ctx->stream));
+    rc = table_upload(ctx, ht, nb);
+    if (rc != C3H_OK) return rc;
     if (!pc) {
       rc = c3_sparse_run(ctx, vtot, htot, lut, p.thr, variant, variant, 0);
       if (rc != C3H_OK) return rc;
@@ -937,7 +896,7 @@ static int extract_vosch_rows(c3h_ctx* ctx, const c3h_grsd_params* p, int varian
   int64_t H = 0;
   int rc = grsd_frames(ctx, p, 20 + variant, ctx->vf_rows, sb, &H);
   if (rc != C3H_OK) return rc;
-  rc = c3_cols(ctx, p, variant, thr, color_mode, H, ctx->vf_rows.p, c3h::voxelize_extras(ctx));
+  rc = c3_cols(ctx, p, variant, thr, color_mode, H, ctx->vf_rows.p);
   if (rc != C3H_OK) return rc;
   std::swap(ctx->feat, ctx->vf_rows);  // (extract_frames left the C3-HLAC rows in feat)
   ctx->feat_dim = 20 + variant;

@@ -156,7 +156,6 @@ struct VhRec {
   uint32_t n_occ;                // occupied voxels (runs)
   unsigned long long n_valid;    // valid points
   uint32_t n_off;                // voxels whose centroid lies in another cell
-  uint32_t ocur;                 // the off-cell records filed so far
 };
 inline VhRec vh_rec_init() {
   VhRec r{};

@@ -914,9 +914,8 @@ int grid_for(int64_t n, int cap = 4096) {
 //   vh_counts   the frames' ordinal prefix: frame f's points sort into [ppre[f], ppre[f + 1]).
 //   vh_emit     one thread per run: voxs_run, the centroid and voxel index at the run's ordinal,
 //               the frame's off-cell count.
-//   vh_offcell  (dim 137) the off-cell records, filed per frame once the host knows the counts.
 // No kernel writes past what the host sized by ptot (keys, idx, head, ord, cent, vkeys: one
-// element per point at most) or by the counts it read back (the off-cell records).
+// element per point at most).
 constexpr int kVhChunk = kBlock * 8;
 
 __global__ __launch_bounds__(kBlock) void vh_bounds_kernel(const VhTable* __restrict__ T, int64_t ptot,
@@ -1056,33 +1055,6 @@ __global__ __launch_bounds__(kBlock) void vh_emit_kernel(const VhTable* __restri
     voxs_own_cell(v, fr.mn, fr.dv, own);
     if (voxs_moved(r.c, leaf, own, nb)) atomicAdd(&rec[f].n_off, 1u);
   }
-}
-
-__global__ __launch_bounds__(kBlock) void vh_offcell_kernel(const VhTable* __restrict__ T, int nf,
-                                                            const int64_t* __restrict__ vord, int64_t vtot,
-                                                            const float4* __restrict__ cent,
-                                                            const int32_t* __restrict__ vkeys, VhOffPre opre,
-                                                            VhRec* __restrict__ rec, int32_t* __restrict__ offcell) {
-  const float leaf = T->leaf;
-  for (int64_t q = blockIdx.x * (int64_t)kBlock + threadIdx.x; q < vtot; q += (int64_t)gridDim.x * kBlock) {
-    const int f = vf_frame_of(vord, nf, q);
-    const VhFrame& fr = T->fr[f];
-    const float4 c4 = cent[q];
-    const float c[3] = {c4.x, c4.y, c4.z};
-    const uint32_t v = (uint32_t)vkeys[q];
-    int own[3], nb[3];
-    voxs_own_cell(v, fr.mn, fr.dv, own);
-    if (!voxs_moved(c, leaf, own, nb)) continue;
-    const int64_t k = (int64_t)atomicAdd(&rec[f].ocur, 1u);
-    if (k < opre.v[f + 1] - opre.v[f]) voxs_offcell_record(offcell + 8 * (opre.v[f] + k), v, nb, fr.mn);
-  }
-}
-
-__global__ __launch_bounds__(kBlock) void vh_grid_words_kernel(const float4* __restrict__ cent,
-                                                               const int32_t* __restrict__ vkeys, int64_t nc,
-                                                               uint32_t* __restrict__ grid, int set) {
-  for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < nc; i += (int64_t)gridDim.x * kBlock)
-    grid[vkeys[i]] = set ? (kOcc | (__float_as_uint(cent[i].w) & 0x00ffffffu)) : 0u;
 }
 
 // ---- batched voxeliser (c3h_run_point_frames) ----------------------------------------
@@ -1913,20 +1885,6 @@ hipError_t launch_vh_voxels(const VhTable* d_tab, int nf, const VfKey& key, int6
   scan_write_kernel<false><<<(unsigned)nb, kBlock, 0, s>>>(b.head, ptot, b.block_sums, b.ord);
   vh_counts_kernel<<<1, 128, 0, s>>>(d_tab, ptot, b.head, b.ord, b.vord, rec);
   vh_emit_kernel<<<grid_for(ptot, 8192), kBlock, 0, s>>>(d_tab, ptot, b.keys2, b.idx2, b.head, b.ord, cent, vkeys, rec);
-  return hipGetLastError();
-}
-
-hipError_t launch_vh_offcell(const VhTable* d_tab, int nf, const int64_t* vord, int64_t vtot, const float4* cent,
-                             const int32_t* vkeys, const VhOffPre& opre, VhRec* rec, int32_t* offcell, hipStream_t s) {
-  if (vtot <= 0) return hipSuccess;
-  vh_offcell_kernel<<<grid_for(vtot, 8192), kBlock, 0, s>>>(d_tab, nf, vord, vtot, cent, vkeys, opre, rec, offcell);
-  return hipGetLastError();
-}
-
-hipError_t launch_vh_grid_words(const float4* cent, const int32_t* vkeys, int64_t nc, uint32_t* grid, int set,
-                                hipStream_t s) {
-  if (nc <= 0) return hipSuccess;
-  vh_grid_words_kernel<<<grid_for(nc, 8192), kBlock, 0, s>>>(cent, vkeys, nc, grid, set);
   return hipGetLastError();
 }
 
