@@ -41,7 +41,8 @@ G7 runs on G6's subdivisions: on (9,7,6) its one mode has 8 * 6 * 5 = 240 = 15 *
 whole number of score_kernel<16> workgroups, and every case must leave a partial last workgroup
 in some mode (here 6 * 4 * 3 = 72 = 4 * 16 + 8).
 
-References per case:
+References per case (by name, cached; build_case, compress64_case, restate32_case and
+box_norms64_case take a case dict: fast_search_data.py shares them):
   oracle(name)      the float64 oracle (pyoracle.search, dbl=True): lists and scores
   compress64(name)  float64 compress of the rows as setData normalises them (float32 division,
                     search.cpp:563-570), and the forward bound of a length-F fp32 chain
@@ -82,10 +83,14 @@ def positions_per_workgroup(D, r):
     return 64 if D <= 256 and 256 * (D + r + 3) <= LDS_PER_WORKGROUP else 16
 
 
-def rows(sb, F, rng):
-    """-> (rows, exist): small integers, ~30 % empty rows, EXIST0_ROWS rows with data and exist 0."""
+def rows(sb, F, rng, common=0.0):
+    """-> (rows, exist): small integers, ~30 % empty rows, EXIST0_ROWS rows with data and exist 0.
+    common: every row with data also gets common x one random row (search_fp16_cases.COMMON's
+    device: it keeps the scores of r <= 2 models away from 0)."""
     H = int(np.prod(sb))
     f = np.floor(rng.random((H, F)) * 4).astype(np.float32)
+    if common:
+        f = f + np.float32(common) * rng.random(F, dtype=np.float32)[None, :]
     f[rng.random(H) < 0.3] = 0
     live = np.flatnonzero(f.any(1))
     ex = np.zeros(H, np.int32)
@@ -103,6 +108,13 @@ def bases(c):
         axis_t, var, _ = synth.random_bases(c["F"], c["D"], 1, 1, seed=c["seed"])
         rng = np.random.default_rng(c["seed"] + 1000)
         return axis_t, var, (rng.standard_normal((c["M"], c["r"], c["D"])) / np.sqrt(c["r"])).astype(np.float32)
+    if c.get("flat_q"):
+        # model rows of weight 1, 1/2, 1, 1/2, ... on np_ref.flat_bases: random_bases' rows decay as
+        # 0.85^(i/2), which hides a model's last rows below 1e-4 of the score from r of about 40;
+        # unweighted, r = D would score 1 everywhere
+        axis_t, var, _ = synth.random_bases(c["F"], c["D"], 1, 1, seed=c["seed"])
+        w = np.where(np.arange(c["r"]) % 2, np.float32(0.5), np.float32(1))
+        return axis_t, var, (npr.flat_bases(c["D"], c["M"], c["r"], c["seed"] + 1) * w[None, :, None]).astype(np.float32)
     return synth.random_bases(c["F"], c["D"], c["M"], c["r"], seed=c["seed"])
 
 
@@ -148,22 +160,26 @@ def normalise(f, fmax):
     return np.where(fm[None, :] == 0, np.float32(0), np.where(f == fm[None, :], np.float32(1), q)).astype(np.float32)
 
 
-def case(name):
-    """The inputs of a case: its table row plus f, ex, axis_t, var, ap (whitened, None when
+def build_case(row):
+    """The inputs of a table row: the row plus f, ex, axis_t, var, ap (whitened, None when
     uncompressed), axis_q, fmax (None without) and thr."""
+    c = dict(row)
+    rng = np.random.default_rng(c["seed"])
+    c["f"], c["ex"] = rows(c["sb"], c["F"], rng, c.get("common", 0.0))
+    c["axis_t"], c["var"], c["axis_q"] = bases(c)
+    c["ap"] = None if c["axis_t"] is None else synth.whiten(c["axis_t"], c["var"])
+    c["fmax"] = None
+    if c.get("with_fmax"):
+        fm = rng.integers(2, 6, c["F"]).astype(np.float32)  # 3: equal to values of that column
+        fm[7] = 0
+        c["fmax"] = fm
+    c["thr"] = threshold(c["sb"], c["ex"], c["box"], c["rotate"])
+    return c
+
+
+def case(name):
     if name not in _CASE:
-        c = dict(CASES[name])
-        rng = np.random.default_rng(c["seed"])
-        c["f"], c["ex"] = rows(c["sb"], c["F"], rng)
-        c["axis_t"], c["var"], c["axis_q"] = bases(c)
-        c["ap"] = None if c["axis_t"] is None else synth.whiten(c["axis_t"], c["var"])
-        c["fmax"] = None
-        if c.get("with_fmax"):
-            fm = rng.integers(2, 6, c["F"]).astype(np.float32)  # 3: equal to values of that column
-            fm[7] = 0
-            c["fmax"] = fm
-        c["thr"] = threshold(c["sb"], c["ex"], c["box"], c["rotate"])
-        _CASE[name] = c
+        _CASE[name] = build_case(CASES[name])
     return _CASE[name]
 
 
@@ -181,20 +197,28 @@ def oracle(name):
     return _ORACLE[name]
 
 
-def compress64(name):
+def compress64_rows(f, ap, fmax):
     """-> (G64, bound): G64 = fn @ ap^T in float64 (fn: the float32-normalised rows), and the
     elementwise bound on a float32 fma chain of length F against it, gamma_F * (|fn| @ |ap|^T) with
     gamma_F = F u / (1 - F u), plus u * |G64| for the rounding of G64 itself to float32."""
+    fn = normalise(f, fmax).astype(np.float64)
+    F = f.shape[1]
+    if ap is None:
+        G, mag = fn, np.abs(fn)
+    else:
+        ap = ap.astype(np.float64)
+        G, mag = fn @ ap.T, np.abs(fn) @ np.abs(ap).T
+    g = F * U32 / (1 - F * U32)
+    return G, g * mag + U32 * np.abs(G)
+
+
+def compress64_case(c):
+    return compress64_rows(c["f"], c["ap"], c["fmax"])
+
+
+def compress64(name):
     if name not in _C64:
-        c = case(name)
-        fn = normalise(c["f"], c["fmax"]).astype(np.float64)
-        if c["ap"] is None:
-            G, mag = fn, np.abs(fn)
-        else:
-            ap = c["ap"].astype(np.float64)
-            G, mag = fn @ ap.T, np.abs(fn) @ np.abs(ap).T
-        g = c["F"] * U32 / (1 - c["F"] * U32)
-        _C64[name] = (G, g * mag + U32 * np.abs(G))
+        _C64[name] = compress64_case(case(name))
     return _C64[name]
 
 
@@ -204,47 +228,53 @@ def _fma32(a, b, acc):
 
 
 def restate32(name):
-    """The route in fp32 -> scores in the oracle's layout (mode, model, position)."""
     if name not in _R32:
-        c = case(name)
-        sb, M, r, D = c["sb"], c["M"], c["r"], c["D"]
-        fn = normalise(c["f"], c["fmax"])
-        if c["ap"] is None:
-            G = fn
-        else:
-            G = np.zeros((fn.shape[0], D), np.float32)
-            for j in range(c["F"]):  # ascending j
-                G = _fma32(fn[:, j:j + 1], c["ap"][None, :, j], G)
-        gv = G.reshape(sb[2], sb[1], sb[0], D)
-        ev = c["ex"].astype(np.int64).reshape(sb[2], sb[1], sb[0])
-        q = c["axis_q"].reshape(M * r, D)
-        out = []
-        for _, r3, e in modes(sb, c["box"], c["rotate"]):
-            gate = _box_sum(ev, r3, e) > c["thr"]
-            fb = _box_sum(gv, r3, e)  # float32 adds from 0 in (dz, dy, dx) order
-            P = fb.shape[0]
-            ff = np.zeros(P, np.float32)
-            t = np.zeros((M * r, P), np.float32)
-            for d in range(D):  # ascending d
-                ff = _fma32(fb[:, d], fb[:, d], ff)
-                t = _fma32(q[:, d:d + 1], fb[None, :, d], t)
-            t = t.reshape(M, r, P)
-            q2 = np.zeros((M, P), np.float32)
-            for i in range(r):
-                q2 = _fma32(t[:, i], t[:, i], q2)
-            with np.errstate(divide="ignore", invalid="ignore"):
-                sc = np.sqrt(q2.astype(np.float64)) / np.sqrt(ff.astype(np.float64))[None, :]
-            sc[:, ~gate] = -1.0
-            out.append(sc.reshape(-1))
-        _R32[name] = np.concatenate(out)
+        _R32[name] = restate32_case(case(name))
     return _R32[name]
 
 
+def restate32_case(c):
+    """The route in fp32 -> scores in the oracle's layout (mode, model, position)."""
+    sb, M, r, D = c["sb"], c["M"], c["r"], c["D"]
+    fn = normalise(c["f"], c["fmax"])
+    if c["ap"] is None:
+        G = fn
+    else:
+        G = np.zeros((fn.shape[0], D), np.float32)
+        for j in range(c["F"]):  # ascending j
+            G = _fma32(fn[:, j:j + 1], c["ap"][None, :, j], G)
+    gv = G.reshape(sb[2], sb[1], sb[0], D)
+    ev = c["ex"].astype(np.int64).reshape(sb[2], sb[1], sb[0])
+    q = c["axis_q"].reshape(M * r, D)
+    out = []
+    for _, r3, e in modes(sb, c["box"], c["rotate"]):
+        gate = _box_sum(ev, r3, e) > c["thr"]
+        fb = _box_sum(gv, r3, e)  # float32 adds from 0 in (dz, dy, dx) order
+        P = fb.shape[0]
+        ff = np.zeros(P, np.float32)
+        t = np.zeros((M * r, P), np.float32)
+        for d in range(D):  # ascending d
+            ff = _fma32(fb[:, d], fb[:, d], ff)
+            t = _fma32(q[:, d:d + 1], fb[None, :, d], t)
+        t = t.reshape(M, r, P)
+        q2 = np.zeros((M, P), np.float32)
+        for i in range(r):
+            q2 = _fma32(t[:, i], t[:, i], q2)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            sc = np.sqrt(q2.astype(np.float64)) / np.sqrt(ff.astype(np.float64))[None, :]
+        sc[:, ~gate] = -1.0
+        out.append(sc.reshape(-1))
+    return np.concatenate(out)
+
+
 def box_norms64(name):
+    return box_norms64_case(case(name), compress64(name)[0])
+
+
+def box_norms64_case(c, G64):
     """Float64 norms of the compressed box rows, every scheduled mode (scan order)."""
-    c = case(name)
     sb = c["sb"]
-    gv = compress64(name)[0].reshape(sb[2], sb[1], sb[0], -1)
+    gv = G64.reshape(sb[2], sb[1], sb[0], -1)
     return [np.sqrt((_box_sum(gv, r3, e) ** 2).sum(1)) for _, r3, e in modes(sb, c["box"], c["rotate"])]
 
 
